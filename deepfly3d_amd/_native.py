@@ -72,6 +72,17 @@ PROTOTYPES = {
     "df3d_relayout_19_to_38": (c_int, [c_void_p, POINTER(c_int), c_int, c_void_p, c_void_p]),
     "df3d_triangulate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "df3d_triangulate_scaled": (c_int, [c_void_p, c_void_p, c_double, c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "df3d_heatmap_peaks": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_ps_proposals": (
+        c_int,
+        [POINTER(c_double), POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double,
+         c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "df3d_ps_solve": (
+        c_int,
+        [POINTER(c_int), POINTER(c_int), POINTER(c_double), c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
     "df3d_column_median": (c_int, [c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_void_p]),
     "df3d_procrustes_work_doubles": (c_longlong, [c_longlong]),
     "df3d_procrustes": (c_int, [c_void_p, c_longlong, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_longlong, c_void_p]),

@@ -40,7 +40,12 @@ def parse_cli_args(argv=None):
                         "fp32's exponent range, 8 significant bits: confidences ~6e-3 off on peaked maps, outside that tolerance.  f16 / f32s refuse weights beyond "
                         "the half range when they are loaded, and if an activation overflows on real images (an infinity or a NaN in any heat-map) the run "
                         "stops with an error that says so instead of writing df3d_result.pkl: rerun with --dtype f32")
+    p.add_argument("--auto-correct", dest="auto_correct", action="store_true",
+                   help="Correct the 2-D detections with the pictorial-structures model (bone-length prior, multi-view reprojection "
+                        "consistency over the heat-map peaks) before triangulating; the arg-max detections are kept as points2d_argmax")
     args = p.parse_args(argv)
+    if args.auto_correct and args.skip_estimation:
+        p.error("--auto-correct needs the heat-map peaks of this run's pose estimation: it cannot be combined with --skip-pose-estimation")
     inp = Path(args.input_folder).expanduser().resolve()
     args.output_folder = str(inp.with_name(inp.stem + "_df3d")) if args.output_folder is None else str(Path(args.output_folder).expanduser().resolve())
     args.input_folder = str(inp)
@@ -70,10 +75,15 @@ def run(args):
         return 0
     logger.info(f"\nWorking in {args.input_folder}")
     core = Core(args.input_folder, args.output_folder, args.num_images_max, args.order, dtype=args.dtype, device=getattr(args, "device", None))
+    auto = getattr(args, "auto_correct", False)
     if not args.skip_estimation:
-        core.pose2d_estimation(args.batch_size, args.pin_memory_disabled)
+        from .config import PICTORIAL_DEFAULTS
+
+        core.pose2d_estimation(args.batch_size, args.pin_memory_disabled, num_peaks=PICTORIAL_DEFAULTS["num_peaks"] if auto else 0)
         core.save()
     core.calibrate_calc(0, core.max_img_id)
+    if auto:
+        core.auto_correct()
     core.save()
     if args.video_2d or args.video_3d:
         # f4 (reference cli.py:305-321): frames drawn on the GPU (csrc/render.hip), encoded by ffmpeg when present.  Rank 0 draws and

@@ -31,6 +31,32 @@ TRACKED_SIDE = [BODY_COXA, COXA_FEMUR, FEMUR_TIBIA, TIBIA_TARSUS, TARSUS_TIP] * 
 TRACKED = TRACKED_SIDE * 2
 
 
+# ---- pictorial-structures correction.  The bone prior is the reference's `bone_param`
+# (df3d/skeleton_fly.py:252-261): length mean 0.9, deviation 0.3 for every joint that ends a leg segment, "no bone" for
+# body-coxa, antenna and stripe joints.
+BONE_MEAN, BONE_STD = 0.9, 0.3
+PICTORIAL_DEFAULTS = {
+    "num_peaks": 10,        # K: the reference's `num_peak` (at most 16)
+    "num_proposals": 64,    # M: proposals kept per (frame, joint) (at most 256)
+    "tau": 30.0,            # pixels: the number the reference carries as `alpha_reproj`
+    "w_reproj": 1.0,
+    "w_heatmap": 1.0,
+    "w_bone": 1.0,
+}
+
+
+def bone_tree():
+    """(parent [38] int32, bone [38, 2] float64 (mean, deviation)) from TRACKED: a coxa-femur, femur-tibia, tibia-tarsus or
+    tarsus-tip joint hangs from the joint before it; every other joint is a root.  6 chains of 5 joints + 8 single joints."""
+    parent = np.full(len(TRACKED), -1, dtype=np.int32)
+    bone = np.zeros((len(TRACKED), 2), dtype=np.float64)
+    for j, kind in enumerate(TRACKED):
+        if kind in (COXA_FEMUR, FEMUR_TIBIA, TIBIA_TARSUS, TARSUS_TIP):
+            parent[j] = j - 1
+            bone[j] = (BONE_MEAN, BONE_STD)
+    return parent, bone
+
+
 def load_calibration():
     """{cam_id: {R, tvec, intr, distort}} as in the reference's data/calib.pkl."""
     d = np.load(config["calib_path"])

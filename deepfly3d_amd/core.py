@@ -99,6 +99,9 @@ class Core:
         self.camera_ordering = self.setup_camera_ordering(camera_ordering)
         self.camNet = self.points2d = self.points3d = self.conf = None
         self._points2d_shard = None  # multi-GPU: this rank's frames of points2d (device tensor, normalised), kept for the sharded DLT
+        self.peaks = None             # (count, points, values) of pose2d_estimation(num_peaks=K), numpy [7, T, 19, ...]; rank 0
+        self.points2d_argmax = None   # the arg-max detections, once auto_correct() has replaced points2d
+        self._corrected = False       # every rank: auto_correct() ran (save() then triangulates on rank 0 alone)
         if os.path.exists(self.save_path):
             self._resume(self.save_path)
 
@@ -172,32 +175,81 @@ class Core:
         return os.path.join(self.output_folder, f"df3d_result_{flat}.pkl")
 
     # -- hot path -------------------------------------------------------------------------------------
-    def pose2d_estimation(self, batch_size: int = 8, disable_pin_memory: bool = False):
+    def pose2d_estimation(self, batch_size: int = 8, disable_pin_memory: bool = False, num_peaks: int = 0):
         """2-D pose on every frame of every camera, then the 19 -> 38 joint layout (reference :170-203).
 
         Under `torch.distributed` (one process per GPU) every rank processes a contiguous range of frames and ONE
-        gather brings the results to rank 0, which alone goes on to calibrate and save."""
+        gather brings the results to rank 0, which alone goes on to calibrate and save.
+        `num_peaks=K` > 0 also keeps the K best local maxima of every heat-map in `self.peaks` for auto_correct()."""
         from . import distributed as dd
 
         flip = [cam for idx, cam in enumerate(self.camera_ordering) if idx > 3]
         rank, world = dd.current()
         t0, t1 = dd.shard_range(self.num_images, world, rank)
-        points19, conf = inference_folder(
+        res = inference_folder(
             folder=self.input_folder, camera_ids_to_flip=flip, return_heatmap=False, return_confidence=True,
             max_img_id=self.max_img_id, batch_size=batch_size, disable_pin_memory=disable_pin_memory, dtype=self.dtype, device=self.device,
-            frame_range=(t0, t1), as_device_tensors=True,
+            frame_range=(t0, t1), as_device_tensors=True, return_peaks=num_peaks,
         )
+        points19, conf, peaks = res[0], res[1], list(res[2:])
         # 19 -> 38 layout on the device, then (N > 1) ONE gather of the device tensors: no host round trip before it
         points2d = ops.relayout_19_to_38(points19.contiguous(), self.camera_ordering)
         self._points2d_shard = points2d if world > 1 else None
+        self._corrected, self.points2d_argmax = False, None
         if dd.collective_needed(world):
-            gathered = dd.gather_packed([(points2d, 1), (conf, 1)], self.num_images)
+            gathered = dd.gather_packed([(points2d, 1), (conf, 1)] + [(p, 1) for p in peaks], self.num_images)
             self.is_primary = rank == 0
             if gathered is None:
-                self.points2d = self.conf = None
+                self.points2d = self.conf = self.peaks = None
                 return
-            points2d, conf = gathered
+            points2d, conf, peaks = gathered[0], gathered[1], gathered[2:]
         self.points2d, self.conf = points2d.cpu().numpy(), conf.cpu().numpy()
+        self.peaks = tuple(p.cpu().numpy() for p in peaks) if peaks else None
+
+    def auto_correct(self, **params):
+        """Pictorial-structures correction of the 2-D detections on the device: replaces `points2d` and the
+        camera network's points by the corrected detections and keeps the arg-max ones in `points2d_argmax`.  Needs calibrated
+        cameras (calibrate_calc) and the peaks of pose2d_estimation(num_peaks=K).  `params` override config.PICTORIAL_DEFAULTS
+        (num_proposals, tau, w_reproj, w_heatmap, w_bone; num_peaks is fixed by the peaks kept).  Multi-GPU: every rank calls
+        this, rank 0 solves, a failure there is raised on every rank (`distributed.agree`)."""
+        from . import distributed as dd
+        from .config import PICTORIAL_DEFAULTS
+
+        error = None
+        if self.is_primary:
+            try:
+                unknown = set(params) - set(PICTORIAL_DEFAULTS) - {"chunk_frames"}
+                if unknown:
+                    raise TypeError(f"auto_correct: unknown parameters {sorted(unknown)}")
+                if self.camNet is None or not self.camNet.has_calibration():
+                    raise RuntimeError("auto_correct needs calibrated cameras: run calibrate_calc() first")
+                if self.peaks is None or self.points2d is None or self.peaks[0].shape[1] != self.points2d.shape[1]:
+                    raise RuntimeError("auto_correct needs the heat-map peaks of this recording: run pose2d_estimation(num_peaks=K) first")
+                self._auto_correct_primary(params)
+            except Exception as e:  # noqa: BLE001  (re-raised by agree, on every rank)
+                error = e
+        dd.agree(error, "auto_correct")
+        self._corrected = True
+
+    def _auto_correct_primary(self, params):
+        from .config import PICTORIAL_DEFAULTS
+
+        p = {**PICTORIAL_DEFAULTS, **params}
+        if "num_peaks" in params and int(params["num_peaks"]) != self.peaks[1].shape[3]:
+            raise ValueError(f"num_peaks={params['num_peaks']}, but pose2d_estimation kept {self.peaks[1].shape[3]} peaks per heat-map")
+        _native.require_gpu()
+        dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
+        count, pts, vals = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in self.peaks)
+        argmax2d = self.points2d_argmax if self.points2d_argmax is not None else self.points2d
+        am = torch.from_numpy(np.ascontiguousarray(argmax2d, dtype=np.float64)).to(dev)
+        P = np.stack([c.P for c in self.camNet.cam_list])
+        res = ops.pictorial_correct(P, self.camera_ordering, am, count, pts, vals, self.image_shape, num_proposals=p["num_proposals"], tau=p["tau"],
+                                    w_reproj=p["w_reproj"], w_heatmap=p["w_heatmap"], w_bone=p["w_bone"], chunk_frames=p.get("chunk_frames", 4096))
+        self.points2d_argmax = np.array(argmax2d, dtype=np.float64, copy=True)
+        self.points2d = res.points2d.cpu().numpy()
+        np.copyto(self.camNet.points2d, self.points2d * self.image_shape[::-1])
+        changed = int((self.points2d != self.points2d_argmax).any(axis=-1).sum())
+        print(f"Auto-correction changed {changed} detections; mean minimum energy per frame {float(res.energy.mean()) if res.energy.numel() else 0.0:.4f}")
 
     def calibrate_calc(self, min_img_id, max_img_id):
         """Bundle adjustment from the shipped initial calibration (reference :229-250; like the reference the
@@ -301,7 +353,9 @@ class Core:
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369)."""
         from . import distributed as dd
 
-        pts3d_sharded = self._triangulate_sharded() if dd.current()[1] > 1 else None   # a collective: every rank takes part
+        # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
+        # triangulates every frame itself -- every rank knows that it ran (the flag is set on all of them) and takes this branch
+        pts3d_sharded = self._triangulate_sharded() if dd.current()[1] > 1 and not getattr(self, "_corrected", False) else None
         error = None
         if self.is_primary:
             try:
@@ -325,6 +379,8 @@ class Core:
             logger.debug("Triangulation skipped.")
         result["camera_ordering"] = self.camera_ordering
         result["heatmap_confidence"] = self.conf
+        if getattr(self, "_corrected", False) and self.points2d_argmax is not None:
+            result["points2d_argmax"] = np.copy(self.points2d_argmax)
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")

@@ -4,50 +4,16 @@
 // M = A^T A of the DLT system (rows x*P2 - P0, y*P2 - P1 of every camera that sees the joint) in
 // registers, diagonalises it with cyclic Jacobi rotations (fully unrolled, no scratch) and returns
 // the eigenvector of the smallest eigenvalue = the last right-singular vector of A
-// (oracle/geometry.py:triangulate_dlt).  M is pre-scaled by 1/trace so the
+// (oracle/geometry.py:triangulate_dlt).  The DLT and the re-layout rule live in geometry_dev.h, shared
+// with the pictorial-structures proposals (pictorial.hip).  M is pre-scaled by 1/trace so the
 // rotations work on O(1) numbers; scaling does not move eigenvectors.  Latency-bound: 5 KB/frame.
-#include "common.h"
+#include "geometry_dev.h"
 
 namespace {
 
-constexpr int MAX_CAM = 8;
-
-struct CamP {
-    double p[MAX_CAM][12];
-};
-
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&a)[4][4], double (&v)[4][4]) {
-    const double apq = a[P][Q];
-    if (apq == 0.0) return;
-    const double app = a[P][P], aqq = a[Q][Q];
-    // tiny off-diagonal relative to the diagonal: nothing to do
-    if (fabs(apq) <= 1e-300) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0);
-    const double s = t * c;
-    a[P][P] = app - t * apq;
-    a[Q][Q] = aqq + t * apq;
-    a[P][Q] = 0.0;
-    a[Q][P] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k != P && k != Q) {
-            const double akp = a[k][P], akq = a[k][Q];
-            a[k][P] = c * akp - s * akq;
-            a[P][k] = a[k][P];
-            a[k][Q] = s * akp + c * akq;
-            a[Q][k] = a[k][Q];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double vkp = v[k][P], vkq = v[k][Q];
-        v[k][P] = c * vkp - s * vkq;
-        v[k][Q] = s * vkp + c * vkq;
-    }
-}
+using df3d::CamP;
+using df3d::MAX_CAM;
+using df3d::jacobi_rotate;
 
 __global__ __launch_bounds__(256) void triangulate_kernel(CamP cams, const double* __restrict__ pts, int ncam,
                                                           long long TJ, double row_scale, double col_scale,
@@ -64,59 +30,10 @@ __global__ __launch_bounds__(256) void triangulate_kernel(CamP cams, const doubl
     int nviews = 0;
     for (int c = 0; c < ncam; ++c) {
         const double2 rc = *reinterpret_cast<const double2*>(pts + ((size_t)c * TJ + idx) * 2);
-        const double row = rc.x * row_scale, col = rc.y * col_scale;
-        if (row != 0.0 && col != 0.0) {
-            ++nviews;
-            double r0[4], r1[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                r0[k] = col * cams.p[c][8 + k] - cams.p[c][k];      // x * P[2] - P[0],  x = col_px
-                r1[k] = row * cams.p[c][8 + k] - cams.p[c][4 + k];  // y * P[2] - P[1],  y = row_px
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = i; j < 4; ++j) a[i][j] += r0[i] * r0[j] + r1[i] * r1[j];
-        }
+        DF3D_DLT_ADD_VIEW(a, nviews, cams.p[c], rc.x * row_scale, rc.y * col_scale);
     }
     double out0 = 0.0, out1 = 0.0, out2 = 0.0;
-    if (nviews >= 2) {
-        const double tr = a[0][0] + a[1][1] + a[2][2] + a[3][3];
-        const double inv = tr > 0.0 ? 1.0 / tr : 1.0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = i; j < 4; ++j) {
-                a[i][j] *= inv;
-                a[j][i] = a[i][j];
-            }
-        double v[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[i][j] = (i == j) ? 1.0 : 0.0;
-
-        for (int sweep = 0; sweep < 16; ++sweep) {
-            const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[0][3]) + fabs(a[1][2]) + fabs(a[1][3]) +
-                               fabs(a[2][3]);
-            if (off < 1e-40) break;
-            jacobi_rotate<0, 1>(a, v);
-            jacobi_rotate<0, 2>(a, v);
-            jacobi_rotate<0, 3>(a, v);
-            jacobi_rotate<1, 2>(a, v);
-            jacobi_rotate<1, 3>(a, v);
-            jacobi_rotate<2, 3>(a, v);
-        }
-        // eigenvector of the smallest eigenvalue (select with a compare chain: no dynamic indexing)
-        double best = a[0][0];
-        double e0 = v[0][0], e1 = v[1][0], e2 = v[2][0], e3 = v[3][0];
-        if (a[1][1] < best) { best = a[1][1]; e0 = v[0][1]; e1 = v[1][1]; e2 = v[2][1]; e3 = v[3][1]; }
-        if (a[2][2] < best) { best = a[2][2]; e0 = v[0][2]; e1 = v[1][2]; e2 = v[2][2]; e3 = v[3][2]; }
-        if (a[3][3] < best) { best = a[3][3]; e0 = v[0][3]; e1 = v[1][3]; e2 = v[2][3]; e3 = v[3][3]; }
-        out0 = e0 / e3;
-        out1 = e1 / e3;
-        out2 = e2 / e3;
-    }
+    DF3D_DLT_SOLVE(a, nviews, out0, out1, out2);
     X[idx * 3 + 0] = out0;
     X[idx * 3 + 1] = out1;
     X[idx * 3 + 2] = out2;
@@ -142,13 +59,8 @@ __global__ __launch_bounds__(256) void relayout_kernel(const float* __restrict__
     for (int k = 0; k < 7; ++k)
         if (ord.o[k] == cam) pos = k;
     double row = 0.0, col = 0.0;
-    const bool right = pos >= 0 && pos < 3;   // ordering[0:3] -> joints 0..18
-    const bool left = pos >= 4 && pos < 7;    // ordering[4:7] -> joints 19..37
-    int src = -1;
-    if (right && j < 19) src = j;
-    if (left && j >= 19) src = j - 19;
-    if (pos == 2 && j >= 15) src = -1;       // ordering[2] cannot see antenna / stripes
-    if (pos == 4 && j >= 19 + 15) src = -1;  // ordering[4] neither
+    bool left;
+    const int src = df3d::relayout_source(pos, j, &left);
     if (src >= 0) {
         const float2 p = *reinterpret_cast<const float2*>(in + (((size_t)cam * T + t) * 19 + src) * 2);
         row = (double)p.x;

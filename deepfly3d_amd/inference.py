@@ -193,12 +193,15 @@ DEVICE_BATCH_VIEWS = 896
 
 def inference_folder(folder, camera_ids_to_flip=(), return_heatmap=False, return_confidence=True, max_img_id=None,
                      batch_size=8, disable_pin_memory=False, dtype="f32", device=None, state_dict=None, frame_range=None,
-                     as_device_tensors=False):
+                     as_device_tensors=False, return_peaks=0):
     """Drop-in for df2d.inference.inference_folder (see module docstring).  Host work: listing and reading the
     files.  Device work: JPEG decode (csrc/jpeg.hip), flip / resize / normalise, hourglass, arg-max.
     `frame_range=(t0, t1)` (multi-GPU sharding) restricts the call to images t0 <= id < t1; the outputs then have
     t1 - t0 frames.  `as_device_tensors=True` returns the results as CUDA tensors instead of numpy arrays (the
-    multi-GPU path gathers them without a host round trip)."""
+    multi-GPU path gathers them without a host round trip).  `return_peaks=K` (1..16) also returns the K best local maxima of every
+    heat-map (ops.heatmap_peaks, run on each batch's heat-maps in the stream of its forward, before the next forward reuses them):
+    peak_count (7, T, 19) int32, peak_points (7, T, 19, K, 2) float32 normalised, peak_values (7, T, 19, K) float32, after the
+    other outputs.  With 0 (the default) the call is the one above."""
     from .jpeg import JpegFolderReader
 
     _native.require_gpu()
@@ -209,12 +212,18 @@ def inference_folder(folder, camera_ids_to_flip=(), return_heatmap=False, return
     t_first, t_stop = (0, max_img_id + 1) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
     T = max(0, t_stop - t_first)
     ncam = config["num_cameras"]
+    K = int(return_peaks)
+    if K < 0 or K > 16:
+        raise ValueError("return_peaks must be in [0, 16]")
     if T == 0 and frame_range is not None:  # an empty shard
         out = [np.zeros((ncam, 0, config["num_predict"], 2), np.float32)]
         if return_heatmap:
             out.append(np.zeros((ncam, 0, config["num_predict"], config["input_shape"][0] // 4, config["input_shape"][1] // 4), np.float32))
         if return_confidence:
             out.append(np.zeros((ncam, 0, config["num_predict"], 1), np.float32))
+        if K:
+            out += [np.zeros((ncam, 0, config["num_predict"]), np.int32), np.zeros((ncam, 0, config["num_predict"], K, 2), np.float32),
+                    np.zeros((ncam, 0, config["num_predict"], K), np.float32)]
         if as_device_tensors:
             dev0 = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
             out = [torch.from_numpy(a).to(dev0) for a in out]
@@ -227,6 +236,11 @@ def inference_folder(folder, camera_ids_to_flip=(), return_heatmap=False, return
     conf = torch.empty((ncam, T, config["num_predict"], 1), dtype=torch.float32, device=dev)
     points_flat, conf_flat = points.view(ncam * T, config["num_predict"], 2), conf.view(ncam * T, config["num_predict"], 1)
     heat = [] if return_heatmap else None
+    if K:
+        peaks = (torch.empty((ncam, T, config["num_predict"]), dtype=torch.int32, device=dev),
+                 torch.empty((ncam, T, config["num_predict"], K, 2), dtype=torch.float32, device=dev),
+                 torch.empty((ncam, T, config["num_predict"], K), dtype=torch.float32, device=dev))
+        peaks_flat = [p.view(ncam * T, *p.shape[2:]) for p in peaks]
     bs = max(1, int(batch_size), DEVICE_BATCH_VIEWS if not return_heatmap else 1)
     # a short first batch gets the GPU going while the reader threads fetch the first full-size one
     first = min(bs, 224)
@@ -262,11 +276,14 @@ def inference_folder(folder, camera_ids_to_flip=(), return_heatmap=False, return
                     ns = min(7, luma.shape[0])
                     engine.canary(exact, lambda e: e.forward_u8(luma[:ns], flips[0][:ns], PREPROCESS["mean"], PREPROCESS["std"], resize=PREPROCESS["resize"]),
                                   what=f"the first {ns} views of {folder}")
-                res = inference_frames(luma, flips[k], engine, return_heatmap=return_heatmap)
+                res = inference_frames(luma, flips[k], engine, return_heatmap=return_heatmap or K > 0)
                 # items are (camera, frame) in camera-major order = the flat order of points[ncam, T]: contiguous copies
                 lo = starts[k]
                 points_flat[lo : lo + len(chunk)] = res[0]
                 conf_flat[lo : lo + len(chunk), :, 0] = res[1]
+                if K:   # same stream, before the next forward overwrites the heat-maps
+                    for dst, src in zip(peaks_flat, ops.heatmap_peaks(res[2], K)):
+                        dst[lo : lo + len(chunk)] = src
                 if return_heatmap:
                     heat.append(res[2].cpu())
         done = True
@@ -281,4 +298,6 @@ def inference_folder(folder, camera_ids_to_flip=(), return_heatmap=False, return
         out.append(hm.to(dev) if as_device_tensors else hm.numpy())
     if return_confidence:
         out.append(host(conf))
+    if K:
+        out += [host(p) for p in peaks]
     return tuple(out) if len(out) > 1 else out[0]

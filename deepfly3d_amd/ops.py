@@ -155,3 +155,139 @@ def oneeuro_filter(series, freq=100.0, mincutoff=0.1, beta=2.0, dcutoff=1.0, fir
         "df3d_oneeuro_filter",
     )
     return out
+
+
+@_on_tensor_device
+def heatmap_peaks(heatmaps, k):
+    """heatmaps [n, J, H, W] float32 (cuda) -> (count [n, J] int32, points [n, J, k, 2] float32 (row/H, col/W), values [n, J, k]
+    float32): the k best local maxima of every plane (df3d_heatmap_peaks; peak 0 is heatmap_argmax's cell)."""
+    lib = _native.load()
+    _need(heatmaps, torch.float32, "heatmaps")
+    n, j, h, w = heatmaps.shape
+    k = int(k)
+    count = torch.empty((n, j), dtype=torch.int32, device=heatmaps.device)
+    pts = torch.empty((n, j, k, 2), dtype=torch.float32, device=heatmaps.device)
+    vals = torch.empty((n, j, k), dtype=torch.float32, device=heatmaps.device)
+    _native.check(lib.df3d_heatmap_peaks(heatmaps.data_ptr(), n, j, h, w, k, count.data_ptr(), pts.data_ptr(), vals.data_ptr(), _stream(heatmaps)),
+                  "df3d_heatmap_peaks")
+    return count, pts, vals
+
+
+def _pictorial_inputs(P, camera_ordering, points2d, peak_count, peak_pts, peak_val):
+    _need(points2d, torch.float64, "points2d")
+    _need(peak_count, torch.int32, "peak_count")
+    _need(peak_pts, torch.float32, "peak_pts")
+    if peak_val is not None:
+        _need(peak_val, torch.float32, "peak_val")
+    if points2d.dim() != 4 or points2d.shape[0] != 7 or tuple(points2d.shape[2:]) != (38, 2):
+        raise ValueError("points2d must be [7, T, 38, 2]")
+    T = points2d.shape[1]
+    k = peak_pts.shape[3] if peak_pts.dim() == 5 else -1
+    if tuple(peak_count.shape) != (7, T, 19) or tuple(peak_pts.shape) != (7, T, 19, k, 2) or (peak_val is not None and tuple(peak_val.shape) != (7, T, 19, k)):
+        raise ValueError("peaks must be count [7, T, 19], points [7, T, 19, K, 2] and values [7, T, 19, K] of the recording of points2d")
+    if any(t.device != points2d.device for t in (peak_count, peak_pts) + ((peak_val,) if peak_val is not None else ())):
+        raise ValueError("points2d and the peaks must be on one device")
+    order = (ctypes.c_int * 7)(*[int(c) for c in camera_ordering])
+    Ph = None
+    if P is not None:
+        Ph = np.ascontiguousarray(P.detach().cpu().numpy() if isinstance(P, torch.Tensor) else P, dtype=np.float64)
+        if Ph.shape != (7, 3, 4):
+            raise ValueError("P must be [7, 3, 4]")
+    return T, k, order, Ph
+
+
+@_on_tensor_device
+def ps_proposals(P, camera_ordering, points2d, peak_count, peak_pts, peak_val, image_shape, frames=None, num_proposals=64, tau=30.0,
+                 w_reproj=1.0, w_heatmap=1.0, X0=None):
+    """Proposals of the pictorial-structures model for frames [t0, t1) (default all), df3d_ps_proposals.  P [7, 3, 4] pixels of the
+    physical cameras; points2d [7, T, 38, 2] float64 cuda (the re-layout of the arg-max detections, normalised); peaks as
+    heatmap_peaks returns them per camera [7, T, 19, ...]; image_shape [W, H]; X0 = arg_max_points3d(P, points2d, image_shape), computed
+    when None.  Returns {count [n, 38], index, X, U, match [n, 38, M]}."""
+    lib = _native.load()
+    T, k, order, Ph = _pictorial_inputs(P, camera_ordering, points2d, peak_count, peak_pts, peak_val)
+    t0, t1 = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    n, m, dev = max(0, t1 - t0), int(num_proposals), points2d.device
+    kept = {"count": torch.zeros((n, 38), dtype=torch.int32, device=dev), "index": torch.zeros((n, 38, max(m, 0)), dtype=torch.int32, device=dev),
+            "X": torch.zeros((n, 38, max(m, 0), 3), dtype=torch.float64, device=dev), "U": torch.zeros((n, 38, max(m, 0)), dtype=torch.float64, device=dev),
+            "match": torch.zeros((n, 38, max(m, 0)), dtype=torch.int32, device=dev)}
+    dp = ctypes.POINTER(ctypes.c_double)
+    if X0 is None:
+        X0 = arg_max_points3d(Ph, points2d, image_shape)
+    if tuple(X0.shape) != (T, 38, 3) or X0.dtype != torch.float64 or X0.device != dev or not X0.is_contiguous():
+        raise ValueError("X0 must be the [T, 38, 3] float64 triangulation of points2d on its device")
+    _native.check(
+        lib.df3d_ps_proposals(Ph.ctypes.data_as(dp), order, X0.data_ptr(), peak_count.data_ptr(), peak_pts.data_ptr(), peak_val.data_ptr(), T, t0, t1 - t0,
+                              k, m, float(image_shape[1]), float(image_shape[0]), float(tau), float(w_reproj), float(w_heatmap), kept["count"].data_ptr(),
+                              kept["index"].data_ptr(), kept["X"].data_ptr(), kept["U"].data_ptr(), kept["match"].data_ptr(), _stream(points2d)),
+        "df3d_ps_proposals",
+    )
+    return kept
+
+
+@_on_tensor_device
+def ps_solve(camera_ordering, points2d, peak_count, peak_pts, kept, frames=None, w_bone=1.0, out=None):
+    """Exact min-sum over the skeleton's bone tree (config.bone_tree) on the kept proposals of frames [t0, t1), df3d_ps_solve.
+    Writes those frames of out = (points2d [7, T, 38, 2], choice [T, 38] int32, energy [T] float64), allocated when None, and
+    returns it."""
+    from .config import bone_tree
+
+    lib = _native.load()
+    T, k, order, _ = _pictorial_inputs(None, camera_ordering, points2d, peak_count, peak_pts, None)
+    t0, t1 = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    n, m, dev = max(0, t1 - t0), int(kept["index"].shape[-1]), points2d.device
+    for name in ("count", "index", "X", "U", "match"):
+        if kept[name].shape[:2] != (n, 38) or kept[name].device != dev:
+            raise ValueError(f"kept[{name!r}] does not belong to frames [{t0}, {t1})")
+    if out is None:
+        out = (points2d.clone(), torch.zeros((T, 38), dtype=torch.int32, device=dev), torch.zeros((T,), dtype=torch.float64, device=dev))
+    parent, bone = bone_tree()
+    par = (ctypes.c_int * 38)(*[int(p) for p in parent])
+    bone = np.ascontiguousarray(bone, dtype=np.float64)
+    work = torch.empty((max(1, 38 * n),), dtype=torch.float64, device=dev)
+    _native.check(
+        lib.df3d_ps_solve(order, par, bone.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(w_bone), points2d.data_ptr(), peak_count.data_ptr(),
+                          peak_pts.data_ptr(), T, t0, n, k, m, kept["count"].data_ptr(), kept["index"].data_ptr(), kept["X"].data_ptr(), kept["U"].data_ptr(),
+                          kept["match"].data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), work.data_ptr(), work.numel(), _stream(points2d)),
+        "df3d_ps_solve",
+    )
+    return out
+
+
+@_on_tensor_device
+def arg_max_points3d(P, points2d, image_shape):
+    """[T, 38, 3]: df3d_triangulate_scaled of the normalised points2d [7, T, 38, 2] (pixels = points2d * (H, W), as
+    CameraNetwork.triangulate sees them) -- the correction's proposal 0, bit for bit what the uncorrected run triangulates."""
+    lib = _native.load()
+    _need(points2d, torch.float64, "points2d")
+    Ph = np.ascontiguousarray(P.detach().cpu().numpy() if isinstance(P, torch.Tensor) else P, dtype=np.float64)
+    ncam, T, J, _ = points2d.shape
+    X = torch.empty((T, J, 3), dtype=torch.float64, device=points2d.device)
+    _native.check(lib.df3d_triangulate_scaled(Ph.ctypes.data_as(ctypes.c_void_p), points2d.data_ptr(), float(image_shape[1]), float(image_shape[0]), ncam, T, J,
+                                              X.data_ptr(), _stream(points2d)), "df3d_triangulate_scaled")
+    return X
+
+
+class PictorialResult:
+    """What `pictorial_correct` returns (device tensors): points2d [7, T, 38, 2] float64 normalised (the corrected detections),
+    choice [T, 38] int32 (the chosen proposal of every joint; 0 = the arg-max DLT), energy [T] float64 (each frame's minimum)."""
+
+    def __init__(self, points2d, choice, energy):
+        self.points2d, self.choice, self.energy = points2d, choice, energy
+
+
+def pictorial_correct(P, camera_ordering, points2d, peak_count, peak_pts, peak_val, image_shape, num_proposals=64, tau=30.0, w_reproj=1.0,
+                      w_heatmap=1.0, w_bone=1.0, chunk_frames=4096):
+    """Pictorial-structures correction of the arg-max detections: proposals, then the exact solve, in chunks of
+    `chunk_frames` frames so that the proposal storage stays bounded (~38 M 40 B per frame).  Arguments as ps_proposals."""
+    T = points2d.shape[1]
+    out = None
+    chunk = max(1, int(chunk_frames))
+    X0 = arg_max_points3d(P, points2d, image_shape) if T else None
+    for t0 in range(0, T, chunk):
+        t1 = min(T, t0 + chunk)
+        kept = ps_proposals(P, camera_ordering, points2d, peak_count, peak_pts, peak_val, image_shape, (t0, t1), num_proposals, tau, w_reproj, w_heatmap, X0)
+        out = ps_solve(camera_ordering, points2d, peak_count, peak_pts, kept, (t0, t1), w_bone, out)
+    if out is None:   # an empty recording: validate the arguments all the same
+        kept = ps_proposals(P, camera_ordering, points2d, peak_count, peak_pts, peak_val, image_shape, (0, 0), num_proposals, tau, w_reproj, w_heatmap)
+        out = ps_solve(camera_ordering, points2d, peak_count, peak_pts, kept, (0, 0), w_bone, out)
+    return PictorialResult(*out)

@@ -147,6 +147,40 @@ int df3d_triangulate_scaled(const double* P, const double* pts_norm_dev, double 
                             int T, int J, double* X_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a6b pictorial-structures correction of the 2-D detections (the model is this project's own
+ *     specification, restated in float64 by tests/pictorial_oracle.py).  All three run asynchronously on `stream` and validate
+ *     their arguments before they touch the device.
+ * df3d_heatmap_peaks: the k (1..16) best local maxima of every [h, w] plane (powers of two, 64 <= h*w <= 8192), value descending then
+ *     flat index ascending.  A cell is a peak when its value is finite, > every finite 8-neighbour before it in row-major order and
+ *     >= every finite one after it; peak 0 is then df3d_heatmap_argmax's cell whenever the plane's maximum is finite.
+ *     count_dev [n, joints] int32 (<= k); pts_dev [n, joints, k, 2] float32 (row / h, col / w); val_dev [n, joints, k] float32;
+ *     unused slots are zero.
+ * df3d_ps_proposals: frames [t0, t0 + tn) of a T-frame recording.  P_host [7, 3, 4] HOST float64 (pixels, physical cameras),
+ *     ordering_host[7] (camera_ordering), X0_dev [T, 38, 3] float64 = df3d_triangulate_scaled(P, argmax2d, img_h, img_w) of the
+ *     re-layout of the arg-max detections (proposal 0: it IS df3d_triangulate's point), peak_*_dev [7, T, 19, ...]
+ *     (df3d_heatmap_peaks of the network's planes), img_h / img_w the image size in pixels.  Per (frame, joint): proposal 0,
+ *     proposal 1 + q k^2 + i k + j = the two-view DLT of peak i and peak j of the q-th pair of the cameras that see the joint;
+ *     U = sum over those cameras of w_reproj min(d, tau)^2 / tau^2 - w_heatmap h (d, h: distance to and value of the nearest
+ *     peak).  Kept: proposal 0, then the m - 1 (m <= 256) lowest U, ties to the lower index.  Outputs [tn, 38] kept_count,
+ *     [tn, 38, m] kept_index (proposal index), kept_X [.., 3], kept_U, kept_match (byte a = the peak matched in the a-th seeing camera).
+ * df3d_ps_solve: exact min-sum over the tree parent_host[38] (-1 = none; every joint parents at most one joint) with the bone
+ *     cost w_bone ((|X_parent - X_j| - mu_j) / sigma_j)^2, bone_host [38, 2] = (mu, sigma), on df3d_ps_proposals' kept sets.
+ *     Writes frames [t0, t0 + tn) of points2d_dev [7, T, 38, 2] (the matched peaks, un-flipped as the re-layout does; entries
+ *     of cameras that do not see a joint copied from argmax2d), choice_dev [T, 38] (chosen proposal index) and energy_dev [T].
+ *     work_dev: >= 38 * tn doubles.
+ * ---------------------------------------------------------------------------------------------- */
+int df3d_heatmap_peaks(const float* hm_dev, int n, int joints, int h, int w, int k, int* count_dev, float* pts_dev, float* val_dev,
+                       void* stream);
+int df3d_ps_proposals(const double* P_host, const int* ordering_host, const double* X0_dev, const int* peak_count_dev,
+                      const float* peak_pts_dev, const float* peak_val_dev, int T, int t0, int tn, int k, int m, double img_h,
+                      double img_w, double tau, double w_reproj, double w_heatmap, int* kept_count_dev, int* kept_index_dev,
+                      double* kept_X_dev, double* kept_U_dev, int* kept_match_dev, void* stream);
+int df3d_ps_solve(const int* ordering_host, const int* parent_host, const double* bone_host, double w_bone, const double* argmax2d_dev,
+                  const int* peak_count_dev, const float* peak_pts_dev, int T, int t0, int tn, int k, int m, const int* kept_count_dev,
+                  const int* kept_index_dev, const double* kept_X_dev, const double* kept_U_dev, const int* kept_match_dev,
+                  double* points2d_dev, int* choice_dev, double* energy_dev, double* work_dev, size_t work_doubles, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a9  per-side Procrustes registration to the template pose + the `Core.get_points3d` chain.
  *     Replaces reference df3d/procrustes.py:51-151 (`procrustes_seperate`, call site df3d/core.py:358,340),
  *     df3d/plot_util.py:85-91 (`normalize_pose_3d`, call site core.py:341) and df3d/signal_util.py:69-100
