@@ -368,7 +368,10 @@ def _cli(launcher, folder, env, root, extra=()):
         return pickle.load(f)
 
 
-def test_cli_auto_correct_matches_the_oracle(native_lib, cuda, tmp_path, golden_dir, monkeypatch):
+@pytest.mark.parametrize("order", [ORDER, [6, 5, 4, 3, 2, 1, 0]], ids=["identity", "rev"])
+def test_cli_auto_correct_matches_the_oracle(native_lib, cuda, tmp_path, golden_dir, monkeypatch, order):
+    """--order 6 5 4 3 2 1 0 (a rig ordering of core._KNOWN_ORDERINGS) on the sample recording: the flip list pose2d_estimation
+    derives from the ordering, the re-layout and auto_correct together."""
     from deepfly3d_amd.config import bone_tree
     from deepfly3d_amd.inference import inference_folder
     from oracle import geometry as og
@@ -376,19 +379,20 @@ def test_cli_auto_correct_matches_the_oracle(native_lib, cuda, tmp_path, golden_
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DF3D_SYNTHETIC_WEIGHTS="0", PYTHONPATH=root)
     folder = _sample_folder(tmp_path, golden_dir)
-    res = _cli([sys.executable, "-m", "deepfly3d_amd.cli"], folder, env, root)
+    res = _cli([sys.executable, "-m", "deepfly3d_amd.cli"], folder, env, root, extra=("--order", *map(str, order)))
     g3 = np.load(f"{golden_dir}/golden_3d.npz")
     keys = list(res.keys())
     assert [str(k) for k in keys] == [str(k) for k in g3["key_order"]] + ["points2d_argmax"]
+    assert list(res["camera_ordering"]) == order
     # the oracle's solve on the peaks inference_folder returns, with the cameras the run calibrated
     monkeypatch.setenv("DF3D_SYNTHETIC_WEIGHTS", "0")
-    _, _, count, pts, vals = inference_folder(folder, camera_ids_to_flip=[4, 5, 6], max_img_id=1, return_peaks=10)
+    _, _, count, pts, vals = inference_folder(folder, camera_ids_to_flip=[order[i] for i in (4, 5, 6)], max_img_id=1, return_peaks=10)
     P = og.projection_matrices(*(np.stack([res[c][n] for c in range(7)]) for n in ("R", "tvec", "intr")))
     am = res["points2d_argmax"]
-    assert np.array_equal(am, og.relayout_19_to_38(pts[:, :, :, 0], ORDER))
-    kept = po.proposals(P, ORDER, am, count, pts, vals, IMAGE_SHAPE, 10, 64)["kept"]
+    assert np.array_equal(am, og.relayout_19_to_38(pts[:, :, :, 0], order))
+    kept = po.proposals(P, order, am, count, pts, vals, IMAGE_SHAPE, 10, 64)["kept"]
     parent, bone = bone_tree()
-    o_pts, _, _, margin = po.solve(kept, ORDER, am, count, pts, parent, bone)
+    o_pts, _, _, margin = po.solve(kept, order, am, count, pts, parent, bone)
     clear = margin > 1e-9   # joints whose optimum beats every other choice by more than 1e-9 (FMA rounding may flip closer ties)
     assert clear.mean() > 0.5
     assert np.array_equal(res["points2d"][:, clear], o_pts[:, clear])
