@@ -12,7 +12,13 @@ fp32 with seeded synthetic weights (no checkpoints offline); fixed calib.pkl cam
 N > 1: every rank owns its own frame range (weak scaling) and the per-frame results are gathered to rank 0 once
 (RCCL, one packed `dist.gather`), inside the timed region.  Rank 0 prints ONE JSON line.
 
-The line's headline is configs[1] (fp32).  At N = 1 the same process then times, under the same driver clock,
+A plain run does only what its headline needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.
+Everything else below -- the attached legs, the roofline pass, the cpu_baseline and the side file with the whole record -- runs
+with --full only (`extra_measurements`).
+
+    python bench.py --gpus 1 --steps 8 --warmup 2 --full
+
+The line's headline is configs[1] (fp32).  With --full, at N = 1 the same process then times, under the same driver clock,
   config1_f32_split  configs[1] through the f32s engine: float32 tensors, weights and accumulation, the products as two-way IEEE-half splits on
                  the 16-bit matrix pipe (gfx950's exact-fp32 MFMA runs at 1/16 of the half-precision rate); NOT the headline -- its heat-maps differ
                  from the exact-fp32 engine's by the `max_rel_diff_vs_f32_engine` printed beside it (same 5e-5 test tolerance, tests/test_gpu_hourglass.py)
@@ -31,7 +37,7 @@ is BASELINE's 8-GPU table in one shot: configs[3] (with --ba-window: configs[4])
 ranks, one packed gather, Procrustes over the whole sequence on rank 0, all inside the timed region; `"scaling": "strong"`, per-rank frames
 and rank 0's tail (gather / Procrustes ms) on the line.  N = 1 runs the whole stream on one GPU (the same pipeline as the default line).
 
-Roofline fractions (per kernel and for the dominant one), spelled out because a fused kernel has more than one byte count:
+Roofline fractions (--full; per kernel and for the dominant one), spelled out because a fused kernel has more than one byte count:
   frac_mfma      FLOPs EXECUTED on the matrix pipe / time / dense MFMA peak of the dtype (the Winograd tail of the fp32 engine executes 16/36 of a
                  3x3's direct FLOPs: its direct-equivalent rate is printed beside the fraction, never priced against the peak)
   frac_hbm_min   (inputs read once + outputs written once, intermediates on chip) / time / 8 TB/s -- the least the launch can move
@@ -89,19 +95,24 @@ def parse(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the multi-rank control flow (no GPU, gloo): the pipeline is a stub that stamps every frame with its global index, "
                          "everything else -- shards, batches per rank, window bookkeeping, the packed gather -- is the real code; rank 0 checks the gathered sequence")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: the roofline pass, the attached legs and the cpu_baseline (each where the "
+                         "run's configuration has it, less what a --no-* option drops), and write the whole record to the side file (--tables); "
+                         "without it a run sets up, warms up, times its steps, dumps (--dump-outputs) and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--no-bf16-leg", "--no-legs", dest="no_legs", action="store_true",
-                    help="skip the attached legs (configs[2] in bf16 and f16, the configs[4] share)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample")
+                    help="with --full: skip the attached legs (configs[2] in bf16 and f16, the configs[4] share)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample (--full)")
     ap.add_argument("--verify", action="store_true",
                     help="after the timed region rank 0 recomputes a strided sample of EVERY rank's frames on its own GPU (the peers' frame pools are "
                          "seeded by rank, so rank 0 can regenerate them) and requires the gathered records to be bit-identical; the line then carries "
                          "`verify`, `per_rank_frames_per_s`, `gather_ms`, `rccl_world`")
-    ap.add_argument("--full", action="store_true",
+    ap.add_argument("--whole-record", action="store_true",
                     help="print the whole record (per-kernel tables, legends, long workload texts: tens of KB) instead of the <= 4 KB line")
     ap.add_argument("--tables", default=None,
-                    help="where the whole record goes beside the short line (default gpurun_out/bench_full_<dtype>.json; '-' = nowhere)")
+                    help="where the whole record goes beside the short line ('-' = nowhere); by default only --full writes it, as "
+                         "bench_full_<dtype>.json in the folder emit() names")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step (rank 0's points2d, heatmap_confidence, "
                          "points3d; with --ba-window also the last window's cameras) as DIR/<name>.npy, float32 / float64")
@@ -794,7 +805,7 @@ _LEG_ROOF_KEEP = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffi
 def short_line(full):
     """The ONE stdout line, <= 4 KB (tests/test_gpu_bench.py asserts the size): the headline, `config` with a one-sentence workload, `roofline`
     without the per-kernel table, every leg as its rate + its dominant kernel's roofline + its one-off fields, `cpu_baseline`.  Everything
-    dropped here is in the side file the line names (`tables`)."""
+    dropped here is in the side file the line names (`tables`), which --full writes."""
     out = {}
     for k, v in full.items():
         if k == "roofline":
@@ -817,8 +828,11 @@ def short_line(full):
 
 
 def emit(full, a):
-    """Rank 0's output: the whole record to the side file, the short line (or, with --full, the whole record) as the one stdout line."""
+    """Rank 0's output: with --full (or --tables PATH) the whole record to the side file, the short line (or, with --whole-record, the
+    whole record) as the one stdout line."""
     path = a.tables
+    if path is None and not a.full:
+        path = "-"
     if path is None:
         path = os.path.join(ROOT, "gpurun_out", f"bench_full_{full['dtype']}.json")
     if path != "-":
@@ -830,7 +844,7 @@ def emit(full, a):
             full["tables"] = os.path.relpath(path, ROOT)
         except OSError as e:   # a read-only tree: the line still goes out
             full["tables"] = f"not written: {e!r}"
-    print(json.dumps(full if a.full else short_line(full)), flush=True)
+    print(json.dumps(full if a.whole_record else short_line(full)), flush=True)
 
 
 def strong_plan(stream_frames, world, align, frames_per_step):
@@ -841,6 +855,22 @@ def strong_plan(stream_frames, world, align, frames_per_step):
     ranges = dd.all_ranges(stream_frames, world, align)
     per_rank = [(t0, t1, -(-(t1 - t0) // frames_per_step)) for t0, t1 in ranges]
     return per_rank, max(b for _, _, b in per_rank)
+
+
+def extra_measurements(a, world):
+    """What the run measures beside its headline: nothing without --full.  With it, the roofline pass (per-kernel HIP events over steps
+    of its own), the attached legs (N = 1, plain fp32 configs[1] only) and the cpu_baseline (N = 1, weak scaling), less what a --no-*
+    option drops.  Pure: the CPU tests walk it."""
+    if not a.full:
+        return set()
+    out = set()
+    if not a.no_roofline:
+        out.add("roofline")
+    if a.dtype == "f32" and world == 1 and not a.no_legs and a.rank_share == 0 and a.ba_window == 0 and not a.strong:
+        out.add("legs")
+    if not a.no_cpu_baseline and world == 1 and a.rank_share == 0 and not a.strong:
+        out.add("cpu_baseline")
+    return out
 
 
 def main(argv=None):
@@ -907,13 +937,14 @@ def main(argv=None):
         ranges = [(t0, t1) for t0, t1, _ in shards] if a.strong else [(r * total_frames, (r + 1) * total_frames) for r in range(world)]
         verified = job.verify(ranges)
 
+    extras = extra_measurements(a, world)
     roof = None
-    if not a.no_roofline and rank == 0:
+    if "roofline" in extras and rank == 0:
         roof = job.roofline(a.dtype)
 
     # the attached legs (N = 1, plain configs[1] run only): same process, same driver clock
     legs = {}
-    if a.dtype == "f32" and world == 1 and not a.no_legs and a.rank_share == 0 and a.ba_window == 0 and not a.strong:
+    if "legs" in extras:
         legs["config1_f32_split"] = hourglass_leg(a, sd, "f32s", frames, calib, dev, total_frames, "BASELINE configs[1] with split products")
         legs["config2_bf16"] = hourglass_leg(a, sd, "bf16", frames, calib, dev, total_frames, "BASELINE configs[2]")
         legs["config2_f16"] = hourglass_leg(a, sd, "f16", frames, calib, dev, total_frames,
@@ -999,7 +1030,7 @@ def main(argv=None):
                 add_step_hbm(line["config"], roof, sec)
                 add_step_flops(line["config"], roof, sec, a.dtype)
         line.update(legs)
-        if not a.no_cpu_baseline and world == 1 and a.rank_share == 0 and not a.strong:
+        if "cpu_baseline" in extras:
             try:
                 line["cpu_baseline"] = cpu_baseline(sd, frames[:16].cpu(), calib, a.cpu_seconds)
             except Exception as e:  # the baseline is reporting only; never hide the GPU number

@@ -15,7 +15,7 @@ cd "$R"
 timeout ${PYTEST_TIMEOUT:-2000} python -m pytest tests -m gpu ${PYTEST_X--x} -q -rs --durations=15 ${PYTEST_EXTRA:-} >> "$OUT/pytest.log" 2>&1; echo "pytest rc=$?" >> "$OUT/pytest.log"
 tail -25 "$OUT/pytest.log"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$OUT/smoke.log" 2>&1; tail -2 "$OUT/smoke.log"
-timeout 600 python bench.py > "$OUT/bench_default.log" 2>&1
+timeout 600 python bench.py --full > "$OUT/bench_default.log" 2>&1
 python - <<PY
 import json
 l=[x for x in open("$OUT/bench_default.log") if x.startswith("{")]

@@ -7,8 +7,8 @@ TAG=${1:-r06}
 OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$R"
-python bench.py --tables "$OUT/f32_bench_full.json" > "$OUT/f32_bench.log" 2>&1
-python bench.py --dtype bf16 --no-cpu-baseline --tables "$OUT/bf16_bench_full.json" > "$OUT/bf16_bench.log" 2>&1
-python bench.py --dtype f16 --no-cpu-baseline --tables "$OUT/f16_bench_full.json" > "$OUT/f16_bench.log" 2>&1
-python bench.py --dtype f32s --no-cpu-baseline --tables "$OUT/f32s_bench_full.json" > "$OUT/f32s_bench.log" 2>&1
+python bench.py --full --tables "$OUT/f32_bench_full.json" > "$OUT/f32_bench.log" 2>&1
+python bench.py --dtype bf16 --full --no-cpu-baseline --tables "$OUT/bf16_bench_full.json" > "$OUT/bf16_bench.log" 2>&1
+python bench.py --dtype f16 --full --no-cpu-baseline --tables "$OUT/f16_bench_full.json" > "$OUT/f16_bench.log" 2>&1
+python bench.py --dtype f32s --full --no-cpu-baseline --tables "$OUT/f32s_bench_full.json" > "$OUT/f32s_bench.log" 2>&1
 tail -1 "$OUT/f32_bench.log" | cut -c1-400

@@ -1,5 +1,5 @@
-"""-m gpu: the bench.py contract executed -- the one JSON line at N = 1 (headline, roofline with every byte model, the
-attached 16-bit legs and the configs[4] share) and the N = 2 launch the driver uses (torch.distributed.run, here two ranks
+"""-m gpu: the bench.py contract executed -- the one JSON line at N = 1 (a plain run: the headline alone; --full: headline, roofline
+with every byte model, the attached 16-bit legs and the configs[4] share) and the N = 2 launch the driver uses (torch.distributed.run, here two ranks
 sharing the one GPU with gloo standing in for RCCL)."""
 import json
 import os
@@ -41,8 +41,25 @@ def _check_roofline(roof, dtype):
     assert dom["kernel"] == roof["kernel"] and dom["bytes_m1"] > dom["bytes_min"]   # a fused kernel: M1 charges more than the launch can move
 
 
-def test_default_line_has_every_leg_and_every_fraction(native_lib, cuda):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--frames-per-step", "32", "--cpu-seconds", "2"],
+def test_plain_line_is_the_headline_alone(native_lib, cuda, tmp_path):
+    """Without --full the run sets up, warms up, times its steps, dumps and prints the line: no roofline pass, no legs, no cpu_baseline,
+    no side file."""
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames-per-step", "32", "--dump-outputs", str(out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    d = _line(r.stdout)
+    assert {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+            "warmup_settle", "dumped_outputs"} == set(d)
+    assert d["metric"] == "frames/sec (7-view 2D->3D)" and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and "configs[1]" in d["config"]["workload"]
+    assert abs(d["value"] - 64 / (2 * d["ms_per_step"] * 1e-3)) < 1e-5 * d["value"]
+    assert d["dumped_outputs"] == {"points2d": [7, 32, 38, 2], "heatmap_confidence": [7, 32, 19], "points3d": [32, 38, 3]}
+    assert sorted(os.listdir(out)) == ["heatmap_confidence.npy", "points2d.npy", "points3d.npy"]
+
+
+def test_full_line_has_every_leg_and_every_fraction(native_lib, cuda):
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--frames-per-step", "32", "--cpu-seconds", "2", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     short = _line(r.stdout)

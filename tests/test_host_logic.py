@@ -179,6 +179,26 @@ def test_bench_strong_plan_covers_the_stream_for_every_world_size():
     assert [t1 - t0 for t0, t1, _ in per_rank] == [13000] * 4 + [12000] * 4 and steps == 102
 
 
+def test_bench_measures_nothing_beside_the_headline_without_full():
+    """bench.py: a plain run (any configuration, any --no-* option) adds no roofline pass, leg or cpu_baseline; --full adds each where
+    the configuration has it, and the --no-* options drop them again."""
+    import bench
+
+    every = ([], ["--dtype", "f16"], ["--rank-share", "8"], ["--ba-window", "1000"], ["--strong"], ["--verify"], ["--whole-record"],
+             ["--no-roofline", "--no-legs", "--no-cpu-baseline"])
+    for flags in every:
+        for world in (1, 2):
+            assert bench.extra_measurements(bench.parse(flags), world) == set(), (flags, world)
+    full = lambda *f, world=1: bench.extra_measurements(bench.parse(["--full", *f]), world)   # noqa: E731
+    assert full() == {"roofline", "legs", "cpu_baseline"} and full(world=2) == {"roofline"}
+    assert full("--dtype", "f16") == {"roofline", "cpu_baseline"} and full("--ba-window", "1000") == {"roofline", "cpu_baseline"}
+    assert full("--rank-share", "8") == {"roofline"} and full("--strong") == {"roofline"}
+    assert full("--no-roofline") == {"legs", "cpu_baseline"} and full("--no-legs") == {"roofline", "cpu_baseline"}
+    assert full("--no-cpu-baseline") == {"roofline", "legs"} and full("--no-roofline", "--no-legs", "--no-cpu-baseline") == set()
+    a = bench.parse(["--full"])
+    assert a.full and not a.whole_record and a.tables is None and not bench.parse([]).full
+
+
 def test_mjpeg_avi_writer_round_trip(tmp_path):
     """f4's fallback encoder (no ffmpeg in this image): Motion-JPEG in a RIFF/AVI container, header fields consistent with the
     frames written (count, size, rate), every frame recoverable."""
