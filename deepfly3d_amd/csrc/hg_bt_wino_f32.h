@@ -1,25 +1,32 @@
-// fp32 identity-skip bottleneck tail (3x3 -> 1x1 -> + x) with the 3x3 convolution as WINOGRAD F(2x2, 3x3) on the exact-fp32 MFMA
-// (round 6).  The exact-fp32 engine sits at the matrix pipe's roof (0.88 of 157.3 TFLOP/s, hg_bt_ring_f32.h), so the only way left to make
-// it faster is to issue fewer MFMAs: 82 % of the tail's MFMAs are the 3x3 done as direct implicit GEMM (9 taps x 128 x 128 per pixel);
-// Winograd does a 2x2 output patch with 16 instead of 36 multiplies per (cin, cout) pair -- the tail's MFMA count falls to 0.545.
+// fp32 identity-skip bottleneck tail (3x3 -> 1x1 -> + x) with the 3x3 convolution as WINOGRAD F(2x4, 3x3) on the exact-fp32 MFMA
+// (round 6: F(2x2, 3x3); round 7: F(2x4, 3x3)).  The exact-fp32 engine sits at the matrix pipe's roof, so the only way left to make it
+// faster is to issue fewer MFMAs.  Winograd does a 2 x 4 output patch with 4 x 6 = 24 instead of 72 multiplies per (cin, cout) pair: 3 per
+// output pixel (F(2x2): 4, direct: 9) -- the tail's MFMA cycles per tile fall from 2 816 x 64 (direct) to 98 304 (F(2x2)) to 81 920.
 //
-//   Y = A^T [ (G g G^T) (.) (B^T d B) ] A        d: 4x4 input patch of t1 (per channel), g: 3x3 weights (per cin, cout), Y: 2x2 outputs
+//   Y = A2^T [ (G2 g G4^T) (.) (B2^T d B4) ] A4      d: 4 x 6 input patch of t1 (per channel), g: 3x3 weights (per cin, cout), Y: 2 x 4 outputs
 //
-// summed over the 128 input channels INSIDE the transformed domain: 16 "positions" p = 4 i + j, each a plain GEMM
-//   M_p [128 cout x 32 patches] = U_p [128 cout x 128 cin] . V_p [128 cin x 32 patches]
-// over the 32 patches (4 x 8) of an 8 x 16 output tile.  U = G g G^T is transformed once at df3d_hg_set_weights (fp64, rounded once:
-// bt_wino_pack_kernel), V = B^T d B costs adds only, Y = A^T M A costs adds only.
+// F(2, 3) down the rows (points 0, 1, -1, inf), F(4, 3) along the columns (points 0, 1, -1, 1/2, -2, inf; the matrices and the numerics gate:
+// tests/test_wino24_numerics.py), summed over the 128 input channels INSIDE the transformed domain: 24 "positions" p = (i, j), each a GEMM
+//   M_p [128 cout x 16 patches] = U_p [128 cout x 128 cin] . V_p [128 cin x 16 patches]
+// over the 16 patches (4 x 4) of an 8 x 16 output tile.  U = G2 g G4^T is transformed once at df3d_hg_set_weights (fp64, rounded once:
+// bt_wino_pack_kernel), V = B2^T d B4 costs packed adds / FMAs with exact power-of-two and half-integer coefficients, Y = A2^T M A4 likewise.
 //
-// Mapping (one workgroup = one 8 x 16 tile as before, but ONE wave per SIMD: a wave holds 16 positions x 16 accumulator registers = 256):
-//   * wave w owns output channels 32 w .. 32 w + 31 for all 32 patches and all 16 positions: its output transform is in-lane;
-//   * K is walked in 16 chunks of 8 input channels.  Per chunk the four waves build V (16 positions x 8 channels x 32 patches = 16 KB,
-//     double-buffered in LDS) from the t1 halo tile -- every wave a quarter, one channel of one patch per lane: 16 ds_read_b32, 32 adds,
-//     16 ds_write_b32, under the MFMAs of the chunk before -- and each wave then runs 16 x 4 MFMAs: B = V_p (one ds_read_b128), A = its own
-//     1 KB fragment of U_p straight from global memory (L2-resident, 1 MB per bottleneck, prefetched one chunk = 16 fragments ahead:
-//     nothing is shared between waves on the weight side, so no LDS ring and no barrier for it);  ONE barrier per chunk (4 096 MFMA cycles);
-//   * t2 = relu(Y + b2) (b2 is the start value of position (1,1), which enters all four outputs with weight +1) crosses to the
-//     pixel-major mapping of phase 3 through LDS (64 KB in the dead t1 region), and phase 3 is hg_bt_ring_f32.h's, unchanged:
-//     W3 through the 4-slot LDS-DMA ring (which takes the dead V buffers' place), residual add, ADD2 / UP / pooled outputs.
+// Mapping (one workgroup = one 8 x 16 tile, ONE wave per SIMD, v_mfma_f32_16x16x4_f32: 32-cycle issue, 40-cycle dependent latency, so
+// consecutive MFMAs always go to different accumulators):
+//   * wave w owns output channels 32 w .. 32 w + 31 as two 16-row blocks m, for all 16 patches and all 24 positions: 48 accumulator tiles of
+//     4 registers = 192; its output transform is in-lane (lane: patch lane & 15, channels 32 w + 16 m + 4 (lane >> 4) + 0..3);
+//   * K is walked in 16 chunks of 8 input channels = 2 K steps s of 4.  Per chunk the four waves build V (24 positions x 8 channels x 16
+//     patches = 12 KB, three buffers in LDS) from the t1 halo tile -- lane = (patch, channel, row half h): 18 ds_read_b32, 12 + 20 packed ops,
+//     3 ds_write_b128, under the MFMAs of the chunk before -- and each wave then runs 6 passes (s, position pair pp) x 16 MFMAs: B = V_p (one
+//     ds_read_b128 = four positions), A = its own 1 KB fragment of U_p straight from global memory (L2-resident, 1.5 MB per bottleneck,
+//     requested WN_UBUF - 1 passes = 1 024 MFMA cycles ahead);  ONE barrier per chunk (3 072 MFMA cycles);
+//   * t2 = relu(Y + b2) (b2 is the start value of position (1,1), whose column of both A^T is all ones) crosses to the pixel-major mapping
+//     of phase 3 through LDS (64 KB in the dead t1 region), and phase 3 is hg_bt_ring_f32.h's, unchanged: W3 through the 4-slot LDS-DMA ring
+//     (which takes the dead V buffers' place), residual add, ADD2 / UP / pooled outputs.
+//
+// U stream: 96 passes x 16 KB.  Passes 0 .. 63 (1 MiB) sit in the block's Winograd slot (p.w2d, in front of W3), passes 64 .. 95 (512 KiB) in the
+// block's direct-form stage images (p.wstream, BRF_NSTAGE / L2F_NSTAGE x 8 KB = 832 KB): no launch of an engine with `wino` reads those images
+// (hourglass.hip, where they are packed), so the engine's buffer keeps its size.
 //
 // LDS: V / ring 32 KB | t1 halo tile 90 KB (both 64-channel halves; t2 later) | b3 1 KB = 125 952 B: one workgroup per CU.
 // Not bit-identical to the direct form (different products): the engine option `wino` selects it, the tests hold it to the
@@ -28,33 +35,46 @@
 #include "hg_bt_ring_f32.h"
 
 #ifndef WN_ABL
-#define WN_ABL 0   // development builds (scripts/build_variant.sh): ablation mask -- phase 2: 1 no U loads, 2 no input transform, 4 no chunk barrier, 8 no V fragment reads; the rest of a tile: 512 no patch reads, 1024 no V stores, 2048 no packed adds of the input transform; 16 no output transform, 32 no halo DMA for the next tile, 64 no residual / operand loads, 128 no output stores, 256 no phase-3 MFMAs
+#define WN_ABL 0   // development builds (scripts/build_variant.sh): ablation mask -- phase 2: 1 no U loads, 2 no input transform, 4 no chunk barrier; the rest of a tile: 512 no patch reads, 1024 no V stores, 2048 no packed ops of the input transform; 16 no output transform, 32 no halo DMA for the next tile, 64 no residual / operand loads, 128 no output stores, 256 no phase-3 MFMAs
 #endif
 
 namespace hgk {
 
 constexpr int WN_CHUNKS = 16;                          // K chunks of 8 input channels
-constexpr int WN_U_BYTES = WN_CHUNKS * 16 * 4 * 1024;  // [chunk][pass][row group][wave] x 1 KB MFMA A fragments = 1 MiB per bottleneck
+constexpr int WN_PASSES = 6;                           // per chunk: K step s (4 channels) x position pair pp (8 of the 24 positions)
+#ifndef WN_UBUF
+#define WN_UBUF 3   // U fragment buffers of a wave (a divisor of WN_PASSES): fragments are requested WN_UBUF - 1 passes ahead (6: hipcc
+                    // then moves more accumulators between registers inside the chunk loop)
+#endif
+constexpr int WN_PASS_BYTES = 4 * 4 * 1024;            // a pass: [wave 4][fragment 4] x 1 KB MFMA A fragments
+constexpr int WN_U_BYTES = 64 * WN_PASS_BYTES;         // passes 0 .. 63 in the Winograd slot: 1 MiB per bottleneck
+constexpr int WN_U2_BYTES = (WN_CHUNKS * WN_PASSES - 64) * WN_PASS_BYTES;   // passes 64 .. 95 in the direct-form stage images: 512 KiB
 constexpr int WN_W3_BYTES = BRF_W3_STAGES * BR_STAGE_BYTES;   // behind U: W3's 16 stage images with their rows permuted (bt_wino_pack_w3_kernel)
 constexpr int WN_STREAM_BYTES = WN_U_BYTES + WN_W3_BYTES;
 constexpr int WN_STREAM_BYTES_L2 = WN_U_BYTES + 2 * WN_W3_BYTES;   // layer2: U | W3 | Wd (the skip convolution's weights, rows permuted the same way)
-constexpr int WN_V_BYTES = 16 * 1024;                  // one V chunk: [channel 4][row group 4][channel quad 2][patch 32] x 16 bytes
-constexpr int WN_T1_OFF = 2 * WN_V_BYTES;              // = BR_RING_BYTES: the W3 ring reuses the V buffers
+constexpr int WN_V_BYTES = 12 * 1024;                  // one V chunk: [K step s 2][position group pg 6][channel k 4][patch slot 16] x 16 bytes
+constexpr int WN_T1_OFF = BR_RING_BYTES;               // the W3 ring reuses the V buffers
 constexpr int WN_T1_BYTES = 2 * BR_T1_BYTES;           // both 64-channel halves of the 10 x 18 halo tile (92 160)
 constexpr int WN_T2_BYTES = BT_TH * BT_TW * 512;       // t2 [128 pixels][128 channels] fp32 (65 536), inside the t1 region
 constexpr int WN_B3_OFF = WN_T1_OFF + WN_T1_BYTES;
 constexpr int WN_RING2_OFF = WN_B3_OFF + 1024 + 512;   // b3 [256] | b2 [128] | W3 ring slots 4 .. 7
 constexpr int WN_LDS_BYTES = WN_RING2_OFF + BR_RING_BYTES;
 static_assert(WN_LDS_BYTES <= 160 * 1024, "one workgroup per CU");
-static_assert(WN_T1_OFF == BR_RING_BYTES, "the W3 ring takes the V buffers' place");
+static_assert(WN_PASSES % WN_UBUF == 0 && WN_UBUF >= 2, "a chunk's passes use the same buffers in every chunk");
+static_assert(WN_V_BYTES <= BR_RING_BYTES / 2, "V buffers 0, 1 in the W3 ring's slots 0 .. 3, buffer 2 in slots 4 .. 7");
 static_assert(WN_T2_BYTES <= WN_T1_BYTES, "t2 lives in the t1 region");
+static_assert(WN_U2_BYTES <= BRF_NSTAGE * BR_STAGE_BYTES, "U's second part fits the direct-form stage images");
 
-// W2' [9][128 cout][128 cin] fp32 (bn3 folded) -> U stream.  One thread per (cout, cin): G g G^T in fp64, each value rounded once.
-// Fragment (chunk c, pass e, wave w, column j) = 1 KB: lane (l31, half) holds U'_{i j}[32 w + l31][8 c + 4 half + e], i = 0..3 (pass e of a chunk
-// multiplies the K pair (8 c + e, 8 c + 4 + e) at all 16 positions; a wave's four fragments of a pass are 4 KB contiguous: one scalar base,
-// immediate offsets).  U' = s_i s_j U with s_2 = -1: the input transform builds row 2 / column 2 of V with the opposite sign (d1 - d2 instead of
-// d2 - d1: its packed adds then need no operand swap), and the products U' V' = U V are unchanged.
-__global__ __launch_bounds__(256) void bt_wino_pack_kernel(const float* __restrict__ w2, float* __restrict__ ustream) {
+// Positions: V's position group pg = 3 h + jp holds (row i, column j) = (h ? 3 - a : a, 2 jp + b) in element a + 2 b: row half h of the input
+// transform (rows 0, 1 / rows 3, 2 of B2^T d), column pair jp.
+__host__ __device__ constexpr int wn_row(int pg, int q4) { return pg >= 3 ? 3 - (q4 & 1) : (q4 & 1); }
+__host__ __device__ constexpr int wn_col(int pg, int q4) { return 2 * (pg % 3) + (q4 >> 1); }
+
+// W2' [9][128 cout][128 cin] fp32 (bn3 folded) -> U stream.  One thread per (cout, cin): G2 g G4^T in fp64, each value rounded once.
+// Pass P = 6 c + 3 s + pp (chunk c, K step s, position pair pp), wave w, fragment (pgl, m) = 1 KB: lane (r = lane & 15, k = lane >> 4) holds
+// U_{pg}[32 w + 16 m + r][8 c + 4 s + k] for the four positions of group pg = 2 pp + pgl (the MFMA A operand of those positions: one float per
+// lane).  A wave's four fragments of a pass are 4 KB contiguous: one scalar base, immediate offsets.
+__global__ __launch_bounds__(256) void bt_wino_pack_kernel(const float* __restrict__ w2, float* __restrict__ ustream, float* __restrict__ ustream2) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= 128 * 128) return;
     const int co = idx >> 7, ci = idx & 127;
@@ -63,7 +83,7 @@ __global__ __launch_bounds__(256) void bt_wino_pack_kernel(const float* __restri
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) g[ky][kx] = (double)w2[((size_t)(ky * 3 + kx) * 128 + co) * 128 + ci];
-    double t[4][3];   // G g
+    double t[4][3];   // G2 g (rows: F(2, 3))
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
         t[0][kx] = g[0][kx];
@@ -71,16 +91,26 @@ __global__ __launch_bounds__(256) void bt_wino_pack_kernel(const float* __restri
         t[2][kx] = 0.5 * (g[0][kx] - g[1][kx] + g[2][kx]);
         t[3][kx] = g[2][kx];
     }
-    const int c = ci >> 3, half = (ci >> 2) & 1, e = ci & 3, w = co >> 5, l31 = co & 31;
+    const int c = ci >> 3, s = (ci >> 2) & 1, k = ci & 3, w = co >> 5, m = (co >> 4) & 1, r = co & 15;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const double u[4] = {t[i][0], 0.5 * (t[i][0] + t[i][1] + t[i][2]), 0.5 * (t[i][0] - t[i][1] + t[i][2]), t[i][2]};   // (G g) G^T
+    for (int pg = 0; pg < 6; ++pg)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            ustream[((size_t)(((c * 4 + e) * 4 + w) * 4 + j) * 64 + half * 32 + l31) * 4 + i] = (float)(((i == 2) != (j == 2)) ? -u[j] : u[j]);
-    }
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const double* const x = t[wn_row(pg, q4)];
+            double u;   // (G2 g) G4^T: columns F(4, 3)
+            switch (wn_col(pg, q4)) {
+                case 0: u = x[0]; break;
+                case 1: u = (x[0] + x[1] + x[2]) / 3.0; break;
+                case 2: u = (-x[0] + x[1] - x[2]) / 3.0; break;
+                case 3: u = -(16.0 * x[0] + 8.0 * x[1] + 4.0 * x[2]) / 15.0; break;
+                case 4: u = (x[0] - 2.0 * x[1] + 4.0 * x[2]) / 15.0; break;
+                default: u = x[2]; break;
+            }
+            const int P = 6 * c + 3 * s + (pg >> 1);
+            const size_t off = ((size_t)((P & 63) * 4 + w) * 4 + (pg & 1) * 2 + m) * 256 + (r + 16 * k) * 4 + q4;
+            (P < 64 ? ustream : ustream2)[off] = (float)u;
+        }
 }
-
 // W3 [256][128] fp32 -> 16 stage images (hg_bt_ring_f32.h's: output half nh, 16-float K slice k8; 128 rows x 64 bytes, br_swz) with the ROWS PERMUTED:
 // row 32 i + l of an image holds output channel 128 nh + 4 l + i.  Phase 3's accumulator tile i, column l31 is then channel 4 l31 + i: the lane's
 // four tiles are four CONSECUTIVE channels of one pixel, and residual, addends, output and pooled outputs move as 16-byte accesses (a quarter of the
@@ -130,7 +160,9 @@ __device__ __forceinline__ void wn_xload4s(f32x4 (&d)[4], const void* sbase, uns
                  : "v"(voff), "s"(sbase), "n"(STEP), "n"(2 * STEP), "n"(3 * STEP)
                  : "memory");
 }
-// The input transform of one (patch, channel): V' = B'^T d B' as SIXTEEN packed adds in one statement (one VALU clump per chunk).
+
+// The F(2x2, 3x3) input transform of one (patch, channel) -- layer1_wino_f32_kernel's (hg_l1_wino_f32.h; its U' = s_i s_j U with s_2 = -1):
+// V' = B'^T d B' as SIXTEEN packed adds in one statement (one VALU clump per chunk).
 // In: P[b] = (d[0][b], d[1][b]), Q[b] = (d[2][b], d[3][b]) -- the register pairs the two ds_read2st64_b32 of patch column b deliver.
 // Rows first: per column b,  T[b] = (d0 - d2, d1 + d2),  S[b] = (d1 - d2, d1 - d3)   [row 2 with the opposite sign: see bt_wino_pack_kernel];
 // then columns, on whole pairs: j = 0: X0 - X2, 1: X1 + X2, 2: X1 - X2 (opposite sign), 3: X1 - X3 for X = T (rows 0, 1) and X = S (rows 2, 3).
@@ -179,7 +211,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5, l31 = lane & 31;
     const int tiles_x = p.W / BT_TW, tiles_y = p.H / BT_TH;
     const int ntiles = p.V * tiles_y * tiles_x;
     // PERSISTENT: one workgroup per CU walks tiles vb = blockIdx.x, + gridDim.x, ... (a single resident workgroup has nobody to hide its
@@ -225,80 +256,109 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
         }
     };
 
-    // ---- U fragments straight from global memory (L2) into the MFMA A registers: the wave's four fragments (columns j = 0..3) of (chunk c, pass e)
-    //      are 4 KB at U + ((4 c + e) 4 + wave) 4096; lane (l31, half) of fragment j -> U'_{i j}[32 wave + l31][8 c + 4 half + e], i = 0..3.
-    //      Rolling prefetch three passes (3 072 MFMA cycles) ahead: at the start of pass e the registers of the pass before are free and take
-    //      (c + 1, e - 1) [pass 0: (c, 3)] -------------------------------------------------------------------------------------------------------
-    const unsigned char* const ubase = reinterpret_cast<const unsigned char*>(p.w2d) + (size_t)wave * 4096;
-    auto uload = [&](int c, int e, f32x4 (&dst)[4]) { wn_uload4(dst, ubase + (size_t)(c * 4 + e) * 16384, uoff); };
 
-    // ---- input transform: lane -> (patch 8 wave + (lane & 7), channel quad (lane >> 3) & 1, channel lane >> 4) of the chunk -----------
-    // t1 element (halo pixel hp, channel 64 kh + 4 kq + e) sits at hp * 256 + ((kq ^ swz(hp)) << 4) + 4 e of half kh (br_t1_swz): the 64 lanes
-    // of a read touch 64 different banks; chunk c's quads are kq = 2 (c & 7) + {0, 1}: an XOR of the address with (c & 7) << 5
-    const int ptx = lane & 7, pkq = (lane >> 3) & 1, pe = lane >> 4;
-    unsigned rd[4];
+    // ---- U fragments straight from global memory (L2) into the MFMA A registers: the wave's four fragments of pass P = 6 c + e (chunk c,
+    //      pass e of the chunk) are 4 KB at U + (4 P + wave) 4096 -- passes 64 .. 95 in the second part of the stream (p.wstream).  Rolling
+    //      prefetch WN_UBUF - 1 passes ahead: at the start of pass e the registers of the pass before are free and take pass e + WN_UBUF - 1
+    //      (of the next chunk past the chunk's last pass) ---------------------------------------------------------------------------------------
+    const unsigned char* const ubase = reinterpret_cast<const unsigned char*>(p.w2d) + (size_t)wave * 4096;
+    const unsigned char* const ubase2 = reinterpret_cast<const unsigned char*>(p.wstream) + (size_t)wave * 4096 - (size_t)64 * WN_PASS_BYTES;
+    auto uload = [&](int c, int e, f32x4 (&dst)[4]) {
+        const int P = WN_PASSES * c + e;
+        wn_uload4(dst, (P < 64 ? ubase : ubase2) + (size_t)P * WN_PASS_BYTES, uoff);
+    };
+
+    // ---- input transform: wave -> (row half h = wave & 1, patch rows 2 (wave >> 1) + {0, 1}); lane -> (patch column pc = lane & 3, channel
+    //      te = (lane >> 2) & 3 of channel quad kq = (lane >> 4) & 1, patch row 2 (wave >> 1) + (lane >> 5)): 16 patches x 8 channels x 2 row halves.
+    // t1 element (halo pixel hp, channel 64 kh + 4 kq + e) sits at hp * 256 + ((kq ^ swz(hp)) << 4) + 4 e of half kh (br_t1_swz): a read of the 64
+    // lanes touches 8 slots x 4 banks twice (the two patch rows: a two-way conflict); chunk c's quads are kq = 2 (c & 7) + {0, 1}: an XOR of
+    // the address with (c & 7) << 5.  The lane reads halo rows 2 pr + h + t (t = 0, 1, 2: immediate offsets) of halo columns 4 pc + col.
+    const int wh = wave & 1;
+    // V chunk image [K step s 2][position group pg 6][channel k 4][patch slot 16] x 16 bytes: patch n of channel k in slot n ^ 4 k (a permuted
+    // 256-byte row: the 16 lanes of a store quarter -- four patches x four channels -- hit 16 different slots).  The writer (s, k) = (kq, te)
+    // stores groups pg = 3 h + jp; the reader, lane (patch r = lane & 15, channel k = lane >> 4), reads the B operand of four positions.
+    // These lane constants (rd: the patch columns' read addresses, vwr, vrd) are derived per tile, at the start of phase 2, from a copy of the
+    // lane index the compiler cannot see through: kept alive across the tile loop they would also live across phase 3, where layer2's
+    // 64 prefetched x operands leave no room for them (one VGPR went to scratch, its reloads a vmcnt(0) behind the x prefetch)
+    unsigned rd[6], vwr, vrd;
+    auto lane_consts = [&]() {
+        int l = (int)(uoff >> 4);
+        asm volatile("" : "+v"(l));
+        const int ppc = l & 3, pte = (l >> 2) & 3, pkq = (l >> 4) & 1, ppr = 2 * (wave >> 1) + (l >> 5);
 #pragma unroll
-    for (int bb = 0; bb < 4; ++bb) {
-        const int hx = 2 * ptx + bb, hp = (2 * wave) * BT_HW + hx;
-        rd[bb] = (unsigned)(hp * 256 + ((pkq ^ (hx & 15)) << 4) + 4 * pe);
-    }
-    // V chunk image [channel e 4][column j 4][quad kq 2][patch 32][row i 4] floats: the 16 bytes a lane writes per column j (two 8-byte halves)
-    // are V'_{0..3, j} of its (patch, channel), the 16 bytes a lane reads per (e, j) are the B values of MFMAs (4 i + j, e) for its patch; patch n of
-    // quad kq sits in slot n ^ 8 kq (a permuted 512-byte row either way)
-    const unsigned vwr = (unsigned)(pe * 4096 + pkq * 512 + (((8 * wave + ptx) ^ (pkq << 3)) << 4));
-    const unsigned vrd = (unsigned)(half * 512 + ((l31 ^ (half << 3)) << 4));
+        for (int col = 0; col < 6; ++col) {
+            const int hx = 4 * ppc + col, hp = (2 * ppr + wh) * BT_HW + hx;
+            rd[col] = (unsigned)(hp * 256 + ((pkq ^ (hx & 15)) << 4) + 4 * pte);
+        }
+        vwr = (unsigned)(((pkq * 6 + 3 * wh) * 4 + pte) * 256 + (((4 * ppr + ppc) ^ (4 * pte)) << 4));
+        vrd = (unsigned)((l >> 4) * 256 + (((l & 15) ^ (4 * (l >> 4))) << 4));
+    };
     // three V buffers (chunk c is read from buffer c % 3 while chunk c + 2 is built into (c + 2) % 3: a chunk's first fragments can then be
     // requested before the barrier that ends the chunk in front of it): 0, 1 where the W3 ring's slots 0 .. 3 will be, 2 where its slots 4 .. 7 will be
-    auto vbuf_off = [](int b) { return b < 2 ? b * WN_V_BYTES : WN_RING2_OFF; };
-    f32x2 tP[4], tQ[4];
-    unsigned ta[4];   // LDS addresses of the next patch reads (computed in the VALU clump of the chunk before: no lone VALU instruction in phase 2)
+    auto vbuf_off = [](int b) { return b == 0 ? 0 : b == 1 ? BR_RING_BYTES / 2 : WN_RING2_OFF; };
+    // the F(2, 3) step of the two rows a lane builds, per column: (t0 - t2, t1 + t2) for h = 0 (rows 0, 1 of B2^T d), (t0 - t2, t1 - t0) for
+    // h = 1 (rows 3, 2) -- one form, two packed FMAs with wave-uniform coefficients.  The zero coefficients add 0 * t exactly for every finite
+    // t; only a non-finite t1 value would become NaN here instead of staying infinite, and no Winograd form carries an infinity through anyway:
+    // every output of A^T M A sums positions in which one infinite input has opposite signs (inf - inf = NaN), and t1 = relu(W1' a + b1) of
+    // finite activations is finite
+    const f32x2 cw2 = {-1.0f, wh ? 0.0f : 1.0f}, cw0 = {0.0f, wh ? -1.0f : 0.0f};
+    float tR[6][3];   // the patch values of the lane's (patch, channel, row half): [column][row]
+    unsigned ta[6];   // LDS addresses of the next patch reads (computed in the VALU clump of the chunk before)
     auto t_addr = [&](int c) {   // chunk c's patch columns
 #pragma unroll
-        for (int bb = 0; bb < 4; ++bb) ta[bb] = (rd[bb] ^ (unsigned)((c & 7) << 5)) + (t1_addr + (unsigned)((c >> 3) * BR_T1_BYTES));   // (a complete LDS address: one v_xad_u32)
+        for (int col = 0; col < 6; ++col) ta[col] = (rd[col] ^ (unsigned)((c & 7) << 5)) + (t1_addr + (unsigned)((c >> 3) * BR_T1_BYTES));
     };
-    auto t_read = [&](int bb) {   // column bb of the 4 x 4 patch: rows (0, 1) and (2, 3) as register pairs
+    auto t_read = [&](int col) {   // column col of the lane's three rows
         typedef const __attribute__((address_space(3))) float* lds_f;
         if (WN_ABL & 512) {   // (timing only: no patch reads)
-            asm volatile("" : "+v"(tP[bb]), "+v"(tQ[bb]));
+            asm volatile("" : "+v"(tR[col][0]), "+v"(tR[col][1]), "+v"(tR[col][2]));
             return;
         }
-        tP[bb] = f32x2{*(lds_f)(size_t)ta[bb], *(lds_f)(size_t)(ta[bb] + BT_HW * 256)};
-        tQ[bb] = f32x2{*(lds_f)(size_t)(ta[bb] + 2 * BT_HW * 256), *(lds_f)(size_t)(ta[bb] + 3 * BT_HW * 256)};
+#pragma unroll
+        for (int t = 0; t < 3; ++t) tR[col][t] = *(lds_f)(size_t)(ta[col] + t * BT_HW * 256);
     };
-    f32x2 vt[4], vs[4];   // V' of the lane's (patch, channel): columns j = 0 .. 3, rows (0, 1) and (2, 3)
-    // sixteen packed adds + the next reads' four addresses in one clump
+    f32x4 vo[3];   // V of the lane's (patch, channel, row half): column pair jp -> (row a, column 2 jp + b) in element a + 2 b
     auto t_transform = [&](int c_next_addr) {
-        wn_transform(tP, tQ, vt, vs);
-        t_addr(c_next_addr);
-    };
-    // ... and column j's 16 bytes into V buffer `buf`: in phase 2 one store per MFMA group (between MFMAs an LDS instruction is all but free; the four
-    // stores right behind the clump cost 1.8 % of the kernel)
-    auto v_store = [&](int buf, int j) {
-        unsigned char* const dst = smem + vbuf_off(buf) + vwr;
-        *reinterpret_cast<f32x2*>(dst + j * 1024) = vt[j];
-        *reinterpret_cast<f32x2*>(dst + j * 1024 + 8) = vs[j];
-    };
-    auto t_transform_write = [&](int buf, int c_next_addr) {   // (tile entry: clump, then the stores)
-        if (WN_ABL & 2048) {   // (timing only: no packed adds)
+        f32x2 x[6];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                vt[j] = tP[j];
-                vs[j] = tQ[j];
-            }
-        } else {
-            wn_transform(tP, tQ, vt, vs);
-        }
-        t_addr(c_next_addr);
-        unsigned char* const dst = smem + vbuf_off(buf) + vwr;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (WN_ABL & 1024) {   // (timing only: no V stores)
-                asm volatile("" ::"v"(vt[j]), "v"(vs[j]));
+        for (int col = 0; col < 6; ++col) {
+            const f32x2 P = {tR[col][0], tR[col][1]};
+            if (WN_ABL & 2048) {   // (timing only: no packed ops)
+                x[col] = P;
                 continue;
             }
-            *reinterpret_cast<f32x2*>(dst + j * 1024) = vt[j];
-            *reinterpret_cast<f32x2*>(dst + j * 1024 + 8) = vs[j];
+            x[col] = cw0 * f32x2{tR[col][0], tR[col][0]} + (cw2 * f32x2{tR[col][2], tR[col][2]} + P);
         }
+        f32x2 v[6];
+        if (WN_ABL & 2048) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) v[j] = x[j];
+        } else {   // B4^T along the columns (tests/test_wino24_numerics.py: _bt4_f32)
+            const f32x2 h = {0.5f, 0.5f}, two = {2.0f, 2.0f};
+            const f32x2 d13 = x[3] - x[1], d24 = x[4] - x[2];
+            v[0] = h * d13 + (((x[0] + x[4]) - two * x[2]) + d13);
+            v[1] = h * x[3] + (two * x[3] + (h * x[2] + (x[4] - x[1])));
+            v[2] = h * x[3] + (((x[4] + x[1]) - two * x[2]) - h * x[2]);
+            v[3] = two * (x[3] - x[1]) + d24;
+            v[4] = h * (x[1] - x[3]) + d24;
+            v[5] = h * d24 + (((x[5] + x[1]) - two * x[3]) + d24);
+        }
+#pragma unroll
+        for (int jp = 0; jp < 3; ++jp) vo[jp] = f32x4{v[2 * jp][0], v[2 * jp][1], v[2 * jp + 1][0], v[2 * jp + 1][1]};
+        t_addr(c_next_addr);
+    };
+    // ... and column pair jp's 16 bytes into V buffer `buf`: in phase 2 one store per MFMA group (between MFMAs an LDS instruction is all but free)
+    auto v_store = [&](int buf, int jp) {
+        if (WN_ABL & 1024) {   // (timing only: no V stores)
+            asm volatile("" ::"v"(vo[jp]));
+            return;
+        }
+        *reinterpret_cast<f32x4*>(smem + vbuf_off(buf) + vwr + jp * 1024) = vo[jp];
+    };
+    auto t_transform_write = [&](int buf, int c_next_addr) {   // (tile entry: clump, then the stores)
+        t_transform(c_next_addr);
+#pragma unroll
+        for (int jp = 0; jp < 3; ++jp) v_store(buf, jp);
     };
     // W3's 16 stages in two sets of eight (one per 128-channel output half): stage k -> slot k % 8, slots 0 .. 3 where the V buffers were, 4 .. 7
     // in a region of their own.  A whole half is resident before its K loop starts: no wait, no barrier inside the loop (operations retire in
@@ -336,77 +396,82 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
         const size_t htile = (((size_t)view * (p.H / 2) + ty0 / 2 + wave) * (p.W / 2) + tx0 / 2) * (CO * 4);
         const unsigned char* const xtile = reinterpret_cast<const unsigned char*>(p.in) + (L2 ? ftile / 2 : ftile);   // (L2: x has 128 channels)
 
-        // accumulators (b2 is added to position (1,1) -- which enters all four outputs of a patch with weight +1 -- in the output transform: as a
-        // start value it would be a global load straight into accumulator registers, and the wait hipcc puts in front of the first MFMA that
-        // touches them sits inside the chunk loop: a vmcnt(0) per chunk, 580 cycles each)
-        f32x16 acc[16];   // (their first MFMAs take a zero addend: chunk 0, pass 0)
-        f32x4 ufr[4][4];
-        uload(0, 0, ufr[0]);
-        uload(0, 1, ufr[1]);
-        uload(0, 2, ufr[2]);
+        // accumulators [position group pg 6][row block m 2][position q4 4] (b2 is added to position (1,1) in the output transform: as a start
+        // value it would be a global load straight into accumulator registers, and the wait hipcc puts in front of the first MFMA that touches
+        // them sits inside the chunk loop)
+        f32x4 acc[48];   // (their first MFMAs take a zero addend: chunk 0, K step 0)
+        f32x4 ufr[WN_UBUF][4];
+#pragma unroll
+        for (int e = 0; e < WN_UBUF - 1; ++e) uload(0, e, ufr[e]);
         // first tile: both t1 halves of this wave have landed once only the loads issued behind them are outstanding.  Later tiles: the halo was
         // requested during the tile before's phase 3, whose counted waits and barriers have long published it.  The barrier: every wave is past
         // its last reads of the ring (the tile before), V buffer 0 may be written
-        if (first) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+        if (first) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (WN_UBUF - 1)) : "memory");
         first = false;
         br_barrier();
         BR_STAMP(0);
-        asm volatile("" : "+v"(rd[0]), "+v"(rd[1]), "+v"(rd[2]), "+v"(rd[3]));   // (or the first chunks' read addresses are hoisted out of the tile loop: 12 registers kept alive in scratch)
+        lane_consts();
         t_addr(0);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) t_read(g);
+        for (int col = 0; col < 6; ++col) t_read(col);
         t_transform_write(0, 1);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) t_read(g);
+        for (int col = 0; col < 6; ++col) t_read(col);
         t_transform_write(1, 2);
         br_barrier();
         BR_STAMP(1);
 
-        // ---- phase 2: 16 chunks x 4 passes (K pair e) x 4 columns x 4 rows.  Chunk c: MFMAs on V(c) (buffer c % 3) while V(c + 2) is built.
-        //      Nothing vector-side hides behind an fp32 MFMA here, so a chunk issues, beside its 64 MFMAs: 16 U loads (scalar base), 16 + 8 LDS
-        //      reads, 4 LDS stores, ONE clump of 20 VALU instructions, one barrier -------------------------------------------------------------
-        f32x4 vf[2][4];
+        // ---- phase 2: 16 chunks x 6 passes (K step s = e / 3, position pair pp = e % 3) x 4 MFMA groups (position group 2 pp + (g >> 1), row block
+        //      g & 1) x 4 positions.  Chunk c: MFMAs on V(c) (buffer c % 3) while V(c + 2) is built.  Nothing vector-side hides behind an fp32
+        //      MFMA here, so a chunk issues, beside its 96 MFMAs: 24 U loads (scalar base), 12 + 18 LDS reads, 3 LDS stores, ONE clump of packed
+        //      ops, one barrier ------------------------------------------------------------------------------------------------------------------
+        f32x4 vf[2][2];
         // c: the chunk (runtime); BR = c % 3 and FIRST = (c == 0) as compile-time tags
         auto chunk = [&](int c, auto br_tag, auto first_tag) {
             constexpr int BR = decltype(br_tag)::value;
             constexpr bool FIRST = decltype(first_tag)::value;
             const int cn = c + 1 < WN_CHUNKS ? c + 1 : c;   // (the last chunks re-request fragments / rebuild buffers nobody reads any more: one code path)
-            const int c2 = c + 2 < WN_CHUNKS ? c + 2 : WN_CHUNKS - 1, c3 = c + 3 < WN_CHUNKS ? c + 3 : WN_CHUNKS - 1;
-            (void)c2;
+            const int c3 = c + 3 < WN_CHUNKS ? c + 3 : WN_CHUNKS - 1;
             const unsigned char* const vb_ = smem + vbuf_off(BR) + vrd;
             const unsigned char* const vn_ = smem + vbuf_off((BR + 1) % 3) + vrd;
             if (FIRST) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) vf[0][g] = *reinterpret_cast<const f32x4*>(vb_ + g * 1024);
+                for (int g = 0; g < 2; ++g) vf[0][g] = *reinterpret_cast<const f32x4*>(vb_ + g * 1024);
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
+            for (int e = 0; e < WN_PASSES; ++e) {
+                const int pp = e % 3;
                 __builtin_amdgcn_sched_barrier(0);
                 if (!(WN_ABL & 1)) {
-                    wn_uwait<8>(ufr[e]);   // this pass's fragments (requested three passes ago) have landed: behind them only two passes' 8 loads
-                    if (e == 0) uload(c, 3, ufr[3]);
-                    else uload(cn, e - 1, ufr[e - 1]);
+                    wn_uwait<4 * (WN_UBUF - 2)>(ufr[e % WN_UBUF]);   // this pass's fragments have landed: behind them only the passes' between
+                    const int eu = e + WN_UBUF - 1;   // ... and the registers of the pass before take the fragments of pass e + WN_UBUF - 1
+                    if (eu < WN_PASSES) uload(c, eu, ufr[eu % WN_UBUF]);
+                    else uload(cn, eu - WN_PASSES, ufr[eu % WN_UBUF]);
                     __builtin_amdgcn_sched_barrier(0);   // (... issued HERE: the scheduler would sink the statement behind the pass's MFMAs)
                 }
-                if (e == 2 && !(WN_ABL & 2)) {
-                    if (WN_ABL & 4096) t_transform_write((BR + 2) % 3, c3);   // (development: the stores right behind the clump, as before)
-                    else t_transform(c3);   // V(c + 2) from the patch read in pass 0; addresses for the reads of chunk c + 1's pass 0
+                if (e == 3 && !(WN_ABL & 2)) {
+                    if (WN_ABL & 4096) t_transform_write((BR + 2) % 3, c3);   // (development: the stores right behind the clump)
+                    else t_transform(c3);   // V(c + 2) from the patch read in passes 0, 1; addresses for the reads of chunk c + 1's passes 0, 1
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    // LDS instructions are all but free between MFMAs: one V fragment read for the next pass (pass 3: the NEXT chunk's pass 0,
-                    // whose buffer was complete a barrier ago) and, in pass 0, a column of the patch V(c + 2) is built from
-                    if (e < 3) vf[(e + 1) & 1][g] = *reinterpret_cast<const f32x4*>(vb_ + (e + 1) * 4096 + g * 1024);
-                    else vf[0][g] = *reinterpret_cast<const f32x4*>(vn_ + g * 1024);
-                    if (e == 0 && !(WN_ABL & 2)) t_read(g);
-                    if (e == 2 && !(WN_ABL & (2 | 4096 | 1024))) v_store((BR + 2) % 3, g);
+                    // LDS instructions are all but free between MFMAs: the V fragment reads of the next pass (pass 5: the NEXT chunk's pass 0,
+                    // whose buffer was complete a barrier ago), in passes 0, 1 a column of the patch V(c + 2) is built from, in pass 3 a V store
+                    if (g < 2) {
+                        const int en = e + 1, sn = en / 3, ppn = en % 3;
+                        if (e < WN_PASSES - 1) vf[en & 1][g] = *reinterpret_cast<const f32x4*>(vb_ + (sn * 6 + 2 * ppn + g) * 1024);
+                        else vf[0][g] = *reinterpret_cast<const f32x4*>(vn_ + g * 1024);
+                    }
+                    if (e < 2 && g < 3 && !(WN_ABL & 2)) t_read(3 * e + g);
+                    if (e == 3 && g < 3 && !(WN_ABL & (2 | 4096))) v_store((BR + 2) % 3, g);
+                    const int pgl = g >> 1, m = g & 1, ai = ((2 * pp + pgl) * 2 + m) * 4;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if (FIRST && e == 0)   // a tile's first product into each accumulator starts from zero: no 256 v_accvgpr_write per tile
-                            acc[4 * i + g] = __builtin_amdgcn_mfma_f32_32x32x2f32(ufr[e][g][i], vf[e & 1][g][i], f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, 0, 0, 0);
+                    for (int q4 = 0; q4 < 4; ++q4) {
+                        if (FIRST && e < 3)   // a tile's first product into each accumulator starts from zero
+                            acc[ai + q4] = __builtin_amdgcn_mfma_f32_16x16x4f32(ufr[e % WN_UBUF][2 * pgl + m][q4], vf[e & 1][pgl][q4], f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
                         else
-                            acc[4 * i + g] = __builtin_amdgcn_mfma_f32_32x32x2f32(ufr[e][g][i], vf[e & 1][g][i], acc[4 * i + g], 0, 0, 0);
+                            acc[ai + q4] = __builtin_amdgcn_mfma_f32_16x16x4f32(ufr[e % WN_UBUF][2 * pgl + m][q4], vf[e & 1][pgl][q4], acc[ai + q4], 0, 0, 0);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -423,9 +488,8 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
         // the last chunk re-requested fragments nobody multiplies: keep their registers named until they have landed (a load whose destination is
         // dead to the compiler lands, asynchronously, in whatever the register holds by then)
         if (!(WN_ABL & 1)) {
-            wn_uwait<4>(ufr[0]);
-            wn_uwait<0>(ufr[1]);
-            wn_uwait<0>(ufr[2]);
+#pragma unroll
+            for (int e = 0; e < WN_UBUF - 1; ++e) wn_uwait<0>(ufr[e]);
         }
 
         BR_STAMP(2);
@@ -445,42 +509,51 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
         // W3's first half into the ring (both V buffers are dead; slots 4 .. 7 were last read a tile ago): it lands under the output transform
         ring_issue8(0);
 
-        // ---- output transform Y = A^T M A, ReLU, t2 -> LDS (pixel-major, 16-byte chunk ch of pixel (y, x) in slot ch ^ (x & 15) ^ ((y >> 1) & 1)
-        //      of its 512-byte row: conflict-free for these writes (16 lanes = 8 patch columns x 2 patch rows) and for phase 3's reads).
-        //      Address = [pixel (2 ty, 2 tx) | lane part of the slot] ^ [(2 q ^ bb) << 4] + (16 a + bb) * 512: one lane base, XOR constants ----
+        // ---- output transform Y = A2^T M A4, ReLU, t2 -> LDS (pixel-major, 16-byte chunk ch of pixel (y, x) in slot ch ^ (x & 15) ^ ((y >> 1) & 1)
+        //      of its 512-byte row, as phase 3 reads it).  Lane: patch (pr, pc) = (r >> 2, r & 3) of r = lane & 15, channels 32 wave + 16 m + 4 q + 0..3
+        //      (q = lane >> 4): per (m, output pixel) one 16-byte store ----
         if (WN_ABL & 16) {   // (timing only: one value that depends on every accumulator tile, so that phase 2 stays)
             float keep = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 16; ++k) keep += acc[k][0];
+            for (int k = 0; k < 48; ++k) keep += acc[k][0];
             *reinterpret_cast<float*>(t1_lds + lane3 * 4) = keep;
         } else {
-            const int ty = l31_3 >> 3, tx = l31_3 & 7;
-            const unsigned wbase = (unsigned)((32 * ty + 2 * tx) * 512 + ((((8 * wave + half3) ^ (2 * tx) ^ (ty & 1)) & 31) << 4));
+            const int q3 = lane3 >> 4, opr = (lane3 & 15) >> 2, opc = lane3 & 3;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 y[2][2];
-                const f32x4 bb = *reinterpret_cast<const f32x4*>(b2_lds + 32 * wave + 8 * q + 4 * half3);
+            for (int m = 0; m < 2; ++m) {
+                f32x4 y[2][4];
+                const f32x4 bb = *reinterpret_cast<const f32x4*>(b2_lds + 32 * wave + 16 * m + 4 * q3);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * q + e;
-                    float s[2][4];   // A^T M: rows
+                for (int reg = 0; reg < 4; ++reg) {
+                    float M[4][6];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float m1 = j == 1 ? acc[4 + j][r] + bb[e] : acc[4 + j][r];
-                        s[0][j] = acc[j][r] + m1 + acc[8 + j][r];
-                        s[1][j] = m1 - acc[8 + j][r] - acc[12 + j][r];
+                    for (int pg = 0; pg < 6; ++pg)
+#pragma unroll
+                        for (int q4 = 0; q4 < 4; ++q4) M[wn_row(pg, q4)][wn_col(pg, q4)] = acc[(pg * 2 + m) * 4 + q4][reg];
+                    M[1][1] += bb[reg];
+                    float s[2][6];   // A2^T M: rows
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) {
+                        s[0][j] = M[0][j] + M[1][j] + M[2][j];
+                        s[1][j] = M[1][j] - M[2][j] - M[3][j];
                     }
 #pragma unroll
-                    for (int a = 0; a < 2; ++a) {
-                        y[a][0][e] = br_relu(s[a][0] + s[a][1] + s[a][2]);
-                        y[a][1][e] = br_relu(s[a][1] - s[a][2] - s[a][3]);
+                    for (int a = 0; a < 2; ++a) {   // ... A4 (tests/test_wino24_numerics.py: _at4_f32)
+                        const float sa = s[a][1] + s[a][2], sb = s[a][1] - s[a][2];
+                        y[a][0][reg] = br_relu(s[a][0] + sa + s[a][3] + s[a][4]);
+                        y[a][1][reg] = br_relu(sb + 0.5f * s[a][3] - 2.0f * s[a][4]);
+                        y[a][2][reg] = br_relu(sa + 0.25f * s[a][3] + 4.0f * s[a][4]);
+                        y[a][3][reg] = br_relu(sb + 0.125f * s[a][3] - 8.0f * s[a][4] + s[a][5]);
                     }
                 }
+                const int ch = 8 * wave + 4 * m + q3;
 #pragma unroll
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
-                    for (int bb = 0; bb < 2; ++bb)
-                        *reinterpret_cast<f32x4*>(t1_lds + (wbase ^ (unsigned)(((2 * q) ^ bb) << 4)) + (16 * a + bb) * 512) = y[a][bb];
+                    for (int b = 0; b < 4; ++b) {
+                        const int yy = 2 * opr + a, xx = 4 * opc + b;
+                        *reinterpret_cast<f32x4*>(t1_lds + (yy * BT_TW + xx) * 512 + (((ch ^ (xx & 15) ^ (opr & 1)) & 31) << 4)) = y[a][b];
+                    }
             }
         }
         BR_STAMP(3);

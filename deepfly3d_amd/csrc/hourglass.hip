@@ -22,6 +22,7 @@
 #include "hg_l1_f32.h"
 #include "hg_bt_wino_f32.h"
 #include "hg_l1_wino_f32.h"
+static_assert(hgk::WN_U2_BYTES <= hgk::L2F_NSTAGE * hgk::BR_STAGE_BYTES, "layer2: U's second part fits the direct-form stage images");
 #include "hg_c1_res_f32.h"
 
 using namespace hgk;
@@ -124,8 +125,8 @@ struct df3d_hg {
                           // path, streaming output stores); 0 = round 3's kernels (the A/B); bit-identical either way
     int split1 = 1;       // fp32: 1 (default) = plain 256 -> 128 -> 128 -> 256 blocks run as conv1 (every pixel once) + tail (hg_c1_f32.h), bit-identical
                           // (development: 8 + mask splits only the identity blocks (1), layer1 (2), layer2 (4))
-    int wino = 1;         // exact-fp32 engine, split identity blocks: 1 (default) = the tail's 3x3 as Winograd F(2x2, 3x3) (hg_bt_wino_f32.h: 0.545 of the
-                          // direct tail's MFMAs; fp32 tolerance against the oracle, NOT bit-identical to the direct kernels), 0 = direct implicit GEMM
+    int wino = 1;         // exact-fp32 engine, split identity blocks: 1 (default) = the tail's 3x3 as Winograd F(2x4, 3x3) (hg_bt_wino_f32.h: 0.455 of the
+                          // direct tail's MFMA cycles; fp32 tolerance against the oracle, NOT bit-identical to the direct kernels), 0 = direct implicit GEMM
     int c1res = 1;        // exact-fp32 engine with `wino`: 1 (default) = conv1 of the plain identity blocks with W1 resident in LDS (hg_c1_res_f32.h), bit-identical
                           // to conv1_ring_f32_kernel (0); may be switched between forwards (it changes neither the plan nor the weight streams)
     bool split_id() const { return split1 == 1 || (split1 >= 8 && (split1 & 1)); }
@@ -962,7 +963,7 @@ int run_steps(df3d_hg* h, const float* images_all, int n_all, int upto, float* h
                         if (std::is_same<T, float>::value && st.wstream_w2d >= 0) {   // option `wino`: layer2's 3x3 in the Winograd domain as well
                             r.w2d = sb + st.wstream_w2d;
                             ScopedTimer tw(h, s, "bottleneck_wino_f32_kernel<false, false, true>", 2.0 * px * (9.0 * pl * pl + (double)pl * 2 * pl + (double)cin * 2 * pl),
-                                           px * 4.0 * (cin + pl + 2.0 * pl), st.m1_elems * n * eb, 2.0 * px * (4.0 * pl * pl + (double)pl * 2 * pl + (double)cin * 2 * pl));
+                                           px * 4.0 * (cin + pl + 2.0 * pl), st.m1_elems * n * eb, 2.0 * px * (3.0 * pl * pl + (double)pl * 2 * pl + (double)cin * 2 * pl));
                             if (int rc = launch_wino_f32<false, false, true>(r, n * (ti.h / BT_TH) * (ti.w / BT_TW), s)) return rc;
                             break;
                         }
@@ -1083,9 +1084,9 @@ int run_steps(df3d_hg* h, const float* images_all, int n_all, int upto, float* h
                     }
                     if (split && std::is_same<T, float>::value && r.w2d) {   // option `wino`: the tail with its 3x3 in the Winograd domain
                         const int blocks = n * (ti.h / BT_TH) * (ti.w / BT_TW);
-                        // FLOPs: the direct form's (what the block computes, in the reference's terms); the kernel EXECUTES 16/36 of the 3x3's
+                        // FLOPs: the direct form's (what the block computes, in the reference's terms); the kernel EXECUTES 24/72 of the 3x3's
                         ScopedTimer tm(h, s, std::string("bottleneck_wino_f32_kernel<") + (a.in2 ? "true, false, false>" : a.add2 ? "false, true, false>" : "false, false, false>"),
-                                       2.0 * px * (9.0 * pl * pl + 2.0 * pl * pl), px * eb * (cin + 2.0 * pl + pl), st.m1_elems * n * eb, 2.0 * px * (4.0 * pl * pl + 2.0 * pl * pl));
+                                       2.0 * px * (9.0 * pl * pl + 2.0 * pl * pl), px * eb * (cin + 2.0 * pl + pl), st.m1_elems * n * eb, 2.0 * px * (3.0 * pl * pl + 2.0 * pl * pl));
                         const int rc = a.in2 ? launch_wino_f32<true, false>(r, blocks, s) : a.add2 ? launch_wino_f32<false, true>(r, blocks, s) : launch_wino_f32<false, false>(r, blocks, s);
                         if (rc) return rc;
                         break;
@@ -1486,14 +1487,22 @@ int df3d_hg_set_weights(df3d_hg* h, const float* blob_dev, void* lowp_dev, void*
                 hipLaunchKernelGGL(bt_fc_pack_f32_kernel, dim3((HD_FC_STAGES_F32 * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
                                    blob_dev + st.conv.w_off, reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
             if (st.kind != ST_BOTTLENECK || st.wstream < 0) continue;
+            // Option `wino` (st.wstream_w2d >= 0, float32 engine): the direct-form stage images at st.wstream are dead -- every launch of such a
+            // block takes bottleneck_wino_f32_kernel (run_steps: a split step with r.w2d set; ST_BOTTLENECK steps exist only at levels of whole
+            // 8 x 16 tiles, fused and unfused plans, every fuse_upadd mode), conv1 reads st.wstream_c1 (c1res = 0, the UP form) or the W1 images
+            // behind U (c1res = 1), and no other kernel reads st.wstream.  So the images are not packed, and U's second part (passes 64 .. 95 of
+            // bt_wino_pack_kernel, 512 KiB) takes their place: the buffer keeps its size.
+            const bool wino_f32 = st.wstream_w2d >= 0 && h->dtype == DF3D_DTYPE_F32;
             if (st.l2f) {
-                hipLaunchKernelGGL(bt_l2f_pack_kernel, dim3((L2F_NSTAGE * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off,
-                                   blob_dev + st.conv3b.w_off, blob_dev + st.conv4b.w_off, reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
+                if (!wino_f32)
+                    hipLaunchKernelGGL(bt_l2f_pack_kernel, dim3((L2F_NSTAGE * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off,
+                                       blob_dev + st.conv3b.w_off, blob_dev + st.conv4b.w_off, reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
                 hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3(((128 / 16) * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv.w_off,
                                    reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_c1, 128, 128);
-                if (st.wstream_w2d >= 0 && h->dtype == DF3D_DTYPE_F32) {
+                if (wino_f32) {
                     unsigned char* const ws = reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_w2d;
-                    hipLaunchKernelGGL(bt_wino_pack_kernel, dim3(128 * 128 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off, reinterpret_cast<float*>(ws));
+                    hipLaunchKernelGGL(bt_wino_pack_kernel, dim3(128 * 128 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off, reinterpret_cast<float*>(ws),
+                                       reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream));
                     hipLaunchKernelGGL(bt_wino_pack_w3_kernel, dim3(BRF_W3_STAGES * 512 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv3b.w_off, ws + WN_U_BYTES);
                     hipLaunchKernelGGL(bt_wino_pack_w3_kernel, dim3(BRF_W3_STAGES * 512 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv4b.w_off, ws + WN_U_BYTES + WN_W3_BYTES);
                 }
@@ -1512,16 +1521,18 @@ int df3d_hg_set_weights(df3d_hg* h, const float* blob_dev, void* lowp_dev, void*
                 }
                 continue;
             }
-            hipLaunchKernelGGL(bt_ring_pack_f32_kernel, dim3((BRF_NSTAGE * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
-                               blob_dev + st.conv.w_off, blob_dev + st.conv2b.w_off, blob_dev + st.conv3b.w_off,
-                               reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
+            if (!wino_f32)
+                hipLaunchKernelGGL(bt_ring_pack_f32_kernel, dim3((BRF_NSTAGE * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
+                                   blob_dev + st.conv.w_off, blob_dev + st.conv2b.w_off, blob_dev + st.conv3b.w_off,
+                                   reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
             if (st.wstream_c1 >= 0)
                 hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3((C1_NSTAGE * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
                                    blob_dev + st.conv.w_off, reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_c1);
-            if (st.wstream_w2d >= 0 && h->dtype == DF3D_DTYPE_F32)
+            if (wino_f32)
             {
                 unsigned char* const ws = reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_w2d;
-                hipLaunchKernelGGL(bt_wino_pack_kernel, dim3(128 * 128 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off, reinterpret_cast<float*>(ws));
+                hipLaunchKernelGGL(bt_wino_pack_kernel, dim3(128 * 128 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off, reinterpret_cast<float*>(ws),
+                                   reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream));
                 hipLaunchKernelGGL(bt_wino_pack_w3_kernel, dim3(BRF_W3_STAGES * 512 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv3b.w_off, ws + WN_U_BYTES);
                 hipLaunchKernelGGL(c1r_pack_kernel, dim3(C1_NSTAGE * 512 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv.w_off, ws + WN_STREAM_BYTES);
             }
