@@ -22,14 +22,33 @@
 #include "hg_l1_f32.h"
 #include "hg_bt_wino_f32.h"
 #include "hg_l1_wino_f32.h"
-static_assert(hgk::WN_U2_BYTES <= hgk::L2F_NSTAGE * hgk::BR_STAGE_BYTES, "layer2: U's second part fits the direct-form stage images");
 #include "hg_c1_res_f32.h"
+static_assert(hgk::WN_U2_BYTES <= hgk::BRF_NSTAGE * hgk::BR_STAGE_BYTES, "U's second part fits the identity block's stage-image slot");
+static_assert(hgk::WN_U2_BYTES <= hgk::L2F_NSTAGE * hgk::BR_STAGE_BYTES, "layer2: U's second part fits the stage-image slot");
 
 using namespace hgk;
 
 namespace {
 
 enum StepKind { ST_STEM, ST_CONV, ST_POOL, ST_UPADD, ST_BOTTLENECK, ST_HEAD };
+
+// The kernels an ST_BOTTLENECK step runs as, fixed when the plan is built.  The weight streams (Step::wstream*) each form reads, and
+// so the ones set_weights packs for it, are listed with it.
+enum BtForm {
+    BT_REG,         // bottleneck_kernel (hg_kernels.h): weights straight from the blob; no streams
+    BT_L1_LP,       // 16-bit layer1, bottleneck_l1_kernel (hg_bt_l1.h): wstream = its LDS weight image
+    BT_RING_LP,     // 16-bit identity block or layer2, bottleneck_ring_kernel (hg_bt_ring.h): wstream, wstream_w2 (option w2d)
+    BT_RING_F32,    // fp32 / f32s identity block, unsplit: bottleneck_ring_f32_kernel (hg_bt_ring_f32.h): wstream
+    BT_SPLIT_F32,   // fp32 / f32s identity block: conv1_ring_f32_kernel (hg_c1_f32.h) + the ring tail: wstream_c1, wstream, zero page
+    BT_SPLIT_WINO,  // fp32 identity block: conv1_ring_f32_kernel or conv1_res_f32_kernel (option c1res) + bottleneck_wino_f32_kernel:
+                    // wstream_c1, wstream_wino (U's first part | W3' | W1 for conv1_res_f32_kernel), wstream_u2, zero page
+    BT_L1F,         // fp32 / f32s layer1: conv1_ring_f32_kernel + layer1_tail_f32_kernel (hg_l1_f32.h): wstream_c1, wstream, zero page
+    BT_L1F_WINO,    // fp32 layer1: conv1_ring_f32_kernel + layer1_wino_f32_kernel (hg_l1_wino_f32.h): wstream_c1, wstream_wino (U | W3 | Wd),
+                    // zero page
+    BT_L2F,         // fp32 / f32s layer2: conv1_ring_f32_kernel + layer2_tail_f32_kernel (hg_l1_f32.h): wstream_c1, wstream, zero page
+    BT_L2F_WINO,    // fp32 layer2: conv1_ring_f32_kernel + bottleneck_wino_f32_kernel<.., L2>: wstream_c1, wstream_wino (U's first part | W3' |
+                    // Wd'), wstream_u2, zero page
+};
 
 struct TensorDesc {
     size_t off;  // elements per view, from the start of the activation area
@@ -54,17 +73,18 @@ struct Step {
     int pool_out = -1;                // ST_BOTTLENECK: tensor receiving the fused 2x2 max-pool of `out`
     int in2 = -1;                     // ST_BOTTLENECK: low-resolution addend of the input (upsample + add fused on the consumer side)
     int add2 = -1;                    // ST_BOTTLENECK: low-resolution addend of the OUTPUT (upsample + add fused into the producer's epilogue)
-    long long wstream = -1;           // ST_BOTTLENECK, bf16 256 -> 128 -> 128 -> 256: byte offset of its weight stream behind the bf16 blob
+    BtForm form = BT_REG;             // ST_BOTTLENECK: the kernels it runs as
     int pool_in = -1;                 // ST_BOTTLENECK (ring kernels): tensor receiving the 2x2 max-pool of the block's INPUT
-    long long wstream2 = -1;          // ST_HEAD (bf16, not last): byte offset of the phase-C weight stream
-    bool l1 = false;                  // ST_BOTTLENECK, bf16 64 -> 64 -> 64 -> 128: hg_bt_l1.h (wstream = its LDS weight image)
-    bool pool_only = false;           // ... whose full-resolution output nobody reads: `out` IS the pooled tensor
+    bool pool_only = false;           // ST_BOTTLENECK (BT_L1_LP, BT_L1F*) whose full-resolution output nobody reads: `out` IS the pooled tensor
     double m1_elems = 0;              // activation elements per view this step moves in the fusion model M1
-    int t1 = -1;                      // ST_BOTTLENECK, fp32 split form (hg_c1_f32.h): the tensor conv1's kernel writes and the tail kernel reads
-    bool l2f = false;                 // ST_BOTTLENECK, fp32 layer2 128 -> 128 -> 128 -> 256 + skip convolution: conv1 + tail (hg_l1_f32.h)
-    bool l1f = false;                 // ST_BOTTLENECK, fp32 layer1 64 -> 64 -> 64 -> 128 + skip convolution: conv1 + tail (hg_l1_f32.h)
-    long long wstream_w2d = -1;       // ... 16-bit W2D: byte offset of the direct-load form of W2'
-    long long wstream_c1 = -1;        // ... and the byte offset of conv1's weight stream
+    int t1 = -1;                      // ST_BOTTLENECK, fp32 split forms (hg_c1_f32.h): the tensor conv1's kernel writes and the tail kernel reads
+    // byte offsets of the weight streams behind stream_base() (-1: none)
+    long long wstream = -1;           // direct-form stage images (ST_HEAD: Wfc's)
+    long long wstream2 = -1;          // ST_HEAD (16-bit, not last): the phase-C stage images
+    long long wstream_w2 = -1;        // BT_RING_LP with option w2d: W2' as direct-load MFMA fragments (bt_w2d_pack_kernel)
+    long long wstream_c1 = -1;        // fp32 split forms: conv1's stage images
+    long long wstream_wino = -1;      // Winograd forms: the Winograd slot (see BtForm)
+    long long wstream_u2 = -1;        // BT_SPLIT_WINO, BT_L2F_WINO: U's second part, in the slot the direct form gives its stage images
     int chain = -1;                   // >= 0: planned inside chain number `chain` (frees postponed: its tensors share no memory)
 };
 
@@ -214,6 +234,12 @@ struct df3d_hg {
         for (int id : deferred) free_tensor(id);
         deferred.clear();
     }
+    // byte offset of a new weight stream behind stream_base()
+    long long take_stream(size_t bytes) {
+        const long long off = (long long)stream_bytes;
+        stream_bytes += bytes;
+        return off;
+    }
     size_t add_param(const std::string& name, int kind, int taps, int cin, int cout, int cin_pad, int cout_pad, size_t count,
                      int kperm = 0) {
         df3d_hg_param p;
@@ -303,105 +329,78 @@ struct df3d_hg {
             st.conv2b = plan_conv(name + ".conv2", 9, planes, planes, planes, false, true, false);
             if (ds) st.conv4b = plan_conv(name + ".downsample.0", 1, cin, cin, cout, false, false, false);
             st.conv3b = plan_conv(name + ".conv3", 1, planes, planes, cout, false, false, false, lp() ? 1 : 0);
-            if (ring && lp() && cin == 128 && planes == 128 && x2 < 0 && !want_pool) {
-                // layer2: the same ring kernel with 128 input channels and the skip convolution as eight more stages
-                st.wstream = (long long)stream_bytes;
-                stream_bytes += (size_t)br_nstage(128, true) * BR_STAGE_BYTES;
-                if (w2d) {
-                    st.wstream_w2d = (long long)stream_bytes;
-                    stream_bytes += (size_t)BR_W2D_BYTES;
+            const bool tiles = tx.h % BT_TH == 0 && tx.w % BT_TW == 0;
+            const bool f32 = dtype == DF3D_DTYPE_F32;   // the Winograd forms: the exact-fp32 engine only
+            if (ring && lp() && cin == 128 && planes == 128 && x2 < 0 && !want_pool)
+                st.form = BT_RING_LP;   // layer2: the same ring kernel with 128 input channels and the skip convolution as eight more stages
+            else if (ring && cin == 256 && planes == 128)   // weights through the LDS-DMA ring (hg_bt_ring.h, hg_bt_ring_f32.h)
+                st.form = lp() ? BT_RING_LP : !split_id() ? BT_RING_F32 : wino && f32 ? BT_SPLIT_WINO : BT_SPLIT_F32;
+            else if (ring && split_l1() && !lp() && cin == 64 && planes == 64 && ds && x2 < 0 && a2 < 0 && tiles)
+                st.form = wino && f32 && tx.w % L1W_TW == 0 ? BT_L1F_WINO : BT_L1F;   // Winograd: 8 x 32 tiles
+            else if (ring && split_l2() && !lp() && cin == 128 && planes == 128 && ds && x2 < 0 && a2 < 0 && !want_pool && tiles)
+                st.form = wino && f32 ? BT_L2F_WINO : BT_L2F;
+            else if (l1 && lp() && cin == 64 && planes == 64 && tx.h % 16 == 0 && tx.w % 16 == 0)
+                st.form = BT_L1_LP;
+            // The Winograd forms keep the direct form's layout, so the buffer's size does not depend on `wino`: U's second part takes
+            // the slot of the stage images (layer1: the slot stays unused).
+            switch (st.form) {
+                case BT_REG: break;
+                case BT_L1_LP: st.wstream = take_stream(L1_W_BYTES); break;
+                case BT_RING_LP:
+                    st.wstream = take_stream((size_t)br_nstage(cin, ds) * BR_STAGE_BYTES);
+                    if (w2d) st.wstream_w2 = take_stream(BR_W2D_BYTES);
+                    break;
+                case BT_RING_F32: st.wstream = take_stream((size_t)BRF_NSTAGE * BR_STAGE_BYTES); break;
+                case BT_SPLIT_F32:
+                    st.wstream = take_stream((size_t)BRF_NSTAGE * BR_STAGE_BYTES);
+                    st.wstream_c1 = take_stream((size_t)C1_NSTAGE * BR_STAGE_BYTES);
+                    break;
+                case BT_SPLIT_WINO:
+                    st.wstream_u2 = take_stream((size_t)BRF_NSTAGE * BR_STAGE_BYTES);
+                    st.wstream_c1 = take_stream((size_t)C1_NSTAGE * BR_STAGE_BYTES);
+                    st.wstream_wino = take_stream((size_t)WN_STREAM_BYTES + C1R_W_BYTES);
+                    break;
+                case BT_L1F:
+                    st.wstream = take_stream((size_t)L1F_NSTAGE * BR_STAGE_BYTES);
+                    st.wstream_c1 = take_stream((size_t)(64 / 16) * BR_STAGE_BYTES);
+                    break;
+                case BT_L1F_WINO:
+                    take_stream((size_t)L1F_NSTAGE * BR_STAGE_BYTES);
+                    st.wstream_c1 = take_stream((size_t)(64 / 16) * BR_STAGE_BYTES);
+                    st.wstream_wino = take_stream(L1W_STREAM_BYTES);
+                    break;
+                case BT_L2F:
+                    st.wstream = take_stream((size_t)L2F_NSTAGE * BR_STAGE_BYTES);
+                    st.wstream_c1 = take_stream((size_t)(128 / 16) * BR_STAGE_BYTES);
+                    break;
+                case BT_L2F_WINO:
+                    st.wstream_u2 = take_stream((size_t)L2F_NSTAGE * BR_STAGE_BYTES);
+                    st.wstream_c1 = take_stream((size_t)(128 / 16) * BR_STAGE_BYTES);
+                    st.wstream_wino = take_stream(WN_STREAM_BYTES_L2);
+                    break;
+            }
+            if (st.form != BT_REG && cin == 256 && pool_input && x2 < 0 && pooled_of[x] < 0) {   // the ring kernels pool their input on the side
+                st.pool_in = new_tensor(tx.h / 2, tx.w / 2, cin);
+                pooled_of[x] = st.pool_in;
+                elems_per_view += (double)tx.h * tx.w * cin * 1.25;  // model M1 still counts the pooling pass
+            }
+            if (st.wstream_c1 >= 0) st.t1 = new_tensor(tx.h, tx.w, planes);   // split forms: conv1 on every pixel once, the rest on tiles
+            // layer1 (16-bit; fp32 since round 5): the tail writes the pooled tensor only when the full-resolution output (15 of the
+            // block's 37 GB per 896 views) has no other reader
+            st.pool_only = want_pool && only_pool && (st.form == BT_L1_LP || st.form == BT_L1F || st.form == BT_L1F_WINO);
+            int result;
+            if (st.pool_only) {
+                st.out = new_tensor(tx.h / 2, tx.w / 2, cout);
+                result = new_virtual_tensor(tx.h, tx.w, cout);
+                pooled_of[result] = st.out;
+            } else {
+                st.out = result = new_tensor(tx.h, tx.w, cout);
+                if (want_pool) {  // the consumer max-pools this tensor: the epilogue writes the pooled copy too (no pool step)
+                    st.pool_out = new_tensor(tx.h / 2, tx.w / 2, cout);
+                    pooled_of[st.out] = st.pool_out;
                 }
             }
-            if (ring && cin == 256 && planes == 128) {   // weights through the LDS-DMA ring (hg_bt_ring.h, hg_bt_ring_f32.h)
-                st.wstream = (long long)stream_bytes;
-                stream_bytes += (size_t)(lp() ? BR_NSTAGE : BRF_NSTAGE) * BR_STAGE_BYTES;
-                if (w2d && lp()) {
-                    st.wstream_w2d = (long long)stream_bytes;
-                    stream_bytes += (size_t)BR_W2D_BYTES;
-                }
-                if (pool_input && x2 < 0 && pooled_of[x] < 0) {
-                    st.pool_in = new_tensor(tx.h / 2, tx.w / 2, cin);
-                    pooled_of[x] = st.pool_in;
-                    elems_per_view += (double)tx.h * tx.w * cin * 1.25;  // model M1 still counts the pooling pass
-                }
-                if (split_id() && !lp()) {   // fp32 split form: conv1 on every pixel once, the rest on tiles
-                    st.wstream_c1 = (long long)stream_bytes;
-                    stream_bytes += (size_t)C1_NSTAGE * BR_STAGE_BYTES;
-                    st.t1 = new_tensor(tx.h, tx.w, planes);
-                    if (wino && dtype == DF3D_DTYPE_F32) {   // the tail's 3x3 in the Winograd domain: U = G g G^T as per-wave MFMA fragments
-                        st.wstream_w2d = (long long)stream_bytes;
-                        stream_bytes += (size_t)WN_STREAM_BYTES + C1R_W_BYTES;   // U, then W3 with permuted rows, then W1 for the LDS-resident conv1 (hg_c1_res_f32.h)
-                    }
-                }
-            }
-            if (ring && split_l1() && !lp() && cin == 64 && planes == 64 && ds && x2 < 0 && a2 < 0 && tx.h % BT_TH == 0 && tx.w % BT_TW == 0) {
-                // fp32 layer1 in the split form: conv1 on every pixel once, the rest on tiles (hg_l1_f32.h)
-                st.l1f = true;
-                st.wstream = (long long)stream_bytes;
-                stream_bytes += (size_t)L1F_NSTAGE * BR_STAGE_BYTES;
-                st.wstream_c1 = (long long)stream_bytes;
-                stream_bytes += (size_t)(64 / 16) * BR_STAGE_BYTES;
-                st.t1 = new_tensor(tx.h, tx.w, planes);
-                if (wino && dtype == DF3D_DTYPE_F32 && tx.w % L1W_TW == 0) {   // its 3x3 in the Winograd domain (hg_l1_wino_f32.h: 8 x 32 tiles): U | W3 | Wd
-                    st.wstream_w2d = (long long)stream_bytes;
-                    stream_bytes += (size_t)L1W_STREAM_BYTES;
-                }
-                if (want_pool && only_pool) {   // round 5: as the 16-bit layer1 kernel, the tail writes the pooled tensor only (the full-resolution
-                                                // output, 15 of the block's 37 GB per 896 views, has no other reader)
-                    st.pool_only = true;
-                    st.out = new_tensor(tx.h / 2, tx.w / 2, cout);
-                    const int virt = new_virtual_tensor(tx.h, tx.w, cout);
-                    pooled_of[virt] = st.out;
-                    elems_per_view += (double)tx.h * tx.w * cout * 1.25;  // model M1 still counts the pooling pass
-                    push_step(st);
-                    const double px = (double)tx.h * tx.w;
-                    account_conv(px, 1, cin, planes, false);
-                    account_conv(px, 9, planes, planes, false);
-                    account_conv(px, 1, cin, cout, false);
-                    account_conv(px, 1, planes, cout, true);
-                    m1_close();
-                    free_tensor(st.t1);
-                    return virt;
-                }
-            }
-            if (ring && split_l2() && !lp() && cin == 128 && planes == 128 && ds && x2 < 0 && a2 < 0 && !want_pool && tx.h % BT_TH == 0 && tx.w % BT_TW == 0) {
-                st.l2f = true;   // fp32 layer2, the same split form
-                st.wstream = (long long)stream_bytes;
-                stream_bytes += (size_t)L2F_NSTAGE * BR_STAGE_BYTES;
-                st.wstream_c1 = (long long)stream_bytes;
-                stream_bytes += (size_t)(128 / 16) * BR_STAGE_BYTES;
-                st.t1 = new_tensor(tx.h, tx.w, planes);
-                if (wino && dtype == DF3D_DTYPE_F32) {   // its 3x3 in the Winograd domain too (hg_bt_wino_f32.h, L2): U | W3 | Wd
-                    st.wstream_w2d = (long long)stream_bytes;
-                    stream_bytes += (size_t)WN_STREAM_BYTES_L2;
-                }
-            }
-            if (l1 && lp() && cin == 64 && planes == 64 && tx.h % 16 == 0 && tx.w % 16 == 0) {
-                st.l1 = true;   // all weights resident in LDS (hg_bt_l1.h)
-                st.wstream = (long long)stream_bytes;
-                stream_bytes += L1_W_BYTES;
-                if (want_pool && only_pool) {   // the full-resolution tensor is never written
-                    st.pool_only = true;
-                    st.out = new_tensor(tx.h / 2, tx.w / 2, cout);
-                    const int virt = new_virtual_tensor(tx.h, tx.w, cout);
-                    pooled_of[virt] = st.out;
-                    elems_per_view += (double)tx.h * tx.w * cout * 1.25;  // model M1 still counts the pooling pass
-                    push_step(st);
-                    const double px = (double)tx.h * tx.w;
-                    account_conv(px, 1, cin, planes, false);
-                    account_conv(px, 9, planes, planes, false);
-                    account_conv(px, 1, cin, cout, false);
-                    account_conv(px, 1, planes, cout, true);
-                    m1_close();
-                    return virt;
-                }
-            }
-            st.out = new_tensor(tx.h, tx.w, cout);
-            if (want_pool) {  // the consumer max-pools this tensor: the epilogue writes the pooled copy too (no pool step)
-                st.pool_out = new_tensor(tx.h / 2, tx.w / 2, cout);
-                pooled_of[st.out] = st.pool_out;
-                elems_per_view += (double)tx.h * tx.w * cout * 1.25;  // model M1 still counts the pooling pass
-            }
+            if (want_pool) elems_per_view += (double)tx.h * tx.w * cout * 1.25;  // model M1 still counts the pooling pass
             push_step(st);
             const double px = (double)tx.h * tx.w;
             account_conv(px, 1, cin, planes, false);
@@ -410,7 +409,7 @@ struct df3d_hg {
             account_conv(px, 1, planes, cout, true);
             m1_close();
             if (st.t1 >= 0) free_tensor(st.t1);
-            return st.out;
+            return result;
         }
         int a = conv(name + ".conv1", x, 1, planes, true, true, -1);
         int b = conv(name + ".conv2", a, 9, planes, false, true, -1);
@@ -557,12 +556,8 @@ struct df3d_hg {
                 st.kind = ST_HEAD;
                 st.last = last;
                 if (ring) {   // Wfc through the LDS-DMA stage ring (hg_head.h)
-                    st.wstream = (long long)stream_bytes;
-                    stream_bytes += (size_t)(lp() ? HD_FC_STAGES : HD_FC_STAGES_F32) * BR_STAGE_BYTES;
-                    if (!last && lp()) {
-                        st.wstream2 = (long long)stream_bytes;
-                        stream_bytes += (size_t)HD_FC2_STAGES * BR_STAGE_BYTES;
-                    }
+                    st.wstream = take_stream((size_t)(lp() ? HD_FC_STAGES : HD_FC_STAGES_F32) * BR_STAGE_BYTES);
+                    if (!last && lp()) st.wstream2 = take_stream((size_t)HD_FC2_STAGES * BR_STAGE_BYTES);
                 }
                 st.name = last ? "score." + S : "score_." + S;
                 st.in = r;
@@ -638,7 +633,6 @@ struct df3d_hg {
 
 namespace {
 
-// hipFuncSetAttribute acts on the CURRENT device: remember per device (bit i of `mask`) where it has been applied
 // compute units of the current device (persistent kernels launch one workgroup per CU)
 inline int cu_count() {
     static int cached[64] = {0};
@@ -651,6 +645,7 @@ inline int cu_count() {
     return cached[dev];
 }
 
+// hipFuncSetAttribute acts on the CURRENT device: remember per device (bit i of `mask`) where it has been applied
 inline bool first_use_on_this_device(unsigned& mask) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 31) return true;
@@ -658,46 +653,6 @@ inline bool first_use_on_this_device(unsigned& mask) {
     mask |= 1u << dev;
     return first;
 }
-
-template <typename T, int TAPS, int BN, int RB>
-int launch_conv_t(const ConvArgs& a, hipStream_t s) {
-    constexpr int LDS = 2 * (BM + BN) * (RB + 16);
-    static unsigned attr_done = 0;
-    if (first_use_on_this_device(attr_done))
-        DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_mfma_kernel<T, TAPS, BN, RB>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    const long long mt = (a.M + BM - 1) / BM;
-    dim3 grid((unsigned)mt, (unsigned)(a.cout / BN));
-    hipLaunchKernelGGL((conv_mfma_kernel<T, TAPS, BN, RB>), grid, dim3(256), LDS, s, a);
-    DF3D_LAUNCH_CHECK();
-    return DF3D_OK;
-}
-
-template <typename T, int TAPS, int BN>
-int launch_conv_rb(const ConvArgs& a, int rb, hipStream_t s) {
-    if (rb == 128) return launch_conv_t<T, TAPS, BN, 128>(a, s);
-    return launch_conv_t<T, TAPS, BN, 64>(a, s);
-}
-
-template <typename T>
-int launch_conv(const ConvArgs& a, int taps, int rb, hipStream_t s) {
-    int bn = (a.cout % 128 == 0) ? 128 : (a.cout % 64 == 0 ? 64 : 32);
-    // a launch too small to fill the chip with 128-channel tiles (the 4 x 8 hourglass level: 224 workgroups for 896 views) takes
-    // narrower ones: four times the workgroups, each with a quarter of the weights to pull -- the same K order per output, so the
-    // same bits
-    const long long wgs128 = ((a.M + BM - 1) / BM) * (a.cout / bn);
-    if (bn == 128 && wgs128 < 2LL * cu_count()) bn = taps == 1 ? 32 : 64;
-    if (taps == 1) {
-        if (bn == 128) return launch_conv_rb<T, 1, 128>(a, rb, s);
-        if (bn == 64) return launch_conv_rb<T, 1, 64>(a, rb, s);
-        return launch_conv_rb<T, 1, 32>(a, rb, s);
-    }
-    if (bn == 128) return launch_conv_rb<T, 9, 128>(a, rb, s);
-    if (bn == 64) return launch_conv_rb<T, 9, 64>(a, rb, s);
-    df3d::set_error("3x3 convolution with cout %d unsupported", a.cout);
-    return DF3D_EINVAL;
-}
-
 
 hipEvent_t get_event(df3d_hg* h) {
     if (!h->event_pool.empty()) {
@@ -710,22 +665,27 @@ hipEvent_t get_event(df3d_hg* h) {
     return e;
 }
 
+// what the profile records of a launch: flops = the work in the reference's terms, bytes = the least this launch can move (inputs read
+// once, outputs written once, intermediates on chip), bytes_m1 = what the fusion model M1 of SURVEY.md 8(d) charges for the same work
+// (every convolution's input and output, pooling and upsample passes), flops_executed (< 0: = flops) = what the kernel's MFMAs do
+struct Work {
+    double flops, bytes, bytes_m1, flops_executed = -1.0;
+};
+
 struct ScopedTimer {
     df3d_hg* h;
     hipStream_t s;
     df3d_hg::Timed t;
     bool on;
-    // bytes = the least this launch can move (inputs read once, outputs written once, intermediates on chip); bytes_m1 = what the
-    // fusion model M1 of SURVEY.md 8(d) charges for the same work (every convolution's input and output, pooling and upsample passes)
-    ScopedTimer(df3d_hg* h_, hipStream_t s_, const std::string& name, double flops, double bytes, double bytes_m1, double flops_executed = -1.0) : h(h_), s(s_), on(h_->profiling) {
+    ScopedTimer(df3d_hg* h_, hipStream_t s_, const std::string& name, const Work& w) : h(h_), s(s_), on(h_->profiling) {
         if (!on) return;
         t.a = get_event(h);
         t.b = get_event(h);
         t.cls = h->kernel_class(name);
-        t.flops = flops;
-        t.flops_executed = flops_executed >= 0.0 ? flops_executed : flops;
-        t.bytes = bytes;
-        t.bytes_m1 = bytes_m1;
+        t.flops = w.flops;
+        t.flops_executed = w.flops_executed >= 0.0 ? w.flops_executed : w.flops;
+        t.bytes = w.bytes;
+        t.bytes_m1 = w.bytes_m1;
         (void)hipEventRecord(t.a, s);
     }
     ~ScopedTimer() {
@@ -735,29 +695,6 @@ struct ScopedTimer {
     }
 };
 
-template <typename T, int CIN, int PL, bool DS, bool UP = false, bool ADD2 = false>
-int launch_bottleneck_t(const BottleneckArgs& a, int blocks, hipStream_t s) {
-    using C = BtCfg<T, CIN, PL, DS>;
-    static unsigned attr_done = 0;
-    if (first_use_on_this_device(attr_done))
-        DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bottleneck_kernel<T, CIN, PL, DS, UP, ADD2>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
-    hipLaunchKernelGGL((bottleneck_kernel<T, CIN, PL, DS, UP, ADD2>), dim3(blocks), dim3(256), C::LDS_BYTES, s, a);
-    DF3D_LAUNCH_CHECK();
-    return DF3D_OK;
-}
-
-template <typename T>
-int launch_bottleneck(const BottleneckArgs& a, int cin, int pl, int blocks, hipStream_t s) {
-    if (cin == 256 && pl == 128 && a.in2) return launch_bottleneck_t<T, 256, 128, false, true>(a, blocks, s);
-    if (cin == 256 && pl == 128 && a.add2) return launch_bottleneck_t<T, 256, 128, false, false, true>(a, blocks, s);
-    if (cin == 256 && pl == 128) return launch_bottleneck_t<T, 256, 128, false>(a, blocks, s);
-    if (cin == 128 && pl == 128) return launch_bottleneck_t<T, 128, 128, true>(a, blocks, s);
-    if (cin == 64 && pl == 64) return launch_bottleneck_t<T, 64, 64, true>(a, blocks, s);
-    df3d::set_error("fused bottleneck %d -> %d unsupported", cin, pl);
-    return DF3D_EINVAL;
-}
-
 template <typename T> struct TypeName;
 template <> struct TypeName<float> { static constexpr const char* value = "float"; };
 template <> struct TypeName<__hip_bfloat16> { static constexpr const char* value = "__hip_bfloat16"; };
@@ -766,65 +703,215 @@ template <> struct TypeName<F32S> { static constexpr const char* value = "hgk::F
 // the element type of the kernels that only move or compare float32 data (pools, upsample-add, export): F32S tensors ARE float32 tensors
 template <typename T> using StorageT = std::conditional_t<std::is_same<T, F32S>::value, float, T>;
 
-// one launcher per 16-bit element type (hipFuncSetAttribute is per instantiation and per device)
-template <typename T, bool UP, int CIN, bool ADD2, int MODE>
-int launch_ring_lp_(const BtRingArgs& r, int blocks, int lds_bytes, hipStream_t s) {
-    static unsigned attr_done = 0;
-    if (first_use_on_this_device(attr_done))
-        DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bottleneck_ring_kernel<T, UP, CIN, ADD2, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    hipLaunchKernelGGL((bottleneck_ring_kernel<T, UP, CIN, ADD2, MODE>), dim3(blocks), dim3(256), lds_bytes, s, r);
-    DF3D_LAUNCH_CHECK();
-    return DF3D_OK;
+inline std::string targ(bool v) { return v ? "true" : "false"; }
+inline std::string targ(int v) { return std::to_string(v); }
+inline std::string targ(const char* v) { return v; }
+// a kernel instantiation's name as rocprofv3 prints it (the key of the profile tables): kname("k", float_name, 64, true) = "k<float, 64, true>"
+template <typename... A>
+std::string kname(const char* kernel, A... args) {
+    std::string s = kernel;
+    const char* sep = "<";
+    ((s += sep, s += targ(args), sep = ", "), ...);
+    return sizeof...(A) ? s + ">" : s;
 }
-// the ring kernel's MODE (hg_bt_ring.h) of a launch: 0 = all weights through the ring, 1 = W2D (round 3), 2 = W2D + the round-4 form (option `ring2`)
-inline int ring_mode(const BtRingArgs& r, int ring2) { return !r.w2d ? 0 : ring2 ? 2 : 1; }
-template <typename T, bool UP, int CIN, bool ADD2 = false>
-int launch_ring_lp(const BtRingArgs& r, int ring2, int blocks, int lds_bytes, hipStream_t s) {
-    const int mode = ring_mode(r, ring2);
-    return mode == 2 ? launch_ring_lp_<T, UP, CIN, ADD2, 2>(r, blocks, lds_bytes, s)
-           : mode    ? launch_ring_lp_<T, UP, CIN, ADD2, 1>(r, blocks, lds_bytes, s)
-                     : launch_ring_lp_<T, UP, CIN, ADD2, 0>(r, blocks, lds_bytes, s);
-}
-template <typename T, bool UP, bool ADD2 = false, bool TAIL = false>
-int launch_ring_f32(const BtRingArgs& r, int blocks, int lds_bytes, hipStream_t s) {
+
+// One launch of KERNEL, timed under `name` when profiling.  A kernel with dynamic LDS gets its limit raised once per device (the first
+// launch's lds_bytes).
+template <auto KERNEL, typename... A>
+int launch_kernel(df3d_hg* h, const std::string& name, const Work& w, dim3 grid, int threads, int lds_bytes, hipStream_t s, const A&... args) {
+    ScopedTimer tm(h, s, name, w);
     static unsigned attr_done = 0;
-    if (first_use_on_this_device(attr_done))
-        DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bottleneck_ring_f32_kernel<UP, ADD2, TAIL, T>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    hipLaunchKernelGGL((bottleneck_ring_f32_kernel<UP, ADD2, TAIL, T>), dim3(blocks), dim3(256), lds_bytes, s, r);
+    if (lds_bytes > 0 && first_use_on_this_device(attr_done))
+        DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds_bytes, s, args...);
     DF3D_LAUNCH_CHECK();
     return DF3D_OK;
 }
 
-template <bool UP, bool ADD2, bool L2 = false>
-int launch_wino_f32(const BtRingArgs& r, int blocks, hipStream_t s) {
-    static unsigned attr_done = 0;
-    if (first_use_on_this_device(attr_done))
-        DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bottleneck_wino_f32_kernel<UP, ADD2, L2>), hipFuncAttributeMaxDynamicSharedMemorySize, WN_LDS_BYTES));
-    // persistent: one workgroup per CU (it needs the whole register file), walking tiles with stride gridDim; a multiple of 8 keeps virtual
-    // block ids on their XCD (hg_bt_wino_f32.h tile_of)
+template <typename T, int TAPS, int BN, int RB>
+int launch_conv_t(df3d_hg* h, const ConvArgs& a, const Work& w, hipStream_t s) {
+    const dim3 grid((unsigned)((a.M + BM - 1) / BM), (unsigned)(a.cout / BN));
+    return launch_kernel<conv_mfma_kernel<T, TAPS, BN, RB>>(h, kname("conv_mfma_kernel", TypeName<T>::value, TAPS, BN, RB), w, grid, 256,
+                                                            2 * (BM + BN) * (RB + 16), s, a);
+}
+
+template <typename T, int TAPS, int BN>
+int launch_conv_rb(df3d_hg* h, const ConvArgs& a, int rb, const Work& w, hipStream_t s) {
+    if (rb == 128) return launch_conv_t<T, TAPS, BN, 128>(h, a, w, s);
+    return launch_conv_t<T, TAPS, BN, 64>(h, a, w, s);
+}
+
+template <typename T>
+int launch_conv(df3d_hg* h, const ConvArgs& a, int taps, int rb, const Work& w, hipStream_t s) {
+    int bn = (a.cout % 128 == 0) ? 128 : (a.cout % 64 == 0 ? 64 : 32);
+    // a launch too small to fill the chip with 128-channel tiles (the 4 x 8 hourglass level: 224 workgroups for 896 views) takes
+    // narrower ones: four times the workgroups, each with a quarter of the weights to pull -- the same K order per output, so the
+    // same bits
+    const long long wgs128 = ((a.M + BM - 1) / BM) * (a.cout / bn);
+    if (bn == 128 && wgs128 < 2LL * cu_count()) bn = taps == 1 ? 32 : 64;
+    if (taps == 1) {
+        if (bn == 128) return launch_conv_rb<T, 1, 128>(h, a, rb, w, s);
+        if (bn == 64) return launch_conv_rb<T, 1, 64>(h, a, rb, w, s);
+        return launch_conv_rb<T, 1, 32>(h, a, rb, w, s);
+    }
+    if (bn == 128) return launch_conv_rb<T, 9, 128>(h, a, rb, w, s);
+    if (bn == 64) return launch_conv_rb<T, 9, 64>(h, a, rb, w, s);
+    df3d::set_error("3x3 convolution with cout %d unsupported", a.cout);
+    return DF3D_EINVAL;
+}
+
+template <typename T, bool LAST>
+int launch_head(df3d_hg* h, const HeadArgs& a, const Work& w, hipStream_t s) {
+    return launch_kernel<head_kernel<T, LAST>>(h, kname("head_kernel", TypeName<T>::value, LAST), w, dim3((unsigned)((a.M + 127) / 128)), 256,
+                                               HeadCfg<T, LAST>::LDS_BYTES, s, a);
+}
+
+// one fused-bottleneck launch: pixels of its views, the M1 bytes of its step, its 8 x 16 output tiles
+struct BtLaunch {
+    double px, m1;
+    int tiles;
+    bool pool_only;
+};
+// the block's work in the reference's terms: conv1 (when this kernel runs it), the 3x3 (taps3 = 9; fewer: the MFMA work a Winograd kernel
+// executes), conv3, the skip convolution (DS)
+inline double bt_flops(double px, int cin, int pl, bool conv1, bool ds, double taps3 = 9.0) {
+    return 2.0 * px * ((conv1 ? (double)cin * pl : 0.0) + taps3 * pl * pl + 2.0 * pl * pl + (ds ? 2.0 * cin * pl : 0.0));
+}
+// the least a launch moves: its input, t1 (the tails of the split forms), its output (the pooled quarter only: pool_only)
+inline double bt_bytes(double px, int eb, int cin, int pl, bool t1, bool pool_only) {
+    return px * eb * (cin + (t1 ? pl : 0) + (pool_only ? 0.5 * pl : 2.0 * pl));
+}
+
+template <typename T, int CIN, int PL, bool DS, bool UP = false, bool ADD2 = false>
+int launch_bottleneck_t(df3d_hg* h, const BottleneckArgs& a, const BtLaunch& b, hipStream_t s) {
+    return launch_kernel<bottleneck_kernel<T, CIN, PL, DS, UP, ADD2>>(
+        h, kname("bottleneck_kernel", TypeName<T>::value, CIN, PL, DS, UP, ADD2),
+        Work{bt_flops(b.px, CIN, PL, true, DS), bt_bytes(b.px, sizeof(T), CIN, PL, false, false), b.m1}, dim3(b.tiles), 256,
+        BtCfg<T, CIN, PL, DS>::LDS_BYTES, s, a);
+}
+
+template <typename T>
+int launch_bottleneck(df3d_hg* h, const BottleneckArgs& a, int cin, int pl, const BtLaunch& b, hipStream_t s) {
+    if (cin == 256 && pl == 128 && a.in2) return launch_bottleneck_t<T, 256, 128, false, true>(h, a, b, s);
+    if (cin == 256 && pl == 128 && a.add2) return launch_bottleneck_t<T, 256, 128, false, false, true>(h, a, b, s);
+    if (cin == 256 && pl == 128) return launch_bottleneck_t<T, 256, 128, false>(h, a, b, s);
+    if (cin == 128 && pl == 128) return launch_bottleneck_t<T, 128, 128, true>(h, a, b, s);
+    if (cin == 64 && pl == 64) return launch_bottleneck_t<T, 64, 64, true>(h, a, b, s);
+    df3d::set_error("fused bottleneck %d -> %d unsupported", cin, pl);
+    return DF3D_EINVAL;
+}
+
+template <typename T>
+int launch_l1_lp(df3d_hg* h, const BtL1Args& a, const BtLaunch& b, hipStream_t s) {
+    const int tiles = a.V * (a.H / L1_TH) * (a.W / BT_TW);
+    return launch_kernel<bottleneck_l1_kernel<T>>(h, kname("bottleneck_l1_kernel", TypeName<T>::value),
+                                                  Work{bt_flops(b.px, 64, 64, true, true), bt_bytes(b.px, sizeof(T), 64, 64, false, b.pool_only), b.m1},
+                                                  dim3(std::min(tiles, cu_count())), L1_WAVES * 64, L1_LDS_BYTES, s, a);
+}
+
+// MODE (hg_bt_ring.h): 0 = all weights through the ring, 1 = W2D (round 3), 2 = W2D + the round-4 form (option `ring2`)
+template <typename T, bool UP, int CIN, bool ADD2, int MODE>
+int launch_ring_lp_(df3d_hg* h, const BtRingArgs& r, const BtLaunch& b, int lds_bytes, hipStream_t s) {
+    return launch_kernel<bottleneck_ring_kernel<T, UP, CIN, ADD2, MODE>>(
+        h, kname("bottleneck_ring_kernel", TypeName<T>::value, UP, CIN, ADD2, MODE),
+        Work{bt_flops(b.px, CIN, 128, true, CIN == 128), bt_bytes(b.px, sizeof(T), CIN, 128, false, false), b.m1}, dim3(b.tiles), 256, lds_bytes, s, r);
+}
+template <typename T, bool UP, int CIN, bool ADD2 = false>
+int launch_ring_lp(df3d_hg* h, const BtRingArgs& r, const BtLaunch& b, int lds_bytes, hipStream_t s) {
+    return !r.w2d    ? launch_ring_lp_<T, UP, CIN, ADD2, 0>(h, r, b, lds_bytes, s)
+           : h->ring2 ? launch_ring_lp_<T, UP, CIN, ADD2, 2>(h, r, b, lds_bytes, s)
+                      : launch_ring_lp_<T, UP, CIN, ADD2, 1>(h, r, b, lds_bytes, s);
+}
+
+// TAIL: the split form's tail (conv1 ran before, t1 comes from memory)
+template <typename T, bool UP, bool ADD2, bool TAIL>
+int launch_ring_f32(df3d_hg* h, const BtRingArgs& r, const BtLaunch& b, int lds_bytes, hipStream_t s) {
+    return launch_kernel<bottleneck_ring_f32_kernel<UP, ADD2, TAIL, T>>(
+        h, kname("bottleneck_ring_f32_kernel", UP, ADD2, TAIL, TypeName<T>::value),
+        Work{bt_flops(b.px, 256, 128, !TAIL, false), bt_bytes(b.px, 4, 256, 128, TAIL, false), b.m1}, dim3(b.tiles), 256, lds_bytes, s, r);
+}
+
+// the ring kernels' dynamic LDS (development builds: more, to hold one workgroup per CU: > 80 KB)
+inline int ring_lds_bytes() {
+    int lds_bytes = BR_LDS_BYTES;
+#ifdef DF3D_BT_TIMING
+    if (const char* e = getenv("BR_LDS")) lds_bytes = atoi(e);
+#endif
+#ifdef BR_FORCE_LDS
+    lds_bytes = BR_FORCE_LDS;
+#endif
+    return lds_bytes;
+}
+
+// conv1 of the split forms (hg_c1_f32.h): persistent, two workgroups per CU
+template <typename T, bool UP, int CIN, int PL>
+int launch_conv1_f32(df3d_hg* h, const Conv1Args& c, const BtLaunch& b, hipStream_t s) {
+    return launch_kernel<conv1_ring_f32_kernel<UP, CIN, PL, T>>(h, kname("conv1_ring_f32_kernel", UP, CIN, PL, TypeName<T>::value),
+                                                                Work{2.0 * b.px * CIN * PL, b.px * 4.0 * (CIN + PL), 0.0},
+                                                                dim3((unsigned)std::min<long long>(c.M / 128, 2LL * cu_count())), 256, C1_LDS_BYTES, s, c);
+}
+
+// conv1 of the Winograd identity form with W1 resident in LDS (hg_c1_res_f32.h, option c1res): one workgroup per CU
+inline int launch_conv1_res_f32(df3d_hg* h, const Conv1Args& c, const BtLaunch& b, hipStream_t s) {
+    return launch_kernel<conv1_res_f32_kernel>(h, kname("conv1_res_f32_kernel"), Work{2.0 * b.px * 256 * 128, b.px * 4.0 * (256 + 128), 0.0},
+                                               dim3((unsigned)std::min<long long>(c.M / 128, (long long)(cu_count() & ~7))), 256, C1R_LDS_BYTES, s, c);
+}
+
+template <typename T>
+int launch_layer1_tail_f32(df3d_hg* h, const BtRingArgs& r, const BtLaunch& b, hipStream_t s) {
+    return launch_kernel<layer1_tail_f32_kernel<T>>(h, kname("layer1_tail_f32_kernel", TypeName<T>::value),
+                                                    Work{bt_flops(b.px, 64, 64, false, true), bt_bytes(b.px, 4, 64, 64, true, b.pool_only), b.m1},
+                                                    dim3(b.tiles), 256, L1F_LDS_BYTES, s, r);
+}
+
+template <typename T>
+int launch_layer2_tail_f32(df3d_hg* h, const BtRingArgs& r, const BtLaunch& b, hipStream_t s) {
+    return launch_kernel<layer2_tail_f32_kernel<T>>(h, kname("layer2_tail_f32_kernel", TypeName<T>::value),
+                                                    Work{bt_flops(b.px, 128, 128, false, true), bt_bytes(b.px, 4, 128, 128, true, false), b.m1},
+                                                    dim3(b.tiles), 256, L2F_LDS_BYTES, s, r);
+}
+
+// The Winograd tails are persistent: one workgroup per CU (it needs the whole register file), walking tiles with stride gridDim; a
+// multiple of 8 keeps virtual block ids on their XCD (hg_bt_wino_f32.h tile_of).  FLOPs: the direct form's; the kernels EXECUTE 24/72
+// (F(2x4, 3x3)) or 4/9 (layer1's F(2x2, 3x3)) of the 3x3's.
+template <bool UP, bool ADD2, bool L2>
+int launch_wino_f32(df3d_hg* h, const BtRingArgs& r, const BtLaunch& b, hipStream_t s) {
+    constexpr int CIN = L2 ? 128 : 256;
     const int cus = cu_count() & ~7;
-    hipLaunchKernelGGL((bottleneck_wino_f32_kernel<UP, ADD2, L2>), dim3(blocks <= cus ? blocks : cus), dim3(256), WN_LDS_BYTES, s, r);
-    DF3D_LAUNCH_CHECK();
-    return DF3D_OK;
+    return launch_kernel<bottleneck_wino_f32_kernel<UP, ADD2, L2>>(
+        h, kname("bottleneck_wino_f32_kernel", UP, ADD2, L2),
+        Work{bt_flops(b.px, CIN, 128, false, L2), bt_bytes(b.px, 4, CIN, 128, true, false), b.m1, bt_flops(b.px, CIN, 128, false, L2, 3.0)},
+        dim3(b.tiles <= cus ? b.tiles : cus), 256, WN_LDS_BYTES, s, r);
+}
+
+inline int launch_layer1_wino_f32(df3d_hg* h, const BtRingArgs& r, const BtLaunch& b, hipStream_t s) {
+    const int tiles = r.V * (r.H / BT_TH) * (r.W / L1W_TW), cus = cu_count() & ~7;
+    return launch_kernel<layer1_wino_f32_kernel>(
+        h, kname("layer1_wino_f32_kernel"),
+        Work{bt_flops(b.px, 64, 64, false, true), bt_bytes(b.px, 4, 64, 64, true, b.pool_only), b.m1, bt_flops(b.px, 64, 64, false, true, 4.0)},
+        dim3(tiles <= cus ? tiles : cus), 256, L1W_LDS_BYTES, s, r);
 }
 
 template <typename T>
 int run_steps(df3d_hg* h, const float* images_all, int n_all, int upto, float* heatmaps_all, unsigned char* act, hipStream_t s) {
-    const int eb = sizeof(T);
-    const char* const tname = TypeName<T>::value;   // as rocprofv3 prints the template argument
+    constexpr int eb = sizeof(T);
+    constexpr bool F32 = std::is_same<T, float>::value;
     // the weights the kernels read: the caller's float32 blob (f32), its 16-bit copy (bf16 / f16), its pre-split copy (f32s); biases and
     // BatchNorm coefficients always come from the blob
-    const unsigned char* wb = reinterpret_cast<const unsigned char*>(std::is_same<T, float>::value ? (const void*)h->blob : h->lowp);
+    const unsigned char* wb = reinterpret_cast<const unsigned char*>(F32 ? (const void*)h->blob : h->lowp);
+    auto wstream = [&](long long off) { return reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base() + off; };
     // one plan step on the views [v0, v0 + n) of the batch: every tensor is [views][h][w][pitch], so a view range is a
     // contiguous slice of each (the whole batch: v0 = 0, n = n_all)
     auto launch = [&](int i, int v0, int n) -> int {
         const Step& st = h->steps[i];
         auto tptr = [&](int id) -> unsigned char* {
+            if (id < 0) return nullptr;
             const TensorDesc& t = h->tensors[id];
             return act + (t.off * (size_t)n_all + (size_t)v0 * t.h * t.w * t.pitch) * eb;
         };
         const float* const images = images_all ? images_all + (size_t)v0 * h->H * h->W * 3 : nullptr;
         float* const heatmaps = heatmaps_all ? heatmaps_all + (size_t)v0 * h->classes * (h->H / 4) * (h->W / 4) : nullptr;
+        const double m1 = st.m1_elems * n * eb;
         switch (st.kind) {
             case ST_STEM: {
                 StemArgs a;
@@ -843,24 +930,23 @@ int run_steps(df3d_hg* h, const float* images_all, int n_all, int upto, float* h
                 }
                 const int blocks = n * (h->H / 2 / 8) * (h->W / 2 / 16);
                 const double opx = (double)n * (h->H / 2) * (h->W / 2);
-                ScopedTimer tm(h, s, std::is_same<T, F32S>::value ? std::string("stem_f32s_kernel") : std::string(eb == 2 ? "stem_lp_kernel<" : "stem_kernel<") + TypeName<StorageT<T>>::value + ">",
-                               2.0 * opx * 147 * 64, opx * (12.0 * 4 + 64.0 * eb), st.m1_elems * n * eb);
-                if constexpr (sizeof(T) == 2) {
-                    hipLaunchKernelGGL((stem_lp_kernel<T>), dim3(std::min(blocks, 4 * cu_count())), dim3(256), 0, s, a);   // persistent: weights once per workgroup
+                const Work w{2.0 * opx * 147 * 64, opx * (12.0 * 4 + 64.0 * eb), m1};
+                // persistent: the weights once per workgroup
+                if constexpr (eb == 2) {
+                    return launch_kernel<stem_lp_kernel<T>>(h, kname("stem_lp_kernel", TypeName<T>::value), w, dim3(std::min(blocks, 4 * cu_count())), 256, 0, s, a);
                 } else if constexpr (std::is_same<T, F32S>::value) {
                     a.w_bf16 = wb + st.conv.w_off * eb;   // the hi / lo half tiles in the stem's slot of the pre-split copy (stem_relayout_f32s_kernel)
-                    hipLaunchKernelGGL(stem_f32s_kernel, dim3(std::min(blocks, 2 * cu_count())), dim3(256), 0, s, a);   // persistent (57 KB of LDS: two per CU)
-                } else
-                    hipLaunchKernelGGL((stem_kernel<StorageT<T>>), dim3(std::min(blocks, 3 * cu_count())), dim3(256), 0, s, a);   // persistent: weights once per workgroup
-                DF3D_LAUNCH_CHECK();
-                break;
+                    return launch_kernel<stem_f32s_kernel>(h, kname("stem_f32s_kernel"), w, dim3(std::min(blocks, 2 * cu_count())), 256, 0, s, a);   // 57 KB of LDS: two per CU
+                } else {
+                    return launch_kernel<stem_kernel<T>>(h, kname("stem_kernel", TypeName<T>::value), w, dim3(std::min(blocks, 3 * cu_count())), 256, 0, s, a);
+                }
             }
             case ST_CONV: {
                 const TensorDesc& ti = h->tensors[st.in];
                 ConvArgs a;
                 a.in = tptr(st.in);
-                a.out = st.out >= 0 ? tptr(st.out) : nullptr;
-                a.res = st.res >= 0 ? tptr(st.res) : nullptr;
+                a.out = tptr(st.out);
+                a.res = tptr(st.res);
                 a.out_nchw = st.conv.nchw_out ? heatmaps : nullptr;
                 a.w = wb + st.conv.w_off * eb;
                 a.bias = h->blob + st.conv.b_off;
@@ -880,248 +966,162 @@ int run_steps(df3d_hg* h, const float* images_all, int n_all, int upto, float* h
                 int rb = (st.conv.cin_pad % ke128 == 0) ? 128 : 64;
                 if (h->rb_override == 64) rb = 64;
                 const double mm = (double)a.M;
-                int bn_tile = (a.cout % 128 == 0) ? 128 : (a.cout % 64 == 0 ? 64 : 32);
-                if (bn_tile == 128 && ((a.M + BM - 1) / BM) * (a.cout / bn_tile) < 2LL * cu_count()) bn_tile = st.conv.taps == 1 ? 32 : 64;   // as launch_conv picks
-                ScopedTimer tm(h, s, std::string("conv_mfma_kernel<") + tname + ", " + std::to_string(st.conv.taps) + ", " + std::to_string(bn_tile) + ", " + std::to_string(rb) + ">",
-                               2.0 * mm * st.conv.taps * st.conv.cin * st.conv.cout,
-                               mm * eb * (st.conv.cin + st.conv.cout + (st.res >= 0 ? st.conv.cout : 0)), st.m1_elems * n * eb);
-                if (int rc = launch_conv<T>(a, st.conv.taps, rb, s)) return rc;
-                break;
+                const Work w{2.0 * mm * st.conv.taps * st.conv.cin * st.conv.cout, mm * eb * (st.conv.cin + st.conv.cout + (st.res >= 0 ? st.conv.cout : 0)), m1};
+                return launch_conv<T>(h, a, st.conv.taps, rb, w, s);
             }
             case ST_BOTTLENECK: {
                 const TensorDesc& ti = h->tensors[st.in];
                 const bool ds = st.res < 0;
-                BottleneckArgs a;
-                a.in = tptr(st.in);
-                a.in2 = st.in2 >= 0 ? tptr(st.in2) : nullptr;
-                a.add2 = st.add2 >= 0 ? tptr(st.add2) : nullptr;
-                a.out = tptr(st.out);
-                a.pool = st.pool_out >= 0 ? tptr(st.pool_out) : nullptr;
-                a.w1 = wb + st.conv.w_off * eb;
-                a.w2 = wb + st.conv2b.w_off * eb;
-                a.w3 = wb + st.conv3b.w_off * eb;
-                a.wd = ds ? wb + st.conv4b.w_off * eb : nullptr;
-                a.b1 = h->blob + st.conv.b_off;
-                a.b2 = h->blob + st.conv2b.b_off;
-                a.b3 = h->blob + st.conv3b.b_off;
-                a.bd = ds ? h->blob + st.conv4b.b_off : nullptr;
-                a.s1 = h->blob + st.conv.s_off;
-                a.t1 = h->blob + st.conv.t_off;
-                a.V = n;
-                a.H = ti.h;
-                a.W = ti.w;
                 const int cin = st.conv.cin, pl = st.conv.cout;
-                const double px = (double)n * ti.h * ti.w;
-                if (st.l1) {
-                    BtL1Args r;
-                    r.in = a.in;
-                    r.out = st.pool_only ? nullptr : a.out;
-                    r.pool = st.pool_only ? a.out : a.pool;
-                    r.wimage = reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base() + st.wstream;
-                    r.b1 = a.b1; r.b2 = a.b2; r.b3 = a.b3; r.bd = a.bd; r.s1 = a.s1; r.t1 = a.t1;
-                    r.V = n; r.H = ti.h; r.W = ti.w;
-                    ScopedTimer tm(h, s, std::string("bottleneck_l1_kernel<") + tname + ">", 2.0 * px * ((double)cin * pl + 9.0 * pl * pl + 2.0 * pl * pl + 2.0 * cin * pl),
-                                   px * eb * (cin + (st.pool_only ? 0.5 * pl : 2.0 * pl)), st.m1_elems * n * eb);
-                    const int tiles = n * (ti.h / L1_TH) * (ti.w / BT_TW);
-                    if constexpr (sizeof(T) == 2) {
-                        static unsigned attr_done = 0;
-                        if (first_use_on_this_device(attr_done))
-                            DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bottleneck_l1_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, L1_LDS_BYTES));
-                        hipLaunchKernelGGL((bottleneck_l1_kernel<T>), dim3(std::min(tiles, cu_count())), dim3(L1_WAVES * 64), L1_LDS_BYTES, s, r);
-                        DF3D_LAUNCH_CHECK();
+                const BtLaunch b{(double)n * ti.h * ti.w, m1, n * (ti.h / BT_TH) * (ti.w / BT_TW), st.pool_only};
+                // the block's tensors and biases, as every ring and tail kernel takes them; each form adds its weight streams
+                BtRingArgs r{};
+                r.in = tptr(st.in);
+                r.in2 = tptr(st.in2);
+                r.add2 = tptr(st.add2);
+                r.out = st.pool_only ? nullptr : tptr(st.out);
+                r.pool = st.pool_only ? tptr(st.out) : tptr(st.pool_out);
+                r.pool_in = tptr(st.pool_in);
+                r.b1 = h->blob + st.conv.b_off;
+                r.b2 = h->blob + st.conv2b.b_off;
+                r.b3 = h->blob + st.conv3b.b_off;
+                r.bd = ds ? h->blob + st.conv4b.b_off : nullptr;
+                r.s1 = h->blob + st.conv.s_off;
+                r.t1 = h->blob + st.conv.t_off;
+                r.V = n;
+                r.H = ti.h;
+                r.W = ti.w;
+                // the split forms: conv1 writes t1 for every pixel of the level, the tail reads it (and the zero page: the 3x3's padding)
+                Conv1Args c{};
+                auto split = [&]() -> int {
+                    c.in = r.in;
+                    c.in2 = r.in2;
+                    c.H = ti.h;
+                    c.W = ti.w;
+                    c.t1 = tptr(st.t1);
+                    c.wstream = wstream(st.wstream_c1);
+                    c.b1 = r.b1;
+                    c.s1 = r.s1;
+                    c.t1c = r.t1;
+                    c.M = (long long)n * ti.h * ti.w;
+                    r.t1in = c.t1;
+                    r.zeros = wstream(h->zero_off);
+                    if (c.M % 128) {
+                        df3d::set_error("conv1 of the split bottleneck needs whole 128-pixel tiles (M = %lld)", c.M);
+                        return DF3D_EINVAL;
                     }
-                    break;
-                }
-                if (st.l2f) {
-                    if constexpr (sizeof(T) == 4) {
-                        const unsigned char* const sb = reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base();
-                        Conv1Args c;
-                        c.in = a.in;
-                        c.in2 = nullptr;
-                        c.H = ti.h;
-                        c.W = ti.w;
-                        c.t1 = tptr(st.t1);
-                        c.wstream = sb + st.wstream_c1;
-                        c.b1 = a.b1; c.s1 = a.s1; c.t1c = a.t1;
-                        c.M = (long long)n * ti.h * ti.w;
-                        {
-                            ScopedTimer tc(h, s, std::string("conv1_ring_f32_kernel<false, 128, 128, ") + tname + ">", 2.0 * px * cin * pl, px * 4.0 * (cin + pl), 0.0);
-                            static unsigned attr_c1 = 0;
-                            if (first_use_on_this_device(attr_c1))
-                                DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_ring_f32_kernel<false, 128, 128, T>), hipFuncAttributeMaxDynamicSharedMemorySize, C1_LDS_BYTES));
-                            const unsigned c1_grid = (unsigned)std::min<long long>(c.M / 128, 2LL * cu_count());
-                            hipLaunchKernelGGL((conv1_ring_f32_kernel<false, 128, 128, T>), dim3(c1_grid), dim3(256), C1_LDS_BYTES, s, c);
-                            DF3D_LAUNCH_CHECK();
-                        }
-                        BtRingArgs r{};
-                        r.in = a.in; r.out = a.out;
-                        r.t1in = c.t1;
-                        r.zeros = sb + h->zero_off;
-                        r.wstream = sb + st.wstream;
-                        r.b2 = a.b2; r.b3 = a.b3; r.bd = a.bd;
-                        r.V = n; r.H = ti.h; r.W = ti.w;
-                        if (std::is_same<T, float>::value && st.wstream_w2d >= 0) {   // option `wino`: layer2's 3x3 in the Winograd domain as well
-                            r.w2d = sb + st.wstream_w2d;
-                            ScopedTimer tw(h, s, "bottleneck_wino_f32_kernel<false, false, true>", 2.0 * px * (9.0 * pl * pl + (double)pl * 2 * pl + (double)cin * 2 * pl),
-                                           px * 4.0 * (cin + pl + 2.0 * pl), st.m1_elems * n * eb, 2.0 * px * (3.0 * pl * pl + (double)pl * 2 * pl + (double)cin * 2 * pl));
-                            if (int rc = launch_wino_f32<false, false, true>(r, n * (ti.h / BT_TH) * (ti.w / BT_TW), s)) return rc;
-                            break;
-                        }
-                        ScopedTimer tm(h, s, std::string("layer2_tail_f32_kernel<") + tname + ">", 2.0 * px * (9.0 * pl * pl + (double)pl * 2 * pl + (double)cin * 2 * pl), px * 4.0 * (cin + pl + 2.0 * pl), st.m1_elems * n * eb);
-                        static unsigned attr_t = 0;
-                        if (first_use_on_this_device(attr_t))
-                            DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(layer2_tail_f32_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, L2F_LDS_BYTES));
-                        hipLaunchKernelGGL(layer2_tail_f32_kernel<T>, dim3(n * (ti.h / BT_TH) * (ti.w / BT_TW)), dim3(256), L2F_LDS_BYTES, s, r);
-                        DF3D_LAUNCH_CHECK();
+                    return DF3D_OK;
+                };
+                switch (st.form) {
+                    case BT_REG: {
+                        BottleneckArgs a;
+                        a.in = r.in;
+                        a.in2 = r.in2;
+                        a.add2 = r.add2;
+                        a.out = r.out;
+                        a.pool = r.pool;
+                        a.w1 = wb + st.conv.w_off * eb;
+                        a.w2 = wb + st.conv2b.w_off * eb;
+                        a.w3 = wb + st.conv3b.w_off * eb;
+                        a.wd = ds ? wb + st.conv4b.w_off * eb : nullptr;
+                        a.b1 = r.b1; a.b2 = r.b2; a.b3 = r.b3; a.bd = r.bd; a.s1 = r.s1; a.t1 = r.t1;
+                        a.V = n; a.H = ti.h; a.W = ti.w;
+                        return launch_bottleneck<T>(h, a, cin, pl, b, s);
                     }
-                    break;
-                }
-                if (st.l1f) {
-                    if constexpr (sizeof(T) == 4) {
-                        const unsigned char* const sb = reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base();
-                        Conv1Args c;
-                        c.in = a.in;
-                        c.in2 = nullptr;
-                        c.H = ti.h;
-                        c.W = ti.w;
-                        c.t1 = tptr(st.t1);
-                        c.wstream = sb + st.wstream_c1;
-                        c.b1 = a.b1; c.s1 = a.s1; c.t1c = a.t1;
-                        c.M = (long long)n * ti.h * ti.w;
-                        {
-                            ScopedTimer tc(h, s, std::string("conv1_ring_f32_kernel<false, 64, 64, ") + tname + ">", 2.0 * px * cin * pl, px * 4.0 * (cin + pl), 0.0);
-                            static unsigned attr_c1 = 0;
-                            if (first_use_on_this_device(attr_c1))
-                                DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_ring_f32_kernel<false, 64, 64, T>), hipFuncAttributeMaxDynamicSharedMemorySize, C1_LDS_BYTES));
-                            const unsigned c1_grid = (unsigned)std::min<long long>(c.M / 128, 2LL * cu_count());
-                            hipLaunchKernelGGL((conv1_ring_f32_kernel<false, 64, 64, T>), dim3(c1_grid), dim3(256), C1_LDS_BYTES, s, c);
-                            DF3D_LAUNCH_CHECK();
+                    case BT_L1_LP:
+                        if constexpr (eb == 2) {
+                            BtL1Args a;
+                            a.in = r.in;
+                            a.out = r.out;
+                            a.pool = r.pool;
+                            a.wimage = wstream(st.wstream);
+                            a.b1 = r.b1; a.b2 = r.b2; a.b3 = r.b3; a.bd = r.bd; a.s1 = r.s1; a.t1 = r.t1;
+                            a.V = n; a.H = ti.h; a.W = ti.w;
+                            return launch_l1_lp<T>(h, a, b, s);
                         }
-                        BtRingArgs r{};
-                        r.in = a.in;
-                        r.out = st.pool_only ? nullptr : a.out;
-                        r.pool = st.pool_only ? a.out : a.pool;
-                        r.t1in = c.t1;
-                        r.zeros = sb + h->zero_off;
-                        r.wstream = sb + st.wstream;
-                        r.b2 = a.b2; r.b3 = a.b3; r.bd = a.bd;
-                        r.V = n; r.H = ti.h; r.W = ti.w;
-                        if (std::is_same<T, float>::value && st.wstream_w2d >= 0) {   // option `wino`: layer1's 3x3 in the Winograd domain (8 x 32 tiles, persistent)
-                            r.w2d = sb + st.wstream_w2d;
-                            ScopedTimer tw(h, s, "layer1_wino_f32_kernel", 2.0 * px * (9.0 * pl * pl + (double)pl * 2 * pl + (double)cin * 2 * pl),
-                                           px * 4.0 * (cin + pl + (st.pool_only ? 0.5 * pl : 2.0 * pl)), st.m1_elems * n * eb, 2.0 * px * (4.0 * pl * pl + (double)pl * 2 * pl + (double)cin * 2 * pl));
-                            static unsigned attr_w = 0;
-                            if (first_use_on_this_device(attr_w))
-                                DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(layer1_wino_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L1W_LDS_BYTES));
-                            const int tiles = n * (ti.h / BT_TH) * (ti.w / L1W_TW), cus = cu_count() & ~7;
-                            hipLaunchKernelGGL(layer1_wino_f32_kernel, dim3(tiles <= cus ? tiles : cus), dim3(256), L1W_LDS_BYTES, s, r);
-                            DF3D_LAUNCH_CHECK();
-                            break;
-                        }
-                        ScopedTimer tm(h, s, std::string("layer1_tail_f32_kernel<") + tname + ">", 2.0 * px * (9.0 * pl * pl + (double)pl * 2 * pl + (double)cin * 2 * pl), px * 4.0 * (cin + pl + (st.pool_only ? 0.5 * pl : 2.0 * pl)), st.m1_elems * n * eb);
-                        static unsigned attr_t = 0;
-                        if (first_use_on_this_device(attr_t))
-                            DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(layer1_tail_f32_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, L1F_LDS_BYTES));
-                        hipLaunchKernelGGL(layer1_tail_f32_kernel<T>, dim3(n * (ti.h / BT_TH) * (ti.w / BT_TW)), dim3(256), L1F_LDS_BYTES, s, r);
-                        DF3D_LAUNCH_CHECK();
-                    }
-                    break;
-                }
-                if (st.wstream >= 0) {
-                    BtRingArgs r;
-                    r.in = a.in; r.in2 = a.in2; r.add2 = a.add2; r.out = a.out; r.pool = a.pool;
-                    r.t1in = nullptr; r.zeros = nullptr;
-                    r.pool_in = st.pool_in >= 0 ? tptr(st.pool_in) : nullptr;
-                    r.wstream = reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base() + st.wstream;
-                    r.w2d = st.wstream_w2d >= 0 ? reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base() + st.wstream_w2d : nullptr;
-                    r.b1 = a.b1; r.b2 = a.b2; r.b3 = a.b3; r.bd = a.bd; r.s1 = a.s1; r.t1 = a.t1;
-                    r.V = n; r.H = ti.h; r.W = ti.w;
-                    if (ds) {   // 16-bit layer2
-                        ScopedTimer tm(h, s, std::string("bottleneck_ring_kernel<") + tname + ", false, 128, false, " + std::to_string(ring_mode(r, h->ring2)) + ">", 2.0 * px * ((double)cin * pl + 9.0 * pl * pl + 2.0 * pl * pl + 2.0 * cin * pl), px * eb * (cin + 2.0 * pl), st.m1_elems * n * eb);
-                        if constexpr (sizeof(T) == 2)
-                            if (int rc = launch_ring_lp<T, false, 128>(r, h->ring2, n * (ti.h / BT_TH) * (ti.w / BT_TW), BR_LDS_BYTES, s)) return rc;
                         break;
-                    }
-                    const bool split = eb == 4 && st.t1 >= 0;
-                    if (split) {   // fp32 split form: conv1 for every pixel of the level, then the tail on tiles
-                        if constexpr (sizeof(T) == 4) {
-                            Conv1Args c;
-                            c.in = a.in;
-                            c.in2 = a.in2;
-                            c.H = ti.h;
-                            c.W = ti.w;
-                            c.t1 = tptr(st.t1);
-                            c.wstream = reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base() + st.wstream_c1;
-                            c.b1 = a.b1; c.s1 = a.s1; c.t1c = a.t1;
-                            c.M = (long long)n * ti.h * ti.w;
-                            r.t1in = c.t1;
-                            r.zeros = reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base() + h->zero_off;
-                            const bool resident = std::is_same<T, float>::value && st.wstream_w2d >= 0 && !a.in2 && h->c1res;   // option `wino`: W1 resident in LDS
-                            ScopedTimer tc(h, s, resident ? std::string("conv1_res_f32_kernel") : std::string(a.in2 ? "conv1_ring_f32_kernel<true, 256, 128, " : "conv1_ring_f32_kernel<false, 256, 128, ") + tname + ">", 2.0 * px * cin * pl, px * 4.0 * (cin + pl), 0.0);   // (as rocprofv3 prints them)
-                            static unsigned attr_c1[2] = {0, 0};
-                            const void* const fn = a.in2 ? reinterpret_cast<const void*>(conv1_ring_f32_kernel<true, 256, 128, T>) : reinterpret_cast<const void*>(conv1_ring_f32_kernel<false, 256, 128, T>);
-                            if (first_use_on_this_device(attr_c1[a.in2 ? 1 : 0]))
-                                DF3D_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, C1_LDS_BYTES));
-                            if (c.M % 128) {
-                                df3d::set_error("conv1 of the split bottleneck needs whole 128-pixel tiles (M = %lld)", c.M);
-                                return DF3D_EINVAL;
+                    case BT_RING_LP:
+                        if constexpr (eb == 2) {
+                            r.wstream = wstream(st.wstream);
+                            r.w2d = st.wstream_w2 >= 0 ? wstream(st.wstream_w2) : nullptr;
+                            if (cin == 128) return launch_ring_lp<T, false, 128>(h, r, b, BR_LDS_BYTES, s);   // layer2
+                            return r.in2    ? launch_ring_lp<T, true, 256>(h, r, b, ring_lds_bytes(), s)
+                                   : r.add2 ? launch_ring_lp<T, false, 256, true>(h, r, b, ring_lds_bytes(), s)
+                                            : launch_ring_lp<T, false, 256>(h, r, b, ring_lds_bytes(), s);
+                        }
+                        break;
+                    case BT_RING_F32:
+                        if constexpr (eb == 4) {
+                            r.wstream = wstream(st.wstream);
+                            return r.in2    ? launch_ring_f32<T, true, false, false>(h, r, b, ring_lds_bytes(), s)
+                                   : r.add2 ? launch_ring_f32<T, false, true, false>(h, r, b, ring_lds_bytes(), s)
+                                            : launch_ring_f32<T, false, false, false>(h, r, b, ring_lds_bytes(), s);
+                        }
+                        break;
+                    case BT_SPLIT_F32:
+                        if constexpr (eb == 4) {
+                            if (int rc = split()) return rc;
+                            if (int rc = r.in2 ? launch_conv1_f32<T, true, 256, 128>(h, c, b, s) : launch_conv1_f32<T, false, 256, 128>(h, c, b, s)) return rc;
+                            r.wstream = wstream(st.wstream);
+                            return r.in2    ? launch_ring_f32<T, true, false, true>(h, r, b, ring_lds_bytes(), s)
+                                   : r.add2 ? launch_ring_f32<T, false, true, true>(h, r, b, ring_lds_bytes(), s)
+                                            : launch_ring_f32<T, false, false, true>(h, r, b, ring_lds_bytes(), s);
+                        }
+                        break;
+                    case BT_SPLIT_WINO:
+                        if constexpr (F32) {
+                            if (int rc = split()) return rc;
+                            int rc;
+                            if (!r.in2 && h->c1res) {
+                                c.wstream = wstream(st.wstream_wino + WN_STREAM_BYTES);   // W1, behind U's first part and W3'
+                                rc = launch_conv1_res_f32(h, c, b, s);
+                            } else {
+                                rc = r.in2 ? launch_conv1_f32<T, true, 256, 128>(h, c, b, s) : launch_conv1_f32<T, false, 256, 128>(h, c, b, s);
                             }
-                            const unsigned c1_grid = (unsigned)std::min<long long>(c.M / 128, 2LL * cu_count());   // persistent: two workgroups per CU
-                            if (resident) {
-                                if constexpr (std::is_same<T, float>::value) {
-                                    static unsigned attr_c1r = 0;
-                                    if (first_use_on_this_device(attr_c1r))
-                                        DF3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_res_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C1R_LDS_BYTES));
-                                    c.wstream = reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base() + st.wstream_w2d + WN_STREAM_BYTES;
-                                    hipLaunchKernelGGL(conv1_res_f32_kernel, dim3((unsigned)std::min<long long>(c.M / 128, (long long)(cu_count() & ~7))), dim3(256), C1R_LDS_BYTES, s, c);
-                                }
-                            } else if (a.in2)
-                                hipLaunchKernelGGL((conv1_ring_f32_kernel<true, 256, 128, T>), dim3(c1_grid), dim3(256), C1_LDS_BYTES, s, c);
-                            else
-                                hipLaunchKernelGGL((conv1_ring_f32_kernel<false, 256, 128, T>), dim3(c1_grid), dim3(256), C1_LDS_BYTES, s, c);
-                            DF3D_LAUNCH_CHECK();
+                            if (rc) return rc;
+                            r.w2d = wstream(st.wstream_wino);
+                            r.wstream = wstream(st.wstream_u2);
+                            return r.in2    ? launch_wino_f32<true, false, false>(h, r, b, s)
+                                   : r.add2 ? launch_wino_f32<false, true, false>(h, r, b, s)
+                                            : launch_wino_f32<false, false, false>(h, r, b, s);
                         }
-                    }
-                    if (split && std::is_same<T, float>::value && r.w2d) {   // option `wino`: the tail with its 3x3 in the Winograd domain
-                        const int blocks = n * (ti.h / BT_TH) * (ti.w / BT_TW);
-                        // FLOPs: the direct form's (what the block computes, in the reference's terms); the kernel EXECUTES 24/72 of the 3x3's
-                        ScopedTimer tm(h, s, std::string("bottleneck_wino_f32_kernel<") + (a.in2 ? "true, false, false>" : a.add2 ? "false, true, false>" : "false, false, false>"),
-                                       2.0 * px * (9.0 * pl * pl + 2.0 * pl * pl), px * eb * (cin + 2.0 * pl + pl), st.m1_elems * n * eb, 2.0 * px * (3.0 * pl * pl + 2.0 * pl * pl));
-                        const int rc = a.in2 ? launch_wino_f32<true, false>(r, blocks, s) : a.add2 ? launch_wino_f32<false, true>(r, blocks, s) : launch_wino_f32<false, false>(r, blocks, s);
-                        if (rc) return rc;
                         break;
-                    }
-                    const char* const flags2 = split ? (a.in2 ? "true, false, true, " : a.add2 ? "false, true, true, " : "false, false, true, ")
-                                                     : a.in2 ? "true, false, false, " : a.add2 ? "false, true, false, " : "false, false, false, ";
-                    ScopedTimer tm(h, s, eb == 2 ? std::string("bottleneck_ring_kernel<") + tname + (a.in2 ? ", true, 256, false, " : a.add2 ? ", false, 256, true, " : ", false, 256, false, ") + std::to_string(ring_mode(r, h->ring2)) + ">"
-                                                 : std::string("bottleneck_ring_f32_kernel<") + flags2 + tname + ">",   // as rocprofv3 prints them
-                                   2.0 * px * ((split ? 0.0 : (double)cin * pl) + 9.0 * pl * pl + 2.0 * pl * pl), px * eb * (cin + 2.0 * pl + (split ? pl : 0)), st.m1_elems * n * eb);
-                    const int blocks = n * (ti.h / BT_TH) * (ti.w / BT_TW);
-                    int lds_bytes = BR_LDS_BYTES;
-#ifdef DF3D_BT_TIMING
-                    if (const char* e = getenv("BR_LDS")) lds_bytes = atoi(e);   // development: force one workgroup per CU (> 80 KB)
-#endif
-#ifdef BR_FORCE_LDS
-                    lds_bytes = BR_FORCE_LDS;   // development builds: one workgroup per CU (> 80 KB)
-#endif
-                    int rc;
-                    if constexpr (sizeof(T) == 2)
-                        rc = a.in2 ? launch_ring_lp<T, true, 256>(r, h->ring2, blocks, lds_bytes, s) : a.add2 ? launch_ring_lp<T, false, 256, true>(r, h->ring2, blocks, lds_bytes, s)
-                                                                                           : launch_ring_lp<T, false, 256>(r, h->ring2, blocks, lds_bytes, s);
-                    else
-                        rc = split ? (a.in2 ? launch_ring_f32<T, true, false, true>(r, blocks, lds_bytes, s)
-                                      : a.add2 ? launch_ring_f32<T, false, true, true>(r, blocks, lds_bytes, s) : launch_ring_f32<T, false, false, true>(r, blocks, lds_bytes, s))
-                             : a.in2 ? launch_ring_f32<T, true>(r, blocks, lds_bytes, s)
-                             : a.add2 ? launch_ring_f32<T, false, true>(r, blocks, lds_bytes, s)
-                                      : launch_ring_f32<T, false>(r, blocks, lds_bytes, s);
-                    if (rc) return rc;
-                    break;
+                    case BT_L1F:
+                        if constexpr (eb == 4) {
+                            if (int rc = split()) return rc;
+                            if (int rc = launch_conv1_f32<T, false, 64, 64>(h, c, b, s)) return rc;
+                            r.wstream = wstream(st.wstream);
+                            return launch_layer1_tail_f32<T>(h, r, b, s);
+                        }
+                        break;
+                    case BT_L1F_WINO:
+                        if constexpr (F32) {
+                            if (int rc = split()) return rc;
+                            if (int rc = launch_conv1_f32<T, false, 64, 64>(h, c, b, s)) return rc;
+                            r.w2d = wstream(st.wstream_wino);
+                            return launch_layer1_wino_f32(h, r, b, s);
+                        }
+                        break;
+                    case BT_L2F:
+                        if constexpr (eb == 4) {
+                            if (int rc = split()) return rc;
+                            if (int rc = launch_conv1_f32<T, false, 128, 128>(h, c, b, s)) return rc;
+                            r.wstream = wstream(st.wstream);
+                            return launch_layer2_tail_f32<T>(h, r, b, s);
+                        }
+                        break;
+                    case BT_L2F_WINO:
+                        if constexpr (F32) {
+                            if (int rc = split()) return rc;
+                            if (int rc = launch_conv1_f32<T, false, 128, 128>(h, c, b, s)) return rc;
+                            r.w2d = wstream(st.wstream_wino);
+                            r.wstream = wstream(st.wstream_u2);
+                            return launch_wino_f32<false, false, true>(h, r, b, s);
+                        }
+                        break;
                 }
-                ScopedTimer tm(h, s, std::string("bottleneck_kernel<") + tname + ", " + std::to_string(cin) + ", " + std::to_string(pl) + ", " + (ds ? "true" : "false") + ", " + (a.in2 ? "true" : "false") + ", " + (a.add2 ? "true" : "false") + ">",
-                               2.0 * px * ((double)cin * pl + 9.0 * pl * pl + 2.0 * pl * pl + (ds ? 2.0 * cin * pl : 0.0)), px * eb * (cin + 2.0 * pl), st.m1_elems * n * eb);
-                const int blocks = n * (ti.h / BT_TH) * (ti.w / BT_TW);
-                if (int rc = launch_bottleneck<T>(a, cin, pl, blocks, s)) return rc;
-                break;
+                df3d::set_error("bottleneck form %d has no kernels for this element type", (int)st.form);
+                return DF3D_EINVAL;
             }
             case ST_HEAD: {
                 const TensorDesc& ti = h->tensors[st.in];
@@ -1138,50 +1138,31 @@ int run_steps(df3d_hg* h, const float* images_all, int n_all, int upto, float* h
                 a.wsc_ = st.last ? nullptr : wb + st.conv4b.w_off * eb;
                 a.bfc_ = st.last ? nullptr : h->blob + st.conv3b.b_off;
                 a.bsc_ = st.last ? nullptr : h->blob + st.conv4b.b_off;
-                a.fcstream = st.wstream >= 0 ? reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base() + st.wstream : nullptr;
-                a.fc2stream = st.wstream2 >= 0 && ((long long)n * ti.h * ti.w) % 128 == 0 ? reinterpret_cast<const unsigned char*>(h->lowp) + h->stream_base() + st.wstream2 : nullptr;
+                a.fcstream = st.wstream >= 0 ? wstream(st.wstream) : nullptr;
+                a.fc2stream = st.wstream2 >= 0 && ((long long)n * ti.h * ti.w) % 128 == 0 ? wstream(st.wstream2) : nullptr;
                 a.M = (long long)n * ti.h * ti.w;
                 a.HW = ti.h * ti.w;
-                const void* fn = st.last ? reinterpret_cast<const void*>(head_kernel<T, true>) : reinterpret_cast<const void*>(head_kernel<T, false>);
-                using HeadLast = HeadCfg<T, true>;
-                using HeadMid = HeadCfg<T, false>;
-                const int head_lds = st.last ? HeadLast::LDS_BYTES : HeadMid::LDS_BYTES;
-                static unsigned attr_done[2] = {0, 0};
-                if (first_use_on_this_device(attr_done[st.last]))
-                    DF3D_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, head_lds));
                 const double mm = (double)a.M;
                 const double fl = 2.0 * mm * (256.0 * 256 + 256.0 * 19 + (st.last ? 0.0 : 256.0 * 256 + 19.0 * 256));
-                ScopedTimer tm(h, s, std::string("head_kernel<") + tname + ", " + (st.last ? "true" : "false") + ">", fl,
-                               mm * eb * (st.last ? 256.0 : 768.0) + (st.last ? mm * 19 * 4 : 0.0), st.m1_elems * n * eb);
-                const unsigned blocks = (unsigned)((a.M + 127) / 128);
-                if (st.last)
-                    hipLaunchKernelGGL((head_kernel<T, true>), dim3(blocks), dim3(256), head_lds, s, a);
-                else
-                    hipLaunchKernelGGL((head_kernel<T, false>), dim3(blocks), dim3(256), head_lds, s, a);
-                DF3D_LAUNCH_CHECK();
-                break;
+                const Work w{fl, mm * eb * (st.last ? 256.0 : 768.0) + (st.last ? mm * 19 * 4 : 0.0), m1};
+                return st.last ? launch_head<T, true>(h, a, w, s) : launch_head<T, false>(h, a, w, s);
             }
             case ST_POOL: {
                 const TensorDesc& to = h->tensors[st.out];
                 const int chunks = to.pitch * eb / 16;
                 const long long total = (long long)n * to.h * to.w * chunks;
-                ScopedTimer tm(h, s, std::string("pool2_kernel<") + TypeName<StorageT<T>>::value + ">", 0.0, (double)total * 16 * 5, st.m1_elems * n * eb);
-                hipLaunchKernelGGL((pool2_kernel<StorageT<T>>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                                   reinterpret_cast<const u32x4*>(tptr(st.in)), reinterpret_cast<u32x4*>(tptr(st.out)),
-                                   total, to.h, to.w, chunks);
-                DF3D_LAUNCH_CHECK();
-                break;
+                return launch_kernel<pool2_kernel<StorageT<T>>>(h, kname("pool2_kernel", TypeName<StorageT<T>>::value), Work{0.0, (double)total * 16 * 5, m1},
+                                                                dim3((unsigned)((total + 255) / 256)), 256, 0, s, reinterpret_cast<const u32x4*>(tptr(st.in)),
+                                                                reinterpret_cast<u32x4*>(tptr(st.out)), total, to.h, to.w, chunks);
             }
             case ST_UPADD: {
                 const TensorDesc& to = h->tensors[st.out];
                 const int chunks = to.pitch * eb / 16;
                 const long long total = (long long)n * to.h * to.w * chunks;
-                ScopedTimer tm(h, s, std::string("upadd_kernel<") + TypeName<StorageT<T>>::value + ">", 0.0, (double)total * 16 * 2.25, st.m1_elems * n * eb);
-                hipLaunchKernelGGL((upadd_kernel<StorageT<T>>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                                   reinterpret_cast<const u32x4*>(tptr(st.in)), reinterpret_cast<const u32x4*>(tptr(st.res)),
-                                   reinterpret_cast<u32x4*>(tptr(st.out)), total, to.h, to.w, chunks);
-                DF3D_LAUNCH_CHECK();
-                break;
+                return launch_kernel<upadd_kernel<StorageT<T>>>(h, kname("upadd_kernel", TypeName<StorageT<T>>::value), Work{0.0, (double)total * 16 * 2.25, m1},
+                                                                dim3((unsigned)((total + 255) / 256)), 256, 0, s, reinterpret_cast<const u32x4*>(tptr(st.in)),
+                                                                reinterpret_cast<const u32x4*>(tptr(st.res)), reinterpret_cast<u32x4*>(tptr(st.out)), total,
+                                                                to.h, to.w, chunks);
             }
         }
         return DF3D_OK;
@@ -1388,6 +1369,80 @@ __global__ __launch_bounds__(256) void absmax_bits_kernel(const float* __restric
     for (int off = 32; off >= 1; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
     if ((threadIdx.x & 63) == 0) atomicMax(out, m);
 }
+
+// The weight streams behind stream_base(): what each step's kernels read besides the blob.  The 16-bit forms pack from the 16-bit copy of
+// the blob at the start of the buffer, the others from `w` (the float32 blob; f32s: its pre-split copy).
+int pack_streams(df3d_hg* h, void* lowp_dev, const float* w, hipStream_t s) {
+    const unsigned short* const lp = reinterpret_cast<const unsigned short*>(lowp_dev);
+    unsigned char* const base = reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base();
+    for (const Step& st : h->steps) {
+        if (st.kind == ST_HEAD && st.wstream >= 0) {
+            if (!h->lp()) {
+                hipLaunchKernelGGL(bt_fc_pack_f32_kernel, dim3((HD_FC_STAGES_F32 * 512 + 255) / 256), dim3(256), 0, s, w + st.conv.w_off, base + st.wstream);
+                continue;
+            }
+            hipLaunchKernelGGL(bt_fc_pack_kernel, dim3((HD_FC_STAGES * 512 + 255) / 256), dim3(256), 0, s, lp + st.conv.w_off, base + st.wstream);
+            if (st.wstream2 >= 0)
+                hipLaunchKernelGGL(bt_fc2_pack_kernel, dim3((HD_FC2_STAGES * 512 + 255) / 256), dim3(256), 0, s, lp + st.conv3b.w_off, lp + st.conv4b.w_off,
+                                   base + st.wstream2);
+            continue;
+        }
+        if (st.kind != ST_BOTTLENECK) continue;
+        const long long w1 = st.conv.w_off, w2 = st.conv2b.w_off, w3 = st.conv3b.w_off, wd = st.conv4b.w_off;
+        switch (st.form) {
+            case BT_REG: break;
+            case BT_L1_LP:
+                hipLaunchKernelGGL(bt_l1_pack_kernel, dim3((L1_W_BYTES / 16 + 255) / 256), dim3(256), 0, s, lp + w1, lp + w2, lp + w3, lp + wd, base + st.wstream);
+                break;
+            case BT_RING_LP: {
+                if (st.wstream_w2 >= 0)
+                    hipLaunchKernelGGL(bt_w2d_pack_kernel, dim3((BR_W2D_GROUPS * 256 + 255) / 256), dim3(256), 0, s, lp + w2, base + st.wstream_w2);
+                const bool ds = st.res < 0;   // layer2: 128 -> 128 -> 128 -> 256 with the skip convolution
+                hipLaunchKernelGGL(bt_ring_pack_kernel, dim3((br_nstage(st.conv.cin, ds) * 512 + 255) / 256), dim3(256), 0, s, lp + w1, lp + w2, lp + w3,
+                                   ds ? lp + wd : nullptr, st.conv.cin, base + st.wstream);
+                break;
+            }
+            case BT_RING_F32:
+            case BT_SPLIT_F32:
+                hipLaunchKernelGGL(bt_ring_pack_f32_kernel, dim3((BRF_NSTAGE * 512 + 255) / 256), dim3(256), 0, s, w + w1, w + w2, w + w3, base + st.wstream);
+                if (st.form == BT_SPLIT_F32)
+                    hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3((C1_NSTAGE * 512 + 255) / 256), dim3(256), 0, s, w + w1, base + st.wstream_c1);
+                break;
+            case BT_SPLIT_WINO:
+                // No launch of a Winograd form reads direct-form stage images: U's second part has their slot (wstream_u2).
+                hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3((C1_NSTAGE * 512 + 255) / 256), dim3(256), 0, s, w + w1, base + st.wstream_c1);
+                hipLaunchKernelGGL(bt_wino_pack_kernel, dim3(128 * 128 / 256), dim3(256), 0, s, w + w2, reinterpret_cast<float*>(base + st.wstream_wino),
+                                   reinterpret_cast<float*>(base + st.wstream_u2));
+                hipLaunchKernelGGL(bt_wino_pack_w3_kernel, dim3(BRF_W3_STAGES * 512 / 256), dim3(256), 0, s, w + w3, base + st.wstream_wino + WN_U_BYTES);
+                hipLaunchKernelGGL(c1r_pack_kernel, dim3(C1_NSTAGE * 512 / 256), dim3(256), 0, s, w + w1, base + st.wstream_wino + WN_STREAM_BYTES);
+                break;
+            case BT_L1F:
+                hipLaunchKernelGGL(bt_l1f_pack_kernel, dim3((L1F_NSTAGE * 512 + 255) / 256), dim3(256), 0, s, w + w2, w + w3, w + wd, base + st.wstream);
+                hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3(((64 / 16) * 512 + 255) / 256), dim3(256), 0, s, w + w1, base + st.wstream_c1, 64, 64);
+                break;
+            case BT_L1F_WINO:
+                hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3(((64 / 16) * 512 + 255) / 256), dim3(256), 0, s, w + w1, base + st.wstream_c1, 64, 64);
+                hipLaunchKernelGGL(l1_wino_pack_u_kernel, dim3(64 * 64 / 256), dim3(256), 0, s, w + w2, reinterpret_cast<float*>(base + st.wstream_wino));
+                hipLaunchKernelGGL(l1_wino_pack_w_kernel, dim3(4 * 512 / 256), dim3(256), 0, s, w + w3, base + st.wstream_wino + L1W_U_BYTES);
+                hipLaunchKernelGGL(l1_wino_pack_w_kernel, dim3(4 * 512 / 256), dim3(256), 0, s, w + wd, base + st.wstream_wino + L1W_U_BYTES + L1W_W_BYTES);
+                break;
+            case BT_L2F:
+                hipLaunchKernelGGL(bt_l2f_pack_kernel, dim3((L2F_NSTAGE * 512 + 255) / 256), dim3(256), 0, s, w + w2, w + w3, w + wd, base + st.wstream);
+                hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3(((128 / 16) * 512 + 255) / 256), dim3(256), 0, s, w + w1, base + st.wstream_c1, 128, 128);
+                break;
+            case BT_L2F_WINO:   // (as BT_SPLIT_WINO: U's second part in wstream_u2)
+                hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3(((128 / 16) * 512 + 255) / 256), dim3(256), 0, s, w + w1, base + st.wstream_c1, 128, 128);
+                hipLaunchKernelGGL(bt_wino_pack_kernel, dim3(128 * 128 / 256), dim3(256), 0, s, w + w2, reinterpret_cast<float*>(base + st.wstream_wino),
+                                   reinterpret_cast<float*>(base + st.wstream_u2));
+                hipLaunchKernelGGL(bt_wino_pack_w3_kernel, dim3(BRF_W3_STAGES * 512 / 256), dim3(256), 0, s, w + w3, base + st.wstream_wino + WN_U_BYTES);
+                hipLaunchKernelGGL(bt_wino_pack_w3_kernel, dim3(BRF_W3_STAGES * 512 / 256), dim3(256), 0, s, w + wd, base + st.wstream_wino + WN_U_BYTES + WN_W3_BYTES);
+                break;
+        }
+    }
+    if (h->uses_zero_page) DF3D_HIP(hipMemsetAsync(base + h->zero_off, 0, 256, s));
+    DF3D_LAUNCH_CHECK();
+    return DF3D_OK;
+}
 }  // namespace
 
 int df3d_hg_set_weights(df3d_hg* h, const float* blob_dev, void* lowp_dev, void* stream) {
@@ -1428,37 +1483,8 @@ int df3d_hg_set_weights(df3d_hg* h, const float* blob_dev, void* lowp_dev, void*
             hipLaunchKernelGGL((stem_relayout_kernel<__hip_bfloat16>), dim3((64 * 184 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
                                blob_dev + h->steps[0].conv.w_off, reinterpret_cast<unsigned short*>(lowp_dev) + h->steps[0].conv.w_off);
         }
-        // weight streams of the ring bottlenecks: stage-by-stage LDS images (hg_bt_ring.h), from the 16-bit copy (byte movers:
-        // the same kernels serve both formats)
-        for (const Step& st : h->steps) {
-            if (st.kind == ST_HEAD && st.wstream >= 0) {
-                hipLaunchKernelGGL(bt_fc_pack_kernel, dim3((HD_FC_STAGES * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
-                                   reinterpret_cast<const unsigned short*>(lowp_dev) + st.conv.w_off,
-                                   reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
-                if (st.wstream2 >= 0)
-                    hipLaunchKernelGGL(bt_fc2_pack_kernel, dim3((HD_FC2_STAGES * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
-                                       reinterpret_cast<const unsigned short*>(lowp_dev) + st.conv3b.w_off,
-                                       reinterpret_cast<const unsigned short*>(lowp_dev) + st.conv4b.w_off,
-                                       reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream2);
-                continue;
-            }
-            if (st.kind != ST_BOTTLENECK || st.wstream < 0) continue;
-            const unsigned short* lp = reinterpret_cast<const unsigned short*>(lowp_dev);
-            if (st.l1) {
-                hipLaunchKernelGGL(bt_l1_pack_kernel, dim3((L1_W_BYTES / 16 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
-                                   lp + st.conv.w_off, lp + st.conv2b.w_off, lp + st.conv3b.w_off, lp + st.conv4b.w_off,
-                                   reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
-                continue;
-            }
-            if (st.wstream_w2d >= 0)
-                hipLaunchKernelGGL(bt_w2d_pack_kernel, dim3((BR_W2D_GROUPS * 256 + 255) / 256), dim3(256), 0, df3d::as_stream(stream), lp + st.conv2b.w_off,
-                                   reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_w2d);
-            const bool dsb = st.conv.cin != 2 * st.conv.cout;   // layer2: 128 -> 128 -> 128 -> 256 with the skip convolution
-            hipLaunchKernelGGL(bt_ring_pack_kernel, dim3((br_nstage(st.conv.cin, dsb) * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
-                               lp + st.conv.w_off, lp + st.conv2b.w_off, lp + st.conv3b.w_off, dsb ? lp + st.conv4b.w_off : nullptr, st.conv.cin,
-                               reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
-        }
-        DF3D_LAUNCH_CHECK();
+        // (the packers of the 16-bit streams are byte movers: the same kernels serve both formats)
+        if (int rc = pack_streams(h, lowp_dev, nullptr, df3d::as_stream(stream))) return rc;
         h->lowp = lowp_dev;
     } else if (h->dtype == DF3D_DTYPE_F32S && lowp_dev == nullptr) {
         df3d::set_error("an f32s engine needs a df3d_hg_lowp_bytes() device buffer (the pre-split copy of the weights)");
@@ -1482,64 +1508,7 @@ int df3d_hg_set_weights(df3d_hg* h, const float* blob_dev, void* lowp_dev, void*
                                reinterpret_cast<unsigned short*>(reinterpret_cast<float*>(lowp_dev) + h->steps[0].conv.w_off));
             blob_dev = reinterpret_cast<const float*>(lowp_dev);   // (restored below: h->blob stays the caller's float32 blob)
         }
-        for (const Step& st : h->steps) {
-            if (st.kind == ST_HEAD && st.wstream >= 0)
-                hipLaunchKernelGGL(bt_fc_pack_f32_kernel, dim3((HD_FC_STAGES_F32 * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
-                                   blob_dev + st.conv.w_off, reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
-            if (st.kind != ST_BOTTLENECK || st.wstream < 0) continue;
-            // Option `wino` (st.wstream_w2d >= 0, float32 engine): the direct-form stage images at st.wstream are dead -- every launch of such a
-            // block takes bottleneck_wino_f32_kernel (run_steps: a split step with r.w2d set; ST_BOTTLENECK steps exist only at levels of whole
-            // 8 x 16 tiles, fused and unfused plans, every fuse_upadd mode), conv1 reads st.wstream_c1 (c1res = 0, the UP form) or the W1 images
-            // behind U (c1res = 1), and no other kernel reads st.wstream.  So the images are not packed, and U's second part (passes 64 .. 95 of
-            // bt_wino_pack_kernel, 512 KiB) takes their place: the buffer keeps its size.
-            const bool wino_f32 = st.wstream_w2d >= 0 && h->dtype == DF3D_DTYPE_F32;
-            if (st.l2f) {
-                if (!wino_f32)
-                    hipLaunchKernelGGL(bt_l2f_pack_kernel, dim3((L2F_NSTAGE * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off,
-                                       blob_dev + st.conv3b.w_off, blob_dev + st.conv4b.w_off, reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
-                hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3(((128 / 16) * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv.w_off,
-                                   reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_c1, 128, 128);
-                if (wino_f32) {
-                    unsigned char* const ws = reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_w2d;
-                    hipLaunchKernelGGL(bt_wino_pack_kernel, dim3(128 * 128 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off, reinterpret_cast<float*>(ws),
-                                       reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream));
-                    hipLaunchKernelGGL(bt_wino_pack_w3_kernel, dim3(BRF_W3_STAGES * 512 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv3b.w_off, ws + WN_U_BYTES);
-                    hipLaunchKernelGGL(bt_wino_pack_w3_kernel, dim3(BRF_W3_STAGES * 512 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv4b.w_off, ws + WN_U_BYTES + WN_W3_BYTES);
-                }
-                continue;
-            }
-            if (st.l1f) {
-                hipLaunchKernelGGL(bt_l1f_pack_kernel, dim3((L1F_NSTAGE * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off,
-                                   blob_dev + st.conv3b.w_off, blob_dev + st.conv4b.w_off, reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
-                hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3(((64 / 16) * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv.w_off,
-                                   reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_c1, 64, 64);
-                if (st.wstream_w2d >= 0 && h->dtype == DF3D_DTYPE_F32) {
-                    unsigned char* const ws = reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_w2d;
-                    hipLaunchKernelGGL(l1_wino_pack_u_kernel, dim3(64 * 64 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off, reinterpret_cast<float*>(ws));
-                    hipLaunchKernelGGL(l1_wino_pack_w_kernel, dim3(4 * 512 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv3b.w_off, ws + L1W_U_BYTES);
-                    hipLaunchKernelGGL(l1_wino_pack_w_kernel, dim3(4 * 512 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv4b.w_off, ws + L1W_U_BYTES + L1W_W_BYTES);
-                }
-                continue;
-            }
-            if (!wino_f32)
-                hipLaunchKernelGGL(bt_ring_pack_f32_kernel, dim3((BRF_NSTAGE * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
-                                   blob_dev + st.conv.w_off, blob_dev + st.conv2b.w_off, blob_dev + st.conv3b.w_off,
-                                   reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream);
-            if (st.wstream_c1 >= 0)
-                hipLaunchKernelGGL(bt_c1_pack_f32_kernel, dim3((C1_NSTAGE * 512 + 255) / 256), dim3(256), 0, df3d::as_stream(stream),
-                                   blob_dev + st.conv.w_off, reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_c1);
-            if (wino_f32)
-            {
-                unsigned char* const ws = reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream_w2d;
-                hipLaunchKernelGGL(bt_wino_pack_kernel, dim3(128 * 128 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv2b.w_off, reinterpret_cast<float*>(ws),
-                                   reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + st.wstream));
-                hipLaunchKernelGGL(bt_wino_pack_w3_kernel, dim3(BRF_W3_STAGES * 512 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv3b.w_off, ws + WN_U_BYTES);
-                hipLaunchKernelGGL(c1r_pack_kernel, dim3(C1_NSTAGE * 512 / 256), dim3(256), 0, df3d::as_stream(stream), blob_dev + st.conv.w_off, ws + WN_STREAM_BYTES);
-            }
-        }
-        if (h->uses_zero_page)
-            DF3D_HIP(hipMemsetAsync(reinterpret_cast<unsigned char*>(lowp_dev) + h->stream_base() + h->zero_off, 0, 256, df3d::as_stream(stream)));
-        DF3D_LAUNCH_CHECK();
+        if (int rc = pack_streams(h, lowp_dev, blob_dev, df3d::as_stream(stream))) return rc;
         h->lowp = lowp_dev;
     }
     h->blob = blob_caller;
