@@ -83,6 +83,7 @@ PROTOTYPES = {
         [POINTER(c_int), POINTER(c_int), POINTER(c_double), c_double, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "df3d_reproj_errors": (c_int, [POINTER(c_double), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_column_median": (c_int, [c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_void_p]),
     "df3d_procrustes_work_doubles": (c_longlong, [c_longlong]),
     "df3d_procrustes": (c_int, [c_void_p, c_longlong, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_longlong, c_void_p]),

@@ -43,9 +43,14 @@ def parse_cli_args(argv=None):
     p.add_argument("--auto-correct", dest="auto_correct", action="store_true",
                    help="Correct the 2-D detections with the pictorial-structures model (bone-length prior, multi-view reprojection "
                         "consistency over the heat-map peaks) before triangulating; the arg-max detections are kept as points2d_argmax")
+    p.add_argument("--correct-only-flagged", dest="correct_only_flagged", action="store_true",
+                   help="With --auto-correct: keep the correction only on the joints whose reprojection error exceeds the per-joint "
+                        "threshold (40 px) on the arg-max detections; every other detection stays the arg-max one")
     args = p.parse_args(argv)
     if args.auto_correct and args.skip_estimation:
         p.error("--auto-correct needs the heat-map peaks of this run's pose estimation: it cannot be combined with --skip-pose-estimation")
+    if args.correct_only_flagged and not args.auto_correct:
+        p.error("--correct-only-flagged restricts --auto-correct: it needs --auto-correct")
     inp = Path(args.input_folder).expanduser().resolve()
     args.output_folder = str(inp.with_name(inp.stem + "_df3d")) if args.output_folder is None else str(Path(args.output_folder).expanduser().resolve())
     args.input_folder = str(inp)
@@ -82,7 +87,9 @@ def run(args):
         core.pose2d_estimation(args.batch_size, args.pin_memory_disabled, num_peaks=PICTORIAL_DEFAULTS["num_peaks"] if auto else 0)
         core.save()
     core.calibrate_calc(0, core.max_img_id)
-    if auto:
+    if auto and getattr(args, "correct_only_flagged", False):
+        core.auto_correct(flagged_only=True)
+    elif auto:
         core.auto_correct()
     core.save()
     if args.video_2d or args.video_3d:

@@ -44,6 +44,10 @@ PICTORIAL_DEFAULTS = {
     "w_bone": 1.0,
 }
 
+# ---- suspect detections: joint j of a frame is flagged when its largest per-camera reprojection error
+# exceeds REPROJ_THR[j] pixels.  The reference's `config["reproj_thr"]` (df3d/config.py:41): 40 for each of the 38 joints.
+REPROJ_THR = np.full(38, 40.0, dtype=np.float64)
+
 
 def bone_tree():
     """(parent [38] int32, bone [38, 2] float64 (mean, deviation)) from TRACKED: a coxa-femur, femur-tibia, tibia-tarsus or

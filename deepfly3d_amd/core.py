@@ -7,8 +7,9 @@ MI355X back-end.  Same constructor, methods, attributes, exceptions and result-p
     core.calibrate_calc(min_img_id, max_img_id)                        # reference :229-250
     core.save()
 
-GUI-only methods (interactive correction, error navigation, plotting) are out of scope (SURVEY.md sec. 2 row 1);
-the correction store and `corrected_points2d*` are kept so that stored corrections reach the triangulation.
+GUI-only methods (interactive correction, plotting) are out of scope; the correction store and
+`corrected_points2d*` are kept so that stored corrections reach the triangulation.  The error navigation (`next_error`,
+`prev_error`, `next_error_in_range`, `joint_has_error`, `get_joint_reprojection_error`) runs on the device.
 """
 import glob
 import os
@@ -206,12 +207,14 @@ class Core:
         self.points2d, self.conf = points2d.cpu().numpy(), conf.cpu().numpy()
         self.peaks = tuple(p.cpu().numpy() for p in peaks) if peaks else None
 
-    def auto_correct(self, **params):
+    def auto_correct(self, flagged_only=False, **params):
         """Pictorial-structures correction of the 2-D detections on the device: replaces `points2d` and the
         camera network's points by the corrected detections and keeps the arg-max ones in `points2d_argmax`.  Needs calibrated
         cameras (calibrate_calc) and the peaks of pose2d_estimation(num_peaks=K).  `params` override config.PICTORIAL_DEFAULTS
-        (num_proposals, tau, w_reproj, w_heatmap, w_bone; num_peaks is fixed by the peaks kept).  Multi-GPU: every rank calls
-        this, rank 0 solves, a failure there is raised on every rank (`distributed.agree`)."""
+        (num_proposals, tau, w_reproj, w_heatmap, w_bone; num_peaks is fixed by the peaks kept).  `flagged_only=True` keeps the
+        correction only on the joints that the reprojection-error test (DESIGN.md section 10) flags on the arg-max detections;
+        every other detection stays the arg-max one, bit for bit.  Multi-GPU: every rank calls this, rank 0 solves, a failure
+        there is raised on every rank (`distributed.agree`)."""
         from . import distributed as dd
         from .config import PICTORIAL_DEFAULTS
 
@@ -225,13 +228,13 @@ class Core:
                     raise RuntimeError("auto_correct needs calibrated cameras: run calibrate_calc() first")
                 if self.peaks is None or self.points2d is None or self.peaks[0].shape[1] != self.points2d.shape[1]:
                     raise RuntimeError("auto_correct needs the heat-map peaks of this recording: run pose2d_estimation(num_peaks=K) first")
-                self._auto_correct_primary(params)
+                self._auto_correct_primary(params, flagged_only)
             except Exception as e:  # noqa: BLE001  (re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "auto_correct")
         self._corrected = True
 
-    def _auto_correct_primary(self, params):
+    def _auto_correct_primary(self, params, flagged_only=False):
         from .config import PICTORIAL_DEFAULTS
 
         p = {**PICTORIAL_DEFAULTS, **params}
@@ -245,11 +248,92 @@ class Core:
         P = np.stack([c.P for c in self.camNet.cam_list])
         res = ops.pictorial_correct(P, self.camera_ordering, am, count, pts, vals, self.image_shape, num_proposals=p["num_proposals"], tau=p["tau"],
                                     w_reproj=p["w_reproj"], w_heatmap=p["w_heatmap"], w_bone=p["w_bone"], chunk_frames=p.get("chunk_frames", 4096))
+        corrected, flagged = res.points2d, None
+        if flagged_only:
+            # the error test on the arg-max detections, at the point the correction starts from (its proposal 0); pixels = normalised
+            # * (H, W), the product df3d_triangulate_scaled forms
+            scale = torch.tensor([float(v) for v in self.image_shape[::-1]], dtype=torch.float64, device=dev)
+            _, _, mask = ops.reprojection_errors(P, (am * scale).contiguous(), X=ops.arg_max_points3d(P, am, self.image_shape))
+            bit = torch.ones((), dtype=torch.int64, device=dev) << torch.arange(am.shape[2], dtype=torch.int64, device=dev)
+            flagged = (mask[:, None] & bit) != 0                                   # [T, 38]
+            corrected = torch.where(flagged[None, :, :, None], res.points2d, am)
         self.points2d_argmax = np.array(argmax2d, dtype=np.float64, copy=True)
-        self.points2d = res.points2d.cpu().numpy()
+        self.points2d = corrected.cpu().numpy()
         np.copyto(self.camNet.points2d, self.points2d * self.image_shape[::-1])
         changed = int((self.points2d != self.points2d_argmax).any(axis=-1).sum())
-        print(f"Auto-correction changed {changed} detections; mean minimum energy per frame {float(res.energy.mean()) if res.energy.numel() else 0.0:.4f}")
+        energy = f"mean minimum energy per frame {float(res.energy.mean()) if res.energy.numel() else 0.0:.4f}"
+        if flagged is None:
+            print(f"Auto-correction changed {changed} detections; {energy}")
+        else:
+            print(f"Auto-correction changed {changed} detections on {int(flagged.sum())} flagged joints; {energy}")
+
+    # -- suspect detections (reference df3d/core.py:205-227, 481-507) -----------------------------------------
+    # Rank-0 methods on the camera network's detections (pixels, with auto-corrections and the manual corrections that
+    # corrected_points2d_matrix() wrote into it), triangulated as save() triangulates them.  No cache: every call computes what it
+    # needs, so an edit of the points never leaves stale flags.
+    _ERROR_CHUNK_FIRST, _ERROR_CHUNK_LAST = 1024, 65536
+
+    def _reprojection_on(self, ids):
+        """(err [7, n, 38], jmax [n, 38], mask [n]) device tensors of the frames `ids` (host-gathered: a chunk, not the recording,
+        travels to the device)."""
+        from . import distributed as dd
+
+        if dd.current()[0] != 0:
+            raise RuntimeError("the reprojection-error queries are rank-0 methods: the camera network lives on rank 0")
+        if self.camNet is None or not self.camNet.has_calibration():
+            raise RuntimeError("the reprojection-error queries need calibrated cameras: run calibrate_calc() first")
+        px = self.camNet.points2d
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= px.shape[1]):
+            raise IndexError(f"image ids must lie in [0, {px.shape[1]})")
+        _native.require_gpu()
+        dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
+        P = np.stack([c.P for c in self.camNet.cam_list])
+        return ops.reprojection_errors(P, torch.from_numpy(np.ascontiguousarray(px[:, ids])).to(dev))
+
+    def reprojection_errors(self, frames=None):
+        """Per-camera reprojection errors [7, nf, 38] in pixels of the frames `frames` (default all), as a numpy array."""
+        if frames is None:
+            frames = range(self.camNet.points2d.shape[1]) if self.camNet is not None else []
+        return self._reprojection_on(frames)[0].cpu().numpy()
+
+    def get_joint_reprojection_error(self, img_id, joint_id, camNet=None):
+        """The largest reprojection error of joint `joint_id` on image `img_id` over the cameras, in pixels.  `camNet` (the
+        reference's signature): the cameras to take the maximum over, camera ids or Camera objects (or a CameraNetwork)."""
+        err, jmax, _ = self._reprojection_on([img_id])
+        if camNet is None:
+            return float(jmax[0, joint_id])
+        cams = camNet.cam_list if hasattr(camNet, "cam_list") else camNet
+        ids = [int(getattr(c, "cam_id", c)) for c in cams]
+        return float(err[ids, 0, joint_id].max()) if ids else 0.0
+
+    def joint_has_error(self, img_id, joint_id):
+        """Whether joint `joint_id` of image `img_id` is flagged: its error exceeds config.REPROJ_THR[joint_id]."""
+        mask = int(self._reprojection_on([img_id])[2][0])
+        return bool((mask >> int(joint_id)) & 1)
+
+    def next_error_in_range(self, range_of_ids):
+        """The first image id of `range_of_ids`, in its order, with a flagged joint, or None.  Evaluated on the device in chunks of
+        growing size (1 024 ids, doubling up to 65 536), stopping at the first chunk that holds a flagged frame."""
+        import itertools
+
+        it, size = iter(range_of_ids), self._ERROR_CHUNK_FIRST
+        while True:
+            ids = list(itertools.islice(it, size))
+            if not ids:
+                return None
+            hit = torch.nonzero(self._reprojection_on(ids)[2]).flatten()
+            if hit.numel():
+                return ids[int(hit[0])]
+            size = min(2 * size, self._ERROR_CHUNK_LAST)
+
+    def next_error(self, img_id):
+        """The next image after `img_id` with a flagged joint, or None (reference df3d/core.py:205-215)."""
+        return self.next_error_in_range(range(img_id + 1, self.max_img_id + 1))
+
+    def prev_error(self, img_id):
+        """The previous image before `img_id` with a flagged joint, or None (reference df3d/core.py:217-227)."""
+        return self.next_error_in_range(range(img_id - 1, -1, -1))
 
     def calibrate_calc(self, min_img_id, max_img_id):
         """Bundle adjustment from the shipped initial calibration (reference :229-250; like the reference the

@@ -291,3 +291,51 @@ def pictorial_correct(P, camera_ordering, points2d, peak_count, peak_pts, peak_v
         kept = ps_proposals(P, camera_ordering, points2d, peak_count, peak_pts, peak_val, image_shape, (0, 0), num_proposals, tau, w_reproj, w_heatmap)
         out = ps_solve(camera_ordering, points2d, peak_count, peak_pts, kept, (0, 0), w_bone, out)
     return PictorialResult(*out)
+
+
+@_on_tensor_device
+def reprojection_errors(P, points2d_px, X=None, thresholds=None, frames=None):
+    """Per-joint reprojection errors and suspect-joint masks, df3d_reproj_errors.  P [ncam, 3, 4] float64
+    (numpy or tensor, pixels); points2d_px [ncam, T, J, 2] float64 cuda (row_px, col_px); X [T, J, 3] float64 cuda on the same
+    frames, triangulate() of the selected detections when None; thresholds [J] pixels (default config.REPROJ_THR, J = 38);
+    frames: optional frame ids, gathered on the device from points2d_px (and X), the outputs in their order.
+    Returns (err [ncam, nf, J], jmax [nf, J] float64, mask [nf] int64: bit j set when jmax > thresholds[j]) on the device."""
+    from .config import REPROJ_THR
+
+    lib = _native.load()
+    _need(points2d_px, torch.float64, "points2d_px")
+    if points2d_px.dim() != 4 or points2d_px.shape[3] != 2:
+        raise ValueError("points2d_px must be [ncam, T, J, 2]")
+    ncam, T, J, _ = points2d_px.shape
+    dev = points2d_px.device
+    Ph = np.ascontiguousarray(P.detach().cpu().numpy() if isinstance(P, torch.Tensor) else P, dtype=np.float64)
+    if Ph.shape != (ncam, 3, 4):
+        raise ValueError("P must be [ncam, 3, 4]")
+    thr = np.ascontiguousarray(REPROJ_THR if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+    if thr.shape != (J,):
+        raise ValueError(f"thresholds must hold one value per joint ({J})" + (" (config.REPROJ_THR is for 38)" if thresholds is None else ""))
+    if X is not None:
+        _need(X, torch.float64, "X")
+        if tuple(X.shape) != (T, J, 3) or X.device != dev:
+            raise ValueError("X must be [T, J, 3] on the device of points2d_px")
+    px = points2d_px
+    if frames is not None:
+        idx = torch.as_tensor(np.asarray(frames, dtype=np.int64).reshape(-1), device=dev)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= T):
+            raise IndexError(f"frame ids must lie in [0, {T})")
+        px = points2d_px.index_select(1, idx).contiguous()
+        if X is not None:
+            X = X.index_select(0, idx).contiguous()
+    nf = px.shape[1]
+    if X is None:
+        X = triangulate(Ph, px)
+    err = torch.empty((ncam, nf, J), dtype=torch.float64, device=dev)
+    jmax = torch.empty((nf, J), dtype=torch.float64, device=dev)
+    mask = torch.empty((nf,), dtype=torch.int64, device=dev)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _native.check(
+        lib.df3d_reproj_errors(Ph.ctypes.data_as(dp), px.data_ptr(), X.data_ptr(), ncam, nf, J, thr.ctypes.data_as(dp), err.data_ptr(), jmax.data_ptr(),
+                               mask.data_ptr(), _stream(px)),
+        "df3d_reproj_errors",
+    )
+    return err, jmax, mask

@@ -181,6 +181,22 @@ int df3d_ps_solve(const int* ordering_host, const int* parent_host, const double
                   double* points2d_dev, int* choice_dev, double* energy_dev, double* work_dev, size_t work_doubles, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a6c per-joint reprojection errors and suspect-joint masks (the model is this project's own
+ *     specification, restated in float64 by tests/reproj_oracle.py).  The first half of the reference's correction workflow
+ *     (Core.next_error / joint_has_error, reference df3d/core.py:205-227, 481-507).
+ * P_host [ncam, 3, 4] HOST float64 (pixels, no distortion: the DLT's model), pts_px_dev [ncam, T, J, 2] (row_px, col_px),
+ *     X_dev [T, J, 3] (df3d_triangulate of the same detections on the Python paths; taken as given).  A camera is a view of
+ *     (t, j) when both coordinates are non-zero.  With >= 2 views, every view c gets e = |P_c [X; 1] projected - (col, row)|
+ *     in pixels (+inf when w <= 0 or the result is not finite); non-views, and every camera of a joint with < 2 views, get 0.
+ * err_dev [ncam, T, J] (camera-major like points2d), jmax_dev [T, J] = max over cameras (may be NULL), mask_dev [T] int64:
+ *     bit j set when jmax[t, j] > thr_host[j] (strict; thr_host [J] HOST float64, each >= 0 and not NaN, +inf disables j).
+ * 1 <= ncam <= 8, 1 <= J <= 64, T >= 0 (T = 0: nothing to do).  Asynchronous on `stream`; arguments are validated before the
+ *     device is touched.
+ * ---------------------------------------------------------------------------------------------- */
+int df3d_reproj_errors(const double* P_host, const double* pts_px_dev, const double* X_dev, int ncam, int T, int J,
+                       const double* thr_host, double* err_dev, double* jmax_dev, long long* mask_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a9  per-side Procrustes registration to the template pose + the `Core.get_points3d` chain.
  *     Replaces reference df3d/procrustes.py:51-151 (`procrustes_seperate`, call site df3d/core.py:358,340),
  *     df3d/plot_util.py:85-91 (`normalize_pose_3d`, call site core.py:341) and df3d/signal_util.py:69-100
