@@ -84,6 +84,7 @@ PROTOTYPES = {
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
     "df3d_reproj_errors": (c_int, [POINTER(c_double), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_smooth_pose2d": (c_int, [c_void_p, c_int, c_longlong, c_int, c_int, c_double, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p]),
     "df3d_column_median": (c_int, [c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_void_p]),
     "df3d_procrustes_work_doubles": (c_longlong, [c_longlong]),
     "df3d_procrustes": (c_int, [c_void_p, c_longlong, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_longlong, c_void_p]),

@@ -95,9 +95,24 @@ class CameraNetwork:
             cal = lookup.get(c, {})
             self.cam_list.append(Camera(c, self._points2d[c], cal.get("R"), cal.get("tvec"), cal.get("intr"), cal.get("distort"), image_path))
         self.points3d = None
+        self._smoothed = None   # smooth_points2d()'s result; whoever writes points2d in place calls drop_smoothed()
 
     def __getitem__(self, cam_id):
         return self.cam_list[cam_id]
+
+    def smooth_points2d(self, refresh=False):
+        """[ncam, T, J, 2] pixels: the detections smoothed along time for display, every camera in one
+        launch of df3d_smooth_pose2d.  Kept on this object until drop_smoothed() or `refresh`, and handed out read-only: every
+        caller sees the one array, so copy before editing."""
+        if refresh or self._smoothed is None:
+            px = torch.from_numpy(self._points2d).to(self._device())
+            self._smoothed = ops.smooth_pose2d(px).cpu().numpy()
+            self._smoothed.setflags(write=False)
+        return self._smoothed
+
+    def drop_smoothed(self):
+        """Forget the smoothed detections: points2d was edited in place."""
+        self._smoothed = None
 
     @property
     def points2d(self):

@@ -26,6 +26,9 @@ def parse_cli_args(argv=None):
                    default=[0, 1, 2, 3, 4, 5, 6], type=int, nargs="*")
     p.add_argument("--video-2d", help="Generate pose2d videos", action="store_true")
     p.add_argument("--video-3d", help="Generate pose3d videos", action="store_true")
+    p.add_argument("--smooth-2d", dest="smooth_2d", action="store_true",
+                   help="With --video-2d: draw the temporally smoothed 2-D detections (a 20-frame Gaussian where the detections are "
+                        "quiet, the detection itself where they move) instead of the raw ones; results on disk are unchanged")
     p.add_argument("--skip-pose-estimation", help="Skip 2D and 3D pose estimation", dest="skip_estimation", action="store_true")
     p.add_argument("--batch-size", help="Batch size for inference", type=int, default=8)
     p.add_argument("--pin-memory-disabled", help="Disable pinned host staging buffers", action="store_true")
@@ -51,6 +54,8 @@ def parse_cli_args(argv=None):
         p.error("--auto-correct needs the heat-map peaks of this run's pose estimation: it cannot be combined with --skip-pose-estimation")
     if args.correct_only_flagged and not args.auto_correct:
         p.error("--correct-only-flagged restricts --auto-correct: it needs --auto-correct")
+    if args.smooth_2d and not args.video_2d:
+        p.error("--smooth-2d changes what --video-2d draws: it needs --video-2d")
     inp = Path(args.input_folder).expanduser().resolve()
     args.output_folder = str(inp.with_name(inp.stem + "_df3d")) if args.output_folder is None else str(Path(args.output_folder).expanduser().resolve())
     args.input_folder = str(inp)
@@ -103,7 +108,7 @@ def run(args):
 
         def videos(beat):
             if args.video_2d:
-                video.make_pose2d_video(core, fps=fps, progress=beat)
+                video.make_pose2d_video(core, fps=fps, progress=beat, smooth=getattr(args, "smooth_2d", False))
             if args.video_3d:
                 video.make_pose3d_video(core, fps=fps, progress=beat)
 

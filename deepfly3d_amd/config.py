@@ -48,6 +48,26 @@ PICTORIAL_DEFAULTS = {
 # exceeds REPROJ_THR[j] pixels.  The reference's `config["reproj_thr"]` (df3d/config.py:41): 40 for each of the 38 joints.
 REPROJ_THR = np.full(38, 40.0, dtype=np.float64)
 
+# ---- which camera sees which joint (reference df3d/skeleton_fly.py:202-250), by camera id: cameras 0-2 look at the side whose
+# joints are 0..18, cameras 4-6 at the side of joints 19..37, camera 3 faces the fly.  Pinned by tests/golden/skeleton_tables.npz.
+# Where df3d::relayout_source (csrc/geometry_dev.h) fills a joint of a side camera under the identity ordering, this table sees it;
+# the table also lists the antenna for cameras 2 and 4, which the re-layout leaves at zero (as the reference's own does).
+FRONT_CAMERA = 3
+IGNORE_JOINT_ID = [j for j, kind in enumerate(TRACKED) if kind in (BODY_COXA, COXA_FEMUR, ANTENNA)]   # the reference's ignore_joint_id
+
+
+def camera_see_joint(cam_id, joint_id):
+    """Whether camera `cam_id` (0..6; 7 is an alias of the front camera, as in the reference) can see joint `joint_id` (0..37)."""
+    cam_id = FRONT_CAMERA if cam_id == 7 else int(cam_id)
+    if not 0 <= cam_id < config["num_cameras"]:
+        raise NotImplementedError(f"no camera {cam_id}")
+    kind, limb = TRACKED[joint_id], limb_of_joint(joint_id)
+    if cam_id == FRONT_CAMERA:   # the front two legs of both sides from the femur-tibia joint on, and the antennae
+        return limb % 5 in (0, 1, 3) and kind not in (BODY_COXA, COXA_FEMUR)
+    if (limb >= 5) != (cam_id > FRONT_CAMERA):   # a side camera sees its own side only
+        return False
+    return not (cam_id in (2, 4) and kind == STRIPE)   # the two rear cameras cannot see the stripes
+
 
 def bone_tree():
     """(parent [38] int32, bone [38, 2] float64 (mean, deviation)) from TRACKED: a coxa-femur, femur-tibia, tibia-tarsus or

@@ -7,8 +7,9 @@ MI355X back-end.  Same constructor, methods, attributes, exceptions and result-p
     core.calibrate_calc(min_img_id, max_img_id)                        # reference :229-250
     core.save()
 
-GUI-only methods (interactive correction, plotting) are out of scope; the correction store and
-`corrected_points2d*` are kept so that stored corrections reach the triangulation.  The error navigation (`next_error`,
+The GUI itself is out of scope; the methods it drives are here: the correction store and
+`corrected_points2d*`, through which stored corrections reach the triangulation, and the manual half of the correction workflow
+(`nearest_joint`, `move_joint`, `write_corrections`, `check_cameras`, `smooth_points2d`).  The error navigation (`next_error`,
 `prev_error`, `next_error_in_range`, `joint_has_error`, `get_joint_reprojection_error`) runs on the device.
 """
 import glob
@@ -22,7 +23,7 @@ import torch
 
 from . import _native, logger, ops
 from .camera_network import CameraNetwork
-from .config import config, load_calibration
+from .config import IGNORE_JOINT_ID, camera_see_joint, config, load_calibration
 from .db import PoseDB
 from .inference import inference_folder
 from .os_util import camera_videos, extract_frames, get_max_img_id, parse_frame_rate, parse_vid_name, probe_frame_rate
@@ -260,6 +261,7 @@ class Core:
         self.points2d_argmax = np.array(argmax2d, dtype=np.float64, copy=True)
         self.points2d = corrected.cpu().numpy()
         np.copyto(self.camNet.points2d, self.points2d * self.image_shape[::-1])
+        self.camNet.drop_smoothed()
         changed = int((self.points2d != self.points2d_argmax).any(axis=-1).sum())
         energy = f"mean minimum energy per frame {float(res.energy.mean()) if res.energy.numel() else 0.0:.4f}"
         if flagged is None:
@@ -334,6 +336,66 @@ class Core:
     def prev_error(self, img_id):
         """The previous image before `img_id` with a flagged joint, or None (reference df3d/core.py:217-227)."""
         return self.next_error_in_range(range(img_id - 1, -1, -1))
+
+    # -- manual corrections (DESIGN.md section 11; reference df3d/core.py:253-296, 477-479, 509-544) ---------------------------------
+    _MOVE_THRESHOLD = 30   # pixels, per coordinate: a pose that differs less from the estimate on every checked joint is not stored
+
+    def nearest_joint(self, cam_id, img_id, x, y):
+        """The id of the joint of image `img_id` of camera `cam_id` that lies nearest to (x, y), among the joints the camera can
+        see (config.camera_see_joint; the others are put at (9999, 9999) first, as in the reference), in
+        corrected_points2d(cam_id, img_id).  Argument order and comparison are the reference's: `x` is compared with stored
+        column 0 and `y` with stored column 1, and the stored columns are (row_px, col_px) -- so `x` is the ROW and `y` the COLUMN
+        of the pixel.  Euclidean distance, ties to the lowest id; plain numpy.  (A point more than ~4 000 px from every seen joint
+        is nearer to (9999, 9999); inside an image that cannot happen.)"""
+        pts = self.corrected_points2d(cam_id, img_id)
+        pts[[j for j in range(len(pts)) if not camera_see_joint(cam_id, j)]] = [9999, 9999]
+        return int(np.argmin(np.hypot(pts[:, 0] - x, pts[:, 1] - y)))
+
+    def move_joint(self, cam_id, img_id, joint_id, x, y):
+        """Move joint `joint_id` of one image to (x, y) = (row_px, col_px), the stored order (see nearest_joint), and store the
+        pose as a manual correction through write_corrections (reference df3d/core.py:277-284)."""
+        modified = sorted(set(list(self.db.read_modified_joints(cam_id, img_id)) + [int(joint_id)]))
+        points = self.corrected_points2d(cam_id, img_id)
+        points[joint_id] = np.array([x, y])
+        self.write_corrections(cam_id, img_id, modified, points)
+
+    def write_corrections(self, cam_id, img_id, modified_joints, points2d):
+        """Store `points2d` [38, 2] pixels (row, col), ALL joints of the image, as its manual correction -- if it differs from the
+        camera network's estimate by more than 30 px in a coordinate of a joint the camera sees and config.IGNORE_JOINT_ID does not
+        list; unseen joints are stored as zero, the pose normalised by `image_shape` and marked for training.  A pose nearer than
+        that removes the stored correction (reference df3d/core.py:509-544).  save_corrections() writes the store to disk."""
+        joints = range(config["num_joints"])
+        seen = [j for j in joints if camera_see_joint(cam_id, j)]
+        checked = [j for j in seen if j not in IGNORE_JOINT_ID]
+        points2d = np.asarray(points2d, dtype=np.float64)
+        if np.any(np.abs(self.camNet.cam_list[cam_id][img_id] - points2d)[checked] > self._MOVE_THRESHOLD):
+            stored = points2d.copy()
+            stored[[j for j in joints if j not in seen], :] = 0.0
+            # (the reference divides (row, col) by image_shape = [W, H] as it stands; manual_corrections() multiplies by the same)
+            self.db.write(stored / self.image_shape, cam_id, img_id, True, list(modified_joints))
+        else:
+            self.db.remove_corrections(cam_id, img_id)
+
+    def check_cameras(self):
+        """AssertionError naming the cameras without a single detection (reference df3d/core.py:477-479).  The 19 -> 38 re-layout
+        gives the front camera (ordering[3]) none, here as in the reference, so a recording straight from pose2d_estimation names it."""
+        cam_missing = [cam.cam_id for cam in self.camNet.cam_list if cam.is_empty()]
+        assert not cam_missing, "Some cameras are missing: {}".format(cam_missing)
+
+    def smooth_points2d(self, cam_id, refresh=False):
+        """[T, 38, 2] pixels: the detections of camera `cam_id` smoothed along time for display (reference df3d/core.py:286-296;
+        DESIGN.md section 11).  All cameras are smoothed in one launch on the first call and kept on the camera network; a new
+        network (calibrate_calc, reopening a result), auto_correct() and corrected_points2d_matrix() drop them, `refresh=True`
+        recomputes.  The result is a read-only view of the kept array: copy it before editing.  The reference keeps its cache in a mutable default argument, `private_cache=dict()`, which every Core of the
+        process shares, so that a second recording gets the first one's points: that is a bug and not reproduced.  A rank-0 method,
+        like the reprojection-error queries."""
+        from . import distributed as dd
+
+        if dd.current()[0] != 0:
+            raise RuntimeError("smooth_points2d is a rank-0 method: the camera network lives on rank 0")
+        if self.camNet is None:
+            raise RuntimeError("smooth_points2d needs the camera network: run calibrate_calc() first")
+        return self.camNet.smooth_points2d(refresh=refresh)[cam_id]
 
     def calibrate_calc(self, min_img_id, max_img_id):
         """Bundle adjustment from the shipped initial calibration (reference :229-250; like the reference the
@@ -487,6 +549,7 @@ class Core:
         estimates -- in place, like the reference (df3d/core.py:387-401)."""
         corrections = self.db.manual_corrections()
         everything = self.camNet.points2d
+        self.camNet.drop_smoothed()
         for cam_id, per_image in corrections.items():
             for img_id, fix in per_image.items():
                 if cam_id < config["num_cameras"] and img_id < self.num_images:
@@ -499,11 +562,15 @@ class Core:
 
     def plot_2d(self, cam_id, img_id, with_corrections=False, smooth=False, joints=[]):
         """Image `img_id` of camera `cam_id` with its 2-D pose drawn on it, as an ndarray (reference df3d/core.py:298-319).
-        Host-side drawing; `smooth` (temporal smoothing for videos) is accepted and ignored, `joints` restricts the drawing
-        to the listed joint ids."""
+        Host-side drawing.  `smooth=True` draws the temporally smoothed estimate (smooth_points2d) instead of the estimate;
+        with `with_corrections=True` a stored manual correction of the image wins over either.  `joints` restricts the drawing to
+        the listed joint ids."""
         from .config import skeleton_bones
 
-        pts = self.corrected_points2d(cam_id, img_id) if with_corrections else np.array(self.camNet.cam_list[cam_id][img_id], dtype=np.float64)
+        pts = np.array((self.smooth_points2d(cam_id) if smooth else self.camNet.cam_list[cam_id])[img_id], dtype=np.float64)
+        fix = self._correction_for(self.db.manual_corrections(), cam_id, img_id) if with_corrections else None
+        if fix is not None:
+            pts[:] = fix
         if len(joints):
             keep = np.zeros(len(pts), dtype=bool)
             keep[list(joints)] = True

@@ -339,3 +339,57 @@ def reprojection_errors(P, points2d_px, X=None, thresholds=None, frames=None):
         "df3d_reproj_errors",
     )
     return err, jmax, mask
+
+
+def gaussian_window_taps(window_size, sigma, truncate=4.0):
+    """[window_size] float64: what a Gaussian filter of deviation `sigma`, cut at int(truncate * sigma + 0.5) samples and applied
+    to a line of `window_size` samples under nearest extension, multiplies each sample by to form output sample window_size // 2.
+    Taps exp(-k^2 / 2 sigma^2) for |k| <= radius, normalised to sum 1; a tap that falls left of the line adds to sample 0, one
+    that falls right of it to the last sample.  sigma = 0.1 has radius 0: the unit tap, the identity."""
+    w, sigma = int(window_size), float(sigma)
+    if w < 1 or not sigma > 0.0:
+        raise ValueError("window_size must be >= 1 and sigma > 0")
+    radius = int(float(truncate) * sigma + 0.5)
+    k = np.arange(-radius, radius + 1, dtype=np.float64)
+    taps = np.exp(-0.5 * (k / sigma) ** 2)
+    taps /= taps.sum()
+    folded = np.zeros(w, dtype=np.float64)
+    np.add.at(folded, np.clip(w // 2 + np.arange(-radius, radius + 1), 0, w - 1), taps)
+    return folded
+
+
+SMOOTH_SIGMA, KEEP_SIGMA = 7.0, 0.1   # reference df3d/signal_util.py:151-154: a quiet window is smoothed, a lively one kept
+
+
+@_on_tensor_device
+def smooth_pose2d(points2d, window_size=20, std_thr=5.0):
+    """Temporal smoothing of 2-D detections for display (reference df3d/signal_util.py:135-160),
+    df3d_smooth_pose2d.  points2d [..., T, J, 2] float64 cuda with at most 8 leading cameras in all; every (camera, joint,
+    coordinate) series is filtered along T: where the population deviation of the `window_size` samples around a frame is below
+    `std_thr` the frame becomes their Gaussian (sigma 7) average, else it stays.  One launch; returns a new tensor of the same
+    shape.  T = 0 returns an empty tensor.  The reference's `pad` argument only works at its default and is not exposed."""
+    lib = _native.load()
+    _need(points2d, torch.float64, "points2d")
+    if points2d.dim() < 3 or points2d.shape[-1] != 2:
+        raise ValueError("points2d must be [..., T, J, 2]")
+    T, J = int(points2d.shape[-3]), int(points2d.shape[-2])
+    C = int(np.prod(points2d.shape[:-3], dtype=np.int64))
+    out = torch.empty_like(points2d)
+    if C == 0 or J == 0:
+        return out
+    w = int(window_size)
+    ws, wk = gaussian_window_taps(max(w, 1), SMOOTH_SIGMA), gaussian_window_taps(max(w, 1), KEEP_SIGMA)
+    dp = ctypes.POINTER(ctypes.c_double)
+    _native.check(
+        lib.df3d_smooth_pose2d(points2d.data_ptr(), C, T, 2 * J, w, float(std_thr), ws.ctypes.data_as(dp), wk.ctypes.data_as(dp), out.data_ptr(),
+                               _stream(points2d)),
+        "df3d_smooth_pose2d",
+    )
+    return out
+
+
+def filter_batch_2d(points2d, freq=100.0):
+    """The reference's `filter_batch_2d` (df3d/signal_util.py:103-132) on the device: df3d_oneeuro_filter with its constants
+    (mincutoff 1e-4, beta 30, dcutoff 1) and its time stamps, which start at 0 where `filter_batch`'s start at 0.1.
+    points2d [T, J, 2] float64 cuda; bit-identical to the reference's float arithmetic."""
+    return oneeuro_filter(points2d, freq=freq, mincutoff=1e-4, beta=30.0, dcutoff=1.0, first_stamp=0, stamp_step=0.1)

@@ -231,12 +231,14 @@ def _frame_files(core, img_id):
     return out
 
 
-def _grid_frames(core, renderer, batch=16):
-    """Yield (img_id, [2 H, 3 W, 3] uint8 cuda) for every image of the recording: files -> device JPEG decode -> one drawing launch."""
+def _grid_frames(core, renderer, batch=16, smooth=False):
+    """Yield (img_id, [2 H, 3 W, 3] uint8 cuda) for every image of the recording: files -> device JPEG decode -> one drawing launch.
+    `smooth`: draw the temporally smoothed detections (Core.smooth_points2d) instead of the detections."""
     from . import jpeg
 
     W, H = core.image_shape
-    pts = np.stack([core.camNet.cam_list[c].points2d[: core.num_images] for c in GRID_CAMERAS], axis=1)   # (T, 6, J, 2) pixels (row, col)
+    per_cam = core.smooth_points2d if smooth else (lambda c: core.camNet.cam_list[c].points2d)
+    pts = np.stack([per_cam(c)[: core.num_images] for c in GRID_CAMERAS], axis=1)   # (T, 6, J, 2) pixels (row, col)
     pts_dev = torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float64)).to(renderer.dev)
     for t0 in range(0, core.num_images, batch):
         ids = range(t0, min(t0 + batch, core.num_images))
@@ -250,15 +252,16 @@ def _video_stem(core, kind):
     return os.path.join(core.output_folder, f"video_{kind}_" + core.input_folder.replace("/", "_"))
 
 
-def make_pose2d_video(core, fps=None, progress=None):
-    """video_pose2d_<folder>: per image the 2 x 3 camera grid with the 2-D pose drawn on it (reference video.py:21-49).  Returns the path."""
+def make_pose2d_video(core, fps=None, progress=None, smooth=False):
+    """video_pose2d_<folder>: per image the 2 x 3 camera grid with the 2-D pose drawn on it (reference video.py:21-49).  Returns the path.
+    `smooth=True` draws the temporally smoothed detections; the default draws the detections themselves."""
     fps = fps or DEFAULT_FPS
     W, H = core.image_shape
     renderer = FrameRenderer(H, W, config["num_joints"], core.device)
     writer, path = open_writer(_video_stem(core, "pose2d"), 3 * W, 2 * H, fps)
     host = torch.empty((2 * H, 3 * W, 3), dtype=torch.uint8).pin_memory()
     try:
-        for _, frame in _grid_frames(core, renderer):
+        for _, frame in _grid_frames(core, renderer, smooth=smooth):
             host.copy_(frame)
             writer.write(host.numpy())
             if progress is not None:

@@ -197,6 +197,23 @@ int df3d_reproj_errors(const double* P_host, const double* pts_px_dev, const dou
                        const double* thr_host, double* err_dev, double* jmax_dev, long long* mask_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a6d temporal smoothing of the 2-D detections for display: reference df3d/signal_util.py:135-160
+ *     `smooth_pose2d` (call site df3d/core.py:286-296), restated in float64 by tests/smooth_oracle.py.
+ * pts_dev / out_dev [C, T, nch] float64 (nch = J * 2 contiguous doubles per frame); every (camera, channel) series is filtered
+ *     along T on its own.  Output t looks at the `window` samples t - window/2 .. t + window/2 - 1 of the series extended by edge
+ *     replication (frames before 0 read frame 0, frames after T - 1 read frame T - 1), takes their population standard deviation
+ *     sqrt(mean((x - mean)^2)) and writes sum_k w_smooth[k] x[k] when it is below std_thr (strict), sum_k w_keep[k] x[k] otherwise
+ *     (taps of w_keep that are exactly 0 are skipped).  A window that holds a NaN or an infinity has a NaN deviation and takes the
+ *     keep taps.  w_smooth_host / w_keep_host [window] HOST float64, finite: a filter kernel folded onto the window (Python:
+ *     ops.gaussian_window_taps; the reference's pair is sigma 7 and sigma 0.1, the latter the unit tap at window/2).
+ * 1 <= C <= 8, 1 <= nch <= 128, window even in [2, 64], std_thr >= 0 and not NaN, T >= 0 (T = 0: nothing to do); out_dev must
+ *     not overlap pts_dev.  One launch for all cameras, asynchronous on `stream`; arguments are validated before the device is
+ *     touched.
+ * ---------------------------------------------------------------------------------------------- */
+int df3d_smooth_pose2d(const double* pts_dev, int C, long long T, int nch, int window, double std_thr, const double* w_smooth_host,
+                       const double* w_keep_host, double* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a9  per-side Procrustes registration to the template pose + the `Core.get_points3d` chain.
  *     Replaces reference df3d/procrustes.py:51-151 (`procrustes_seperate`, call site df3d/core.py:358,340),
  *     df3d/plot_util.py:85-91 (`normalize_pose_3d`, call site core.py:341) and df3d/signal_util.py:69-100
