@@ -23,7 +23,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # render.hip (f4, the video frames): float64 pixel tests restated in numpy by oracle/render.py, compared bit for bit
 # smooth.hip keeps the default -ffp-contract=fast on purpose: its test bound is 1e-10 px, not bit parity, fused multiply-adds only
 # tighten the sums, and the pass is bound by float64 vector instructions, which contraction cuts by a quarter
-FILE_FLAGS = {"pose3d.hip": ["-ffp-contract=off"], "ba_lsmr.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"]}
+# subpixel.hip: the float64 sub-pixel rule, compared bit for bit with tests/subpixel_oracle.py
+FILE_FLAGS = {"pose3d.hip": ["-ffp-contract=off"], "ba_lsmr.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"],
+              "subpixel.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -49,9 +49,15 @@ def parse_cli_args(argv=None):
     p.add_argument("--correct-only-flagged", dest="correct_only_flagged", action="store_true",
                    help="With --auto-correct: keep the correction only on the joints whose reprojection error exceeds the per-joint "
                         "threshold (40 px) on the arg-max detections; every other detection stays the arg-max one")
+    p.add_argument("--subpixel", action="store_true",
+                   help="Refine every 2-D detection inside its heat-map cell (up to half a cell, 3.75 px, per axis) from the 3 x 3 values round the "
+                        "maximum instead of reporting the cell itself; the result then carries the key subpixel.  Off by default: the default is the "
+                        "reference's arithmetic")
     args = p.parse_args(argv)
     if args.auto_correct and args.skip_estimation:
         p.error("--auto-correct needs the heat-map peaks of this run's pose estimation: it cannot be combined with --skip-pose-estimation")
+    if args.subpixel and args.skip_estimation:
+        p.error("--subpixel needs the heat-maps of this run's pose estimation: it cannot be combined with --skip-pose-estimation")
     if args.correct_only_flagged and not args.auto_correct:
         p.error("--correct-only-flagged restricts --auto-correct: it needs --auto-correct")
     if args.smooth_2d and not args.video_2d:
@@ -89,7 +95,8 @@ def run(args):
     if not args.skip_estimation:
         from .config import PICTORIAL_DEFAULTS
 
-        core.pose2d_estimation(args.batch_size, args.pin_memory_disabled, num_peaks=PICTORIAL_DEFAULTS["num_peaks"] if auto else 0)
+        core.pose2d_estimation(args.batch_size, args.pin_memory_disabled, num_peaks=PICTORIAL_DEFAULTS["num_peaks"] if auto else 0,
+                               subpixel=getattr(args, "subpixel", False))
         core.save()
     core.calibrate_calc(0, core.max_img_id)
     if auto and getattr(args, "correct_only_flagged", False):

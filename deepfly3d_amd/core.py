@@ -104,6 +104,7 @@ class Core:
         self.peaks = None             # (count, points, values) of pose2d_estimation(num_peaks=K), numpy [7, T, 19, ...]; rank 0
         self.points2d_argmax = None   # the arg-max detections, once auto_correct() has replaced points2d
         self._corrected = False       # every rank: auto_correct() ran (save() then triangulates on rank 0 alone)
+        self._subpixel = False        # pose2d_estimation(subpixel=True) ran: save() appends the key "subpixel"
         if os.path.exists(self.save_path):
             self._resume(self.save_path)
 
@@ -177,12 +178,14 @@ class Core:
         return os.path.join(self.output_folder, f"df3d_result_{flat}.pkl")
 
     # -- hot path -------------------------------------------------------------------------------------
-    def pose2d_estimation(self, batch_size: int = 8, disable_pin_memory: bool = False, num_peaks: int = 0):
+    def pose2d_estimation(self, batch_size: int = 8, disable_pin_memory: bool = False, num_peaks: int = 0, subpixel: bool = False):
         """2-D pose on every frame of every camera, then the 19 -> 38 joint layout (reference :170-203).
 
         Under `torch.distributed` (one process per GPU) every rank processes a contiguous range of frames and ONE
         gather brings the results to rank 0, which alone goes on to calibrate and save.
-        `num_peaks=K` > 0 also keeps the K best local maxima of every heat-map in `self.peaks` for auto_correct()."""
+        `num_peaks=K` > 0 also keeps the K best local maxima of every heat-map in `self.peaks` for auto_correct().
+        `subpixel=True` (opt-in) refines every detection, and every kept peak, inside its heat-map cell; save() then
+        appends the key "subpixel" to the result."""
         from . import distributed as dd
 
         flip = [cam for idx, cam in enumerate(self.camera_ordering) if idx > 3]
@@ -191,13 +194,14 @@ class Core:
         res = inference_folder(
             folder=self.input_folder, camera_ids_to_flip=flip, return_heatmap=False, return_confidence=True,
             max_img_id=self.max_img_id, batch_size=batch_size, disable_pin_memory=disable_pin_memory, dtype=self.dtype, device=self.device,
-            frame_range=(t0, t1), as_device_tensors=True, return_peaks=num_peaks,
+            frame_range=(t0, t1), as_device_tensors=True, return_peaks=num_peaks, subpixel=subpixel,
         )
         points19, conf, peaks = res[0], res[1], list(res[2:])
         # 19 -> 38 layout on the device, then (N > 1) ONE gather of the device tensors: no host round trip before it
         points2d = ops.relayout_19_to_38(points19.contiguous(), self.camera_ordering)
         self._points2d_shard = points2d if world > 1 else None
         self._corrected, self.points2d_argmax = False, None
+        self._subpixel = bool(subpixel)
         if dd.collective_needed(world):
             gathered = dd.gather_packed([(points2d, 1), (conf, 1)] + [(p, 1) for p in peaks], self.num_images)
             self.is_primary = rank == 0
@@ -527,6 +531,8 @@ class Core:
         result["heatmap_confidence"] = self.conf
         if getattr(self, "_corrected", False) and self.points2d_argmax is not None:
             result["points2d_argmax"] = np.copy(self.points2d_argmax)
+        if getattr(self, "_subpixel", False):   # only when this run refined its detections: without it the schema is the reference's
+            result["subpixel"] = True
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")

@@ -162,20 +162,21 @@ def preprocess_u8(frames_u8, flip, out_hw=(256, 512)):
     return out
 
 
-def inference_views(images, engine, return_heatmap=False):
-    """images: float32 NHWC [n, 256, 512, 3] cuda -> (points [n, 19, 2], conf [n, 19]) (+ heat-maps)."""
+def inference_views(images, engine, return_heatmap=False, subpixel=False):
+    """images: float32 NHWC [n, 256, 512, 3] cuda -> (points [n, 19, 2], conf [n, 19]) (+ heat-maps).  `subpixel=True`: the points refined
+    inside their heat-map cells (ops.heatmap_argmax(subpixel=True))."""
     hm = engine.forward(images)
-    pts, conf = ops.heatmap_argmax(hm, nonfinite=engine.nonfinite_planes)   # (the overflow guard: engine.check_finite() reads the counter)
+    pts, conf = ops.heatmap_argmax(hm, nonfinite=engine.nonfinite_planes, subpixel=subpixel)   # (the overflow guard: engine.check_finite() reads the counter)
     return (pts, conf, hm) if return_heatmap else (pts, conf)
 
 
-def inference_frames(frames_u8, flip, engine, return_heatmap=False):
+def inference_frames(frames_u8, flip, engine, return_heatmap=False, subpixel=False):
     """frames_u8: uint8 [n, H, W(, C)] cuda camera frames, flip [n] uint8 or None -> (points [n, 19, 2], conf [n, 19]) (+ heat-maps):
     `inference_views(preprocess_u8(frames, flip), engine)` with the resize / normalisation done inside the network's first kernel."""
     if tuple(config["input_shape"]) != (engine.height, engine.width):
         raise ValueError("engine input size differs from config['input_shape']")
     hm = engine.forward_u8(frames_u8, flip, PREPROCESS["mean"], PREPROCESS["std"], resize=PREPROCESS["resize"])
-    pts, conf = ops.heatmap_argmax(hm, nonfinite=engine.nonfinite_planes)
+    pts, conf = ops.heatmap_argmax(hm, nonfinite=engine.nonfinite_planes, subpixel=subpixel)
     return (pts, conf, hm) if return_heatmap else (pts, conf)
 
 
@@ -193,7 +194,7 @@ DEVICE_BATCH_VIEWS = 896
 
 def inference_folder(folder, camera_ids_to_flip=(), return_heatmap=False, return_confidence=True, max_img_id=None,
                      batch_size=8, disable_pin_memory=False, dtype="f32", device=None, state_dict=None, frame_range=None,
-                     as_device_tensors=False, return_peaks=0):
+                     as_device_tensors=False, return_peaks=0, subpixel=False):
     """Drop-in for df2d.inference.inference_folder (see module docstring).  Host work: listing and reading the
     files.  Device work: JPEG decode (csrc/jpeg.hip), flip / resize / normalise, hourglass, arg-max.
     `frame_range=(t0, t1)` (multi-GPU sharding) restricts the call to images t0 <= id < t1; the outputs then have
@@ -201,7 +202,8 @@ def inference_folder(folder, camera_ids_to_flip=(), return_heatmap=False, return
     multi-GPU path gathers them without a host round trip).  `return_peaks=K` (1..16) also returns the K best local maxima of every
     heat-map (ops.heatmap_peaks, run on each batch's heat-maps in the stream of its forward, before the next forward reuses them):
     peak_count (7, T, 19) int32, peak_points (7, T, 19, K, 2) float32 normalised, peak_values (7, T, 19, K) float32, after the
-    other outputs.  With 0 (the default) the call is the one above."""
+    other outputs.  With 0 (the default) the call is the one above.  `subpixel=True` (opt-in) refines the points, and
+    the peak points, inside their heat-map cells by up to half a cell per axis; shapes, dtypes, confidences and peak values are unchanged."""
     from .jpeg import JpegFolderReader
 
     _native.require_gpu()
@@ -276,13 +278,13 @@ def inference_folder(folder, camera_ids_to_flip=(), return_heatmap=False, return
                     ns = min(7, luma.shape[0])
                     engine.canary(exact, lambda e: e.forward_u8(luma[:ns], flips[0][:ns], PREPROCESS["mean"], PREPROCESS["std"], resize=PREPROCESS["resize"]),
                                   what=f"the first {ns} views of {folder}")
-                res = inference_frames(luma, flips[k], engine, return_heatmap=return_heatmap or K > 0)
+                res = inference_frames(luma, flips[k], engine, return_heatmap=return_heatmap or K > 0, subpixel=subpixel)
                 # items are (camera, frame) in camera-major order = the flat order of points[ncam, T]: contiguous copies
                 lo = starts[k]
                 points_flat[lo : lo + len(chunk)] = res[0]
                 conf_flat[lo : lo + len(chunk), :, 0] = res[1]
                 if K:   # same stream, before the next forward overwrites the heat-maps
-                    for dst, src in zip(peaks_flat, ops.heatmap_peaks(res[2], K)):
+                    for dst, src in zip(peaks_flat, ops.heatmap_peaks(res[2], K, subpixel=subpixel)):
                         dst[lo : lo + len(chunk)] = src
                 if return_heatmap:
                     heat.append(res[2].cpu())

@@ -37,10 +37,12 @@ def _need(t, dtype, name):
 
 
 @_on_tensor_device
-def heatmap_argmax(heatmaps, nonfinite=None):
+def heatmap_argmax(heatmaps, nonfinite=None, subpixel=False):
     """heatmaps [n, J, H, W] float32 (cuda) -> (points [n, J, 2] float32 (row/H, col/W), conf [n, J] float32).
     `nonfinite`: an int32 CUDA tensor of one element (zeroed by its owner) that is incremented once per plane holding an infinity or a NaN --
-    the overflow guard of the reduced-precision engines (HourglassEngine.check_finite reads it)."""
+    the overflow guard of the reduced-precision engines (HourglassEngine.check_finite reads it).
+    `subpixel=True` (df3d_heatmap_argmax_subpixel): the point is the arg-max cell moved by up to half a cell per axis to the
+    maximum of the quadratic through its 3 x 3 neighbourhood; the cell, conf and the counter are those of the plain call."""
     lib = _native.load()
     _need(heatmaps, torch.float32, "heatmaps")
     n, j, h, w = heatmaps.shape
@@ -48,10 +50,11 @@ def heatmap_argmax(heatmaps, nonfinite=None):
     conf = torch.empty((n, j), dtype=torch.float32, device=heatmaps.device)
     if nonfinite is not None and not (nonfinite.is_cuda and nonfinite.dtype == torch.int32 and nonfinite.numel() == 1 and nonfinite.device == heatmaps.device):
         raise ValueError("nonfinite must be a one-element int32 CUDA tensor on the heat-maps' device")
+    name = "df3d_heatmap_argmax_subpixel" if subpixel else "df3d_heatmap_argmax_checked"
     _native.check(
-        lib.df3d_heatmap_argmax_checked(heatmaps.data_ptr(), n, j, h, w, pts.data_ptr(), conf.data_ptr(),
-                                        nonfinite.data_ptr() if nonfinite is not None else None, _stream(heatmaps)),
-        "df3d_heatmap_argmax_checked",
+        getattr(lib, name)(heatmaps.data_ptr(), n, j, h, w, pts.data_ptr(), conf.data_ptr(),
+                           nonfinite.data_ptr() if nonfinite is not None else None, _stream(heatmaps)),
+        name,
     )
     return pts, conf
 
@@ -158,9 +161,10 @@ def oneeuro_filter(series, freq=100.0, mincutoff=0.1, beta=2.0, dcutoff=1.0, fir
 
 
 @_on_tensor_device
-def heatmap_peaks(heatmaps, k):
+def heatmap_peaks(heatmaps, k, subpixel=False):
     """heatmaps [n, J, H, W] float32 (cuda) -> (count [n, J] int32, points [n, J, k, 2] float32 (row/H, col/W), values [n, J, k]
-    float32): the k best local maxima of every plane (df3d_heatmap_peaks; peak 0 is heatmap_argmax's cell)."""
+    float32): the k best local maxima of every plane (df3d_heatmap_peaks; peak 0 is heatmap_argmax's cell).  `subpixel=True`
+    (df3d_heatmap_peaks_subpixel): the same peaks, every point refined as heatmap_argmax(subpixel=True) refines its own."""
     lib = _native.load()
     _need(heatmaps, torch.float32, "heatmaps")
     n, j, h, w = heatmaps.shape
@@ -168,8 +172,8 @@ def heatmap_peaks(heatmaps, k):
     count = torch.empty((n, j), dtype=torch.int32, device=heatmaps.device)
     pts = torch.empty((n, j, k, 2), dtype=torch.float32, device=heatmaps.device)
     vals = torch.empty((n, j, k), dtype=torch.float32, device=heatmaps.device)
-    _native.check(lib.df3d_heatmap_peaks(heatmaps.data_ptr(), n, j, h, w, k, count.data_ptr(), pts.data_ptr(), vals.data_ptr(), _stream(heatmaps)),
-                  "df3d_heatmap_peaks")
+    name = "df3d_heatmap_peaks_subpixel" if subpixel else "df3d_heatmap_peaks"
+    _native.check(getattr(lib, name)(heatmaps.data_ptr(), n, j, h, w, k, count.data_ptr(), pts.data_ptr(), vals.data_ptr(), _stream(heatmaps)), name)
     return count, pts, vals
 
 

@@ -16,10 +16,12 @@ from .config import config
 
 
 class FramePipeline:
-    def __init__(self, engine, R, tvec, intr, camera_ordering=(0, 1, 2, 3, 4, 5, 6), image_shape=(960, 480)):
+    def __init__(self, engine, R, tvec, intr, camera_ordering=(0, 1, 2, 3, 4, 5, 6), image_shape=(960, 480), subpixel=False):
         """engine: HourglassEngine; R/tvec/intr: (7,3,3)/(7,3)/(7,3,3) calibration already in camera-id order
-        (i.e. after the reference's `calib_reordered`, core.py:240-242); image_shape = [W, H] of the camera frames."""
+        (i.e. after the reference's `calib_reordered`, core.py:240-242); image_shape = [W, H] of the camera frames.
+        `subpixel=True`: detections refined inside their heat-map cells (ops.heatmap_argmax(subpixel=True))."""
         self.engine = engine
+        self.subpixel = bool(subpixel)
         self.lib = _native.load()
         self.device = engine.device
         self.order = [int(c) for c in camera_ordering]
@@ -34,7 +36,7 @@ class FramePipeline:
         F = frames.shape[0]
         views = frames.reshape(F * 7, *frames.shape[2:])
         hm = self.engine.forward(views)
-        pts, conf = ops.heatmap_argmax(hm, nonfinite=self.engine.nonfinite_planes)  # [F*7, 19, 2], [F*7, 19]; counts planes with inf / NaN
+        pts, conf = ops.heatmap_argmax(hm, nonfinite=self.engine.nonfinite_planes, subpixel=self.subpixel)  # [F*7, 19, 2], [F*7, 19]; counts planes with inf / NaN
         # (frame, camera) -> (camera, frame): a strided copy of F*7*19*3 numbers (data movement only)
         pts_ct = pts.reshape(F, 7, 19, 2).transpose(0, 1).contiguous()
         out_conf[:, t0 : t0 + F] = conf.reshape(F, 7, 19).transpose(0, 1)

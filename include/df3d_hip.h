@@ -123,6 +123,13 @@ int df3d_heatmap_argmax(const float* hm_dev, int n, int joints, int h, int w, fl
  * The host reads the counter once per recording (deepfly3d_amd/inference.py) and refuses the result, naming the dtype to rerun with. */
 int df3d_heatmap_argmax_checked(const float* hm_dev, int n, int joints, int h, int w, float* pts_dev, float* conf_dev,
                                 int* nonfinite_planes_dev, void* stream);
+/* opt-in sub-pixel localisation (this project's own rule, restated in float64 by tests/subpixel_oracle.py and met
+ * bit for bit): df3d_heatmap_argmax_checked whose point is the winning cell moved by the maximum of the quadratic through its 3 x 3
+ * neighbourhood, at most half a cell per axis, evaluated in float64 and rounded once to float32.  A cell on the border of the plane, or
+ * with an infinity or a NaN among the nine values, keeps df3d_heatmap_argmax's point exactly.  The cell, conf_dev and the counter are
+ * those of df3d_heatmap_argmax_checked.  h and w must be powers of two. */
+int df3d_heatmap_argmax_subpixel(const float* hm_dev, int n, int joints, int h, int w, float* pts_dev, float* conf_dev,
+                                 int* nonfinite_planes_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * a4  19 -> 38 joint re-layout and un-flip.   Replaces reference df3d/core.py:187-203.
@@ -171,6 +178,11 @@ int df3d_triangulate_scaled(const double* P, const double* pts_norm_dev, double 
  * ---------------------------------------------------------------------------------------------- */
 int df3d_heatmap_peaks(const float* hm_dev, int n, int joints, int h, int w, int k, int* count_dev, float* pts_dev, float* val_dev,
                        void* stream);
+/* df3d_heatmap_peaks with every peak's point refined by the rule of df3d_heatmap_argmax_subpixel (the neighbours come from the plane
+ * in LDS): count, order and values are df3d_heatmap_peaks', and peak 0's point is df3d_heatmap_argmax_subpixel's bit for bit whenever
+ * the plane's maximum is finite. */
+int df3d_heatmap_peaks_subpixel(const float* hm_dev, int n, int joints, int h, int w, int k, int* count_dev, float* pts_dev,
+                                float* val_dev, void* stream);
 int df3d_ps_proposals(const double* P_host, const int* ordering_host, const double* X0_dev, const int* peak_count_dev,
                       const float* peak_pts_dev, const float* peak_val_dev, int T, int t0, int tn, int k, int m, double img_h,
                       double img_w, double tau, double w_reproj, double w_heatmap, int* kept_count_dev, int* kept_index_dev,
