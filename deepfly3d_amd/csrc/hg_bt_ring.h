@@ -86,6 +86,7 @@ __host__ __device__ constexpr int br_swz(int r, int c) { return (r >> 2) * 256 +
 // stages of one bottleneck's stream: W1 (CIN / 32) | W2 (36) | per 128-channel output half: W3 (4) and, with the 1x1 skip
 // convolution (DS: CIN != 256), Wd (CIN / 32)
 __host__ __device__ constexpr int br_nstage(int cin, bool ds) { return cin / 32 + BR_W2_STAGES + 2 * (4 + (ds ? cin / 32 : 0)); }
+constexpr size_t br_stream_bytes(int cin, bool ds) { return (size_t)br_nstage(cin, ds) * BR_STAGE_BYTES; }   // what bt_ring_pack_kernel writes
 
 // bf16 blob -> weight stream of one bottleneck.  One thread per 16-byte chunk: stages x 128 rows x 4 chunks.
 __global__ __launch_bounds__(256) void bt_ring_pack_kernel(const unsigned short* __restrict__ w1, const unsigned short* __restrict__ w2,

@@ -25,6 +25,7 @@ namespace hgk {
 
 constexpr int BRF_W1_STAGES = 8, BRF_W2_STAGES = 36, BRF_KH_STAGES = BRF_W1_STAGES + BRF_W2_STAGES, BRF_W3_STAGES = 16;
 constexpr int BRF_NSTAGE = 2 * BRF_KH_STAGES + BRF_W3_STAGES;   // 104
+constexpr size_t BRF_STREAM_BYTES = (size_t)BRF_NSTAGE * BR_STAGE_BYTES;   // what bt_ring_pack_f32_kernel writes
 
 // fp32 blob -> weight stream of one bottleneck.  One thread per 16-byte chunk (4 floats): 104 stages x 512 chunks.
 __global__ __launch_bounds__(256) void bt_ring_pack_f32_kernel(const float* __restrict__ w1, const float* __restrict__ w2,

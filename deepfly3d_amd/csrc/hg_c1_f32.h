@@ -32,6 +32,8 @@ struct Conv1Args {
 };
 
 constexpr int C1_NSTAGE = 16;
+constexpr size_t c1_stream_bytes(int cin) { return (size_t)(cin / 16) * BR_STAGE_BYTES; }   // what bt_c1_pack_f32_kernel writes: a stage per 16 input channels
+static_assert(c1_stream_bytes(256) == (size_t)C1_NSTAGE * BR_STAGE_BYTES, "the identity blocks' conv1 stream");
 #ifndef C1_ABLM
 #define C1_ABLM 0   // development builds: ablation mask (1 no MFMAs, 2 no weight DMA, 4 no x loads, 8 no t1 stores)
 #endif

@@ -7,6 +7,7 @@ namespace hgk {
 
 // bf16 blob -> Wfc stage stream: 8 K steps x 2 row halves, every stage the LDS image of 128 rows x 32 K (br_swz order)
 constexpr int HD_FC_STAGES = 16;
+constexpr size_t HD_FC_STREAM_BYTES = (size_t)HD_FC_STAGES * BR_STAGE_BYTES;
 __global__ __launch_bounds__(256) void bt_fc_pack_kernel(const unsigned short* __restrict__ wfc, unsigned char* __restrict__ stream) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= HD_FC_STAGES * 512) return;
@@ -18,6 +19,7 @@ __global__ __launch_bounds__(256) void bt_fc_pack_kernel(const unsigned short* _
 
 // float32 blob -> Wfc stage stream: 16 K steps (16 channels = 64 bytes) x 2 row halves, the same 128-row x 64-byte stage image
 constexpr int HD_FC_STAGES_F32 = 32;
+constexpr size_t HD_FC_STREAM_BYTES_F32 = (size_t)HD_FC_STAGES_F32 * BR_STAGE_BYTES;
 __global__ __launch_bounds__(256) void bt_fc_pack_f32_kernel(const float* __restrict__ wfc, unsigned char* __restrict__ stream) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= HD_FC_STAGES_F32 * 512) return;
@@ -59,6 +61,7 @@ struct HeadArgs {
 // bf16 blob -> phase-C stage stream: per 128-channel output half nh: Wfc_ rows 128 nh .. as 8 K slices of 32 (the host's K order),
 // then the same rows of Wsc_ (K = 32) -> 2 x 9 stages
 constexpr int HD_FC2_STAGES = 18;
+constexpr size_t HD_FC2_STREAM_BYTES = (size_t)HD_FC2_STAGES * BR_STAGE_BYTES;
 __global__ __launch_bounds__(256) void bt_fc2_pack_kernel(const unsigned short* __restrict__ wfc2, const unsigned short* __restrict__ wsc2,
                                                           unsigned char* __restrict__ stream) {
     const int idx = blockIdx.x * 256 + threadIdx.x;

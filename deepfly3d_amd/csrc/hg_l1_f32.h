@@ -21,6 +21,7 @@ namespace hgk {
 
 constexpr int L1F_W2_STAGES = 18, L1F_W3_STAGES = 4, L1F_WD_STAGES = 4;
 constexpr int L1F_NSTAGE = L1F_W2_STAGES + L1F_W3_STAGES + L1F_WD_STAGES;   // 26
+constexpr size_t L1F_STREAM_BYTES = (size_t)L1F_NSTAGE * BR_STAGE_BYTES;   // what bt_l1f_pack_kernel writes
 constexpr int L1F_LDS_BYTES = BR_RING_BYTES + BR_T1_BYTES + 128 * 4;        // ring | t1 halo tile (180 rows x 256 B) | b3 + bd
 
 // fp32 blob -> the tail's weight stream.  One thread per 16-byte chunk: 26 stages x 128 rows x 4 chunks.
@@ -281,6 +282,7 @@ __global__ __launch_bounds__(256, 2) void layer1_tail_f32_kernel(BtRingArgs p) {
 constexpr int L2F_W2_STAGES = 36;                       // per t1 half
 constexpr int L2F_NH_STAGES = 16;                       // per output half: 8 x W3, 8 x Wd
 constexpr int L2F_NSTAGE = 2 * L2F_W2_STAGES + 2 * L2F_NH_STAGES;   // 104
+constexpr size_t L2F_STREAM_BYTES = (size_t)L2F_NSTAGE * BR_STAGE_BYTES;   // what bt_l2f_pack_kernel writes
 constexpr int L2F_LDS_BYTES = BR_RING_BYTES + BR_T1_BYTES + 256 * 4;
 
 __global__ __launch_bounds__(256) void bt_l2f_pack_kernel(const float* __restrict__ w2, const float* __restrict__ w3, const float* __restrict__ wd,

@@ -208,46 +208,40 @@ class HourglassEngine:
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.dtype = dtype
         code = {"f32": _native.DF3D_DTYPE_F32, "bf16": _native.DF3D_DTYPE_BF16, "f16": _native.DF3D_DTYPE_F16, "f32s": _native.DF3D_DTYPE_F32S}[dtype]
-        fp32_storage = dtype in ("f32", "f32s")   # f32s: the f32 engine's plan, buffers and kernels with split products (include/df3d_hip.h)
         h = ctypes.c_void_p()
         _native.check(self.lib.df3d_hg_create(code, num_stacks, ctypes.byref(h)), "df3d_hg_create")
         self.h = h
         self.height, self.width = height, width
         _native.check(self.lib.df3d_hg_set_input(self.h, height, width), "df3d_hg_set_input")
-        if not fuse or os.environ.get("DF3D_FUSE") == "0":   # (DF3D_FUSE=0: developer switch, every convolution as a launch of its own)
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"fuse", 0), "df3d_hg_set_option")
-        if fuse_upadd is not None:  # default: the library's choice (on)
+        # The plan options, in the order they are set: (value, option key, environment override of a value left at None, the dtypes it applies to
+        # (None: all), conversion).  A value of None leaves the library's choice.
+        fp32_storage, lowp = ("f32", "f32s"), ("bf16", "f16")   # f32s: the f32 engine's plan, buffers and kernels with split products (include/df3d_hip.h)
+        flag = lambda v: 1 if v else 0   # noqa: E731
+        options = [
+            (None if fuse and os.environ.get("DF3D_FUSE") != "0" else 0, b"fuse", None, None, int),   # (DF3D_FUSE=0: developer switch, every convolution as a launch of its own)
             # True / 1: added in the epilogue of the bottleneck that produces the up-path tensor (default); 2: folded into the input load of
             # the consuming bottleneck (round 2's form); False / 0: a pass of its own
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"fuse_upadd", int(fuse_upadd)), "df3d_hg_set_option")
-        if ring is not None:  # default: the library's choice (LDS-DMA weight ring in the 256 -> 128 -> 128 -> 256 bottlenecks)
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"ring", 1 if ring else 0), "df3d_hg_set_option")
-        if l1 is not None:  # default: on (bf16): layer1 with LDS-resident weights, writing only the pooled tensor its consumer reads
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"l1", 1 if l1 else 0), "df3d_hg_set_option")
-        if row_bytes:
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"row_bytes", row_bytes), "df3d_hg_set_option")
-        if split1 is None and os.environ.get("DF3D_SPLIT1"):
-            split1 = int(os.environ["DF3D_SPLIT1"])
-        if split1 is not None and fp32_storage:  # fp32: conv1 of the identity-skip bottlenecks as a launch of its own (csrc/hg_c1_f32.h), bit-identical
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"split1", int(split1)), "df3d_hg_set_option")   # (0, 1, or 8 + mask: development)
-        if wino is None and os.environ.get("DF3D_WINO"):
-            wino = int(os.environ["DF3D_WINO"])
-        if wino is not None and dtype == "f32":  # exact fp32: the identity blocks' 3x3 as Winograd F(2x2, 3x3) (csrc/hg_bt_wino_f32.h); fp32 tolerance, not bit-identical to wino=0
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"wino", 1 if wino else 0), "df3d_hg_set_option")
-        if w2d is None and os.environ.get("DF3D_W2D"):
-            w2d = int(os.environ["DF3D_W2D"])
-        if w2d is not None and not fp32_storage:  # 16-bit: the 3x3's weights of the ring bottlenecks as direct per-wave fragment loads (csrc/hg_bt_ring.h), bit-identical
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"w2d", 1 if w2d else 0), "df3d_hg_set_option")
-        if ring2 is None and os.environ.get("DF3D_RING2"):
-            ring2 = int(os.environ["DF3D_RING2"])
-        if ring2 is not None and not fp32_storage:  # 16-bit: 1 (default) = round 4's ring bottleneck (csrc/hg_bt_ring.h MODE 2), 0 = round 3's; bit-identical
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"ring2", 1 if ring2 else 0), "df3d_hg_set_option")
-        if chain_views is None and os.environ.get("DF3D_CHAIN_VIEWS"):
-            chain_views = int(os.environ["DF3D_CHAIN_VIEWS"])
-        if chain_views is not None:  # chains of full-resolution steps in chunks of this many views (0 = whole batch per launch)
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"chain_views", int(chain_views)), "df3d_hg_set_option")
-        if no_reuse:  # tests: the alias-free workspace plan (every tensor keeps memory of its own)
-            _native.check(self.lib.df3d_hg_set_option(self.h, b"no_reuse", 1), "df3d_hg_set_option")
+            (fuse_upadd, b"fuse_upadd", None, None, int),
+            (ring, b"ring", None, None, flag),   # default on: LDS-DMA weight ring in the 256 -> 128 -> 128 -> 256 bottlenecks
+            (l1, b"l1", None, None, flag),   # default on (bf16): layer1 with LDS-resident weights, writing only the pooled tensor its consumer reads
+            (row_bytes or None, b"row_bytes", None, None, int),
+            # fp32: conv1 of the identity-skip bottlenecks as a launch of its own (csrc/hg_c1_f32.h), bit-identical (0, 1, or 8 + mask: development)
+            (split1, b"split1", "DF3D_SPLIT1", fp32_storage, int),
+            # exact fp32: the identity blocks' 3x3 as Winograd F(2x2, 3x3) (csrc/hg_bt_wino_f32.h); fp32 tolerance, not bit-identical to wino=0
+            (wino, b"wino", "DF3D_WINO", ("f32",), flag),
+            # 16-bit: the 3x3's weights of the ring bottlenecks as direct per-wave fragment loads (csrc/hg_bt_ring.h), bit-identical
+            (w2d, b"w2d", "DF3D_W2D", lowp, flag),
+            # 16-bit: 1 (default) = round 4's ring bottleneck (csrc/hg_bt_ring.h MODE 2), 0 = round 3's; bit-identical
+            (ring2, b"ring2", "DF3D_RING2", lowp, flag),
+            # chains of full-resolution steps in chunks of this many views (0 = whole batch per launch)
+            (chain_views, b"chain_views", "DF3D_CHAIN_VIEWS", None, int),
+            (1 if no_reuse else None, b"no_reuse", None, None, int),   # tests: the alias-free workspace plan (every tensor keeps memory of its own)
+        ]
+        for value, key, env, dtypes, convert in options:
+            if value is None and env and os.environ.get(env):
+                value = int(os.environ[env])
+            if value is not None and (dtypes is None or dtype in dtypes):
+                _native.check(self.lib.df3d_hg_set_option(self.h, key, convert(value)), "df3d_hg_set_option")
         if strict is None:   # DF3D_CHECKPOINT_STRICT=0: the non-strict load (e.g. the first N stacks of a checkpoint trained with more)
             strict = os.environ.get("DF3D_CHECKPOINT_STRICT", "1") not in ("0", "false", "no")
         blob = pack_state_dict(self.h, state_dict, strict=strict)
