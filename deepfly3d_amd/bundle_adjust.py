@@ -216,71 +216,44 @@ def _solve_trust_region_2d(B, g, Delta):
     return p[:, np.argmin(value)]
 
 
-def solve_trf(prob, x0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, lsmr_form=_native.LSMR_AUTO, device_scalars=None):
-    """Trust-region-reflective least squares without bounds, LSMR subspace step, x_scale='jac'.
-    x0: device float64 [n].  Returns dict(x=device tensor, cost, nfev, njev, status, lsmr_iters, optimality).
-    lsmr_form: DF3D_LSMR_* of include/df3d_hip.h (AUTO: one persistent data-local kernel per inner solve; LAUNCHES when the adjustment
-    runs beside other work on the device).
-    device_scalars (default True; DF3D_TRF_HOST_SCALARS=1 in the environment turns it off): the driver's scalars stay on the device -- one
-    read-back per outer iteration and one per trial step (df3d_ba_trf_* of include/df3d_hip.h) instead of seven and one; the same
-    arithmetic, the same iterates (tests/test_gpu_ba.py compares the two)."""
-    if device_scalars is None:
-        device_scalars = os.environ.get("DF3D_TRF_HOST_SCALARS", "0") in ("", "0")
-    if device_scalars:
-        return _solve_trf_device_scalars(prob, x0, ftol, xtol, gtol, max_nfev, lsmr_form)
-    dv = _Dev(prob)
-    m, n, nobs = prob.m, prob.n, prob.nobs
-    x = x0.clone()
-    f = dv.new(m)
-    f_new = dv.new(m)
-    Jc = dv.new(12 * nobs)
-    Jp = dv.new(6 * nobs)
-    g = dv.new(n)
-    g_h = dv.new(n)
-    gn_h = dv.new(n)
-    scale = dv.new(n)
-    scale_inv = dv.new(n)
-    tmp_n = dv.new(n)
-    tmp_n2 = dv.new(n)
-    s0 = dv.new(n)
-    s1 = dv.new(n)
-    step_h = dv.new(n)
-    x_new = dv.new(n)
-    Js0 = dv.new(m)
-    Js1 = dv.new(m)
-    tmp_m = dv.new(m)
-    work = dv.new(dv.lib.df3d_ba_lsmr_work_doubles(ctypes.byref(prob.c)))
+class _HostScalars:
+    """solve_trf's back end whose scalars come back to the host in groups: every step is one of _Dev's vector calls, seven read-backs per
+    outer iteration and one per trial step."""
 
-    def refresh_scale(first):
-        dv.colsq(Jc, Jp, tmp_n)
-        _native.check(dv.lib.df3d_ba_update_scale(tmp_n.data_ptr(), scale_inv.data_ptr(), scale.data_ptr(), n, 1 if first else 0, dv.stream()), "df3d_ba_update_scale")
+    def __init__(self, dv, prob, lsmr_form):
+        self.dv, self.prob, self.form = dv, prob, lsmr_form
+        m, n, nobs = prob.m, prob.n, prob.nobs
+        self.f, self.f_new, self.Js0, self.Js1, self.tmp_m = (dv.new(m) for _ in range(5))
+        self.Jc, self.Jp = dv.new(12 * nobs), dv.new(6 * nobs)
+        self.g, self.g_h, self.gn_h, self.scale, self.scale_inv, self.tmp_n, self.step, self.s0, self.s1, self.step_h, self.x_new = (dv.new(n) for _ in range(11))
+        self.work = dv.new(dv.lib.df3d_ba_lsmr_work_doubles(ctypes.byref(prob.c)))
 
-    dv.eval(x, f, Jc, Jp)
-    nfev = njev = 1
-    cost = 0.5 * dv.dot(f, f)
-    dv.rmatvec(Jc, Jp, None, f, g)
-    refresh_scale(True)
-    dv.mul(x, scale_inv, tmp_n)
-    Delta = dv.norm(tmp_n)
-    if Delta == 0:
-        Delta = 1.0
-    if max_nfev is None:
-        max_nfev = n * 100
-    status = None
-    lsmr_iters = []
-    lsmr_fallbacks = 0
-    g_norm = None
-    while True:
-        g_norm = dv.absmax(g)
+    def linearize(self, x, f, first):
+        """J, g = J^T f and the column scaling at x (and f, on the first call, which returns |f|^2 and |x / scale|^2)."""
+        dv, Jc, Jp = self.dv, self.Jc, self.Jp
+        if first:
+            dv.eval(x, f, Jc, Jp)
+            ff = dv.dot(f, f)
+        else:
+            dv.eval(x, None, Jc, Jp)
+        dv.rmatvec(Jc, Jp, None, f, self.g)
+        dv.colsq(Jc, Jp, self.tmp_n)
+        _native.check(dv.lib.df3d_ba_update_scale(self.tmp_n.data_ptr(), self.scale_inv.data_ptr(), self.scale.data_ptr(), self.prob.n, 1 if first else 0, dv.stream()),
+                      "df3d_ba_update_scale")
+        if first:
+            dv.mul(x, self.scale_inv, self.tmp_n)
+            return ff, dv.dot(self.tmp_n, self.tmp_n)
+
+    def subspace(self, f, Delta, gtol):
+        """|g|_inf and, unless it is below gtol, the 2-D model on span(g_h, LSMR step): (|g|_inf, B_S, g_S, LSMR info)."""
+        dv, Jc, Jp, d, g_h, gn_h, s0, s1, Js0, Js1, tmp_m = self.dv, self.Jc, self.Jp, self.scale, self.g_h, self.gn_h, self.s0, self.s1, self.Js0, self.Js1, self.tmp_m
+        g_norm = dv.absmax(self.g)
         if g_norm < gtol:
-            status = 1
-        if status is not None or nfev == max_nfev:
-            break
-        d = scale
-        dv.mul(d, g, g_h)
+            return g_norm, None, None, None
+        dv.mul(d, self.g, g_h)
         # Tikhonov term from the 1-D Cauchy model along -g_h
         dv.matvec(Jc, Jp, d, g_h, tmp_m)
-        jg2, gh2 = dv.dots((tmp_m, tmp_m), (g_h, g_h))   # (round 4: the driver's scalars come back in groups, one read-back each)
+        jg2, gh2 = dv.dots((tmp_m, tmp_m), (g_h, g_h))
         a = 0.5 * jg2
         b = -gh2
         to_tr = Delta / np.sqrt(gh2)
@@ -293,9 +266,7 @@ def solve_trf(prob, x0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, lsmr_for
         ag_value = np.min(cand * (a * cand + b))
         reg_term = -ag_value / Delta**2
         damp = float(np.sqrt(reg_term))
-        info = dv.lsmr(Jc, Jp, d, f, damp, gn_h, work, form=lsmr_form)
-        lsmr_iters.append(int(info[1]))
-        lsmr_fallbacks += int(info[7]) != 0
+        info = dv.lsmr(Jc, Jp, d, f, damp, gn_h, self.work, form=self.form)
         # orthonormal basis S = qr([g_h, gn_h]) (Householder sign convention of LAPACK: R diagonal < 0)
         n0 = np.sqrt(gh2)
         dv.axpby(-1.0 / n0, g_h, 0.0, None, s0)
@@ -306,122 +277,100 @@ def solve_trf(prob, x0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, lsmr_for
         dv.matvec(Jc, Jp, d, s0, Js0)
         dv.matvec(Jc, Jp, d, s1, Js1)
         b00, b01, b11, gs0, gs1 = dv.dots((Js0, Js0), (Js0, Js1), (Js1, Js1), (s0, g_h), (s1, g_h))
-        B_S = np.array([[b00, b01], [b01, b11]])
-        g_S = np.array([gs0, gs1])
-        actual_reduction = -1.0
-        cost_new = cost
-        while actual_reduction <= 0 and nfev < max_nfev:
-            p_S = _solve_trust_region_2d(B_S, g_S, Delta)
-            dv.axpby(float(p_S[0]), s0, float(p_S[1]), s1, step_h)
-            # predicted reduction = -(0.5 |J_h step|^2 + step . g_h), with J_h step = p0 Js0 + p1 Js1
-            dv.axpby(float(p_S[0]), Js0, float(p_S[1]), Js1, tmp_m)
-            dv.mul(d, step_h, tmp_n2)  # step
-            dv.axpby(1.0, x, 1.0, tmp_n2, x_new)
-            dv.eval(x_new, f_new, None, None)
-            nfev += 1
-            jp2, sg, sh2, ff, st2, xx = dv.dots((tmp_m, tmp_m), (step_h, g_h), (step_h, step_h), (f_new, f_new), (tmp_n2, tmp_n2), (x, x))
-            predicted_reduction = -(0.5 * jp2 + sg)
-            step_h_norm = float(np.sqrt(sh2))
-            cost_new = 0.5 * ff
-            if not np.isfinite(cost_new):
-                Delta = 0.25 * step_h_norm
-                continue
-            actual_reduction = cost - cost_new
-            if predicted_reduction > 0:
-                ratio = actual_reduction / predicted_reduction
-            elif predicted_reduction == actual_reduction == 0:
-                ratio = 1
-            else:
-                ratio = 0
-            Delta_new = Delta
-            if ratio < 0.25:
-                Delta_new = 0.25 * step_h_norm
-            elif ratio > 0.75 and step_h_norm > 0.95 * Delta:
-                Delta_new = 2.0 * Delta
-            step_norm = float(np.sqrt(st2))
-            ftol_ok = actual_reduction < ftol * cost and ratio > 0.25
-            xtol_ok = step_norm < xtol * (xtol + float(np.sqrt(xx)))
-            if ftol_ok and xtol_ok:
-                status = 4
-            elif ftol_ok:
-                status = 2
-            elif xtol_ok:
-                status = 3
-            if status is not None:
-                break
-            Delta = Delta_new
-        if actual_reduction > 0:
-            x, x_new = x_new, x
-            f, f_new = f_new, f
-            cost = cost_new
-            dv.eval(x, None, Jc, Jp)
-            njev += 1
-            dv.rmatvec(Jc, Jp, None, f, g)
-            refresh_scale(False)
-    if status is None:
-        status = 0
-    return dict(x=x, cost=cost, nfev=nfev, njev=njev, status=status, lsmr_iters=lsmr_iters, optimality=g_norm, lsmr_fallbacks=lsmr_fallbacks)
+        return g_norm, np.array([[b00, b01], [b01, b11]]), np.array([gs0, gs1]), info
+
+    def trial(self, p_S, x, x_new, f_new):
+        """x_new = x + D (p0 s0 + p1 s1), f_new = f(x_new); returns |J_h step|^2, step_h . g_h, |step_h|^2, |f_new|^2, |step|^2, |x|^2."""
+        dv, step_h, tmp_m, step = self.dv, self.step_h, self.tmp_m, self.step
+        dv.axpby(float(p_S[0]), self.s0, float(p_S[1]), self.s1, step_h)
+        dv.axpby(float(p_S[0]), self.Js0, float(p_S[1]), self.Js1, tmp_m)   # J_h step = p0 J_h s0 + p1 J_h s1
+        dv.mul(self.scale, step_h, step)
+        dv.axpby(1.0, x, 1.0, step, x_new)
+        dv.eval(x_new, f_new, None, None)
+        return dv.dots((tmp_m, tmp_m), (step_h, self.g_h), (step_h, step_h), (f_new, f_new), (step, step), (x, x))
 
 
-def _solve_trf_device_scalars(prob, x0, ftol, xtol, gtol, max_nfev, lsmr_form):
-    """solve_trf with the scalars of an outer iteration left on the device (see there): the host keeps the trust radius, the 2x2
+class _DeviceScalars(_HostScalars):
+    """solve_trf's back end whose scalars stay on the device (df3d_ba_trf_* of include/df3d_hip.h): one read-back per outer iteration and
+    one per trial step; the LSMR damping is read from device memory.  Same buffers, same arithmetic."""
+
+    def __init__(self, dv, prob, lsmr_form):
+        super().__init__(dv, prob, lsmr_form)
+        self.P = ctypes.byref(prob.c)
+        self.sub = (ctypes.c_double * 19)()
+        self.tri = (ctypes.c_double * 6)()
+
+    def linearize(self, x, f, first):
+        dv = self.dv
+        _native.check(dv.lib.df3d_ba_trf_linearize(self.P, x.data_ptr(), f.data_ptr(), 1 if first else 0, self.Jc.data_ptr(), self.Jp.data_ptr(), self.g.data_ptr(),
+                                                   self.tmp_n.data_ptr(), self.scale_inv.data_ptr(), self.scale.data_ptr(), 1 if first else 0, dv.scratch.data_ptr(),
+                                                   dv.stream()), "df3d_ba_trf_linearize")
+        if first:
+            dv.mul(x, self.scale_inv, self.tmp_n)
+            return dv.dots((f, f), (self.tmp_n, self.tmp_n))
+
+    def subspace(self, f, Delta, gtol):
+        dv, sub = self.dv, self.sub
+        _native.check(dv.lib.df3d_ba_trf_subspace(self.P, self.Jc.data_ptr(), self.Jp.data_ptr(), self.scale.data_ptr(), self.g.data_ptr(), f.data_ptr(), Delta,
+                                                  self.g_h.data_ptr(), self.gn_h.data_ptr(), self.s0.data_ptr(), self.s1.data_ptr(), self.Js0.data_ptr(),
+                                                  self.Js1.data_ptr(), self.tmp_m.data_ptr(), self.work.data_ptr(), dv.scratch.data_ptr(), sub, dv.stream(), self.form),
+                      "df3d_ba_trf_subspace")
+        # (when |g|_inf is below gtol, what was enqueued behind it is not looked at)
+        return sub[0], np.array([[sub[6], sub[7]], [sub[7], sub[8]]]), np.array([sub[9], sub[10]]), list(sub[11:19])
+
+    def trial(self, p_S, x, x_new, f_new):
+        dv = self.dv
+        _native.check(dv.lib.df3d_ba_trf_trial(self.P, float(p_S[0]), float(p_S[1]), self.s0.data_ptr(), self.s1.data_ptr(), self.Js0.data_ptr(), self.Js1.data_ptr(),
+                                               self.scale.data_ptr(), x.data_ptr(), self.g_h.data_ptr(), self.step_h.data_ptr(), self.tmp_m.data_ptr(),
+                                               self.step.data_ptr(), x_new.data_ptr(), f_new.data_ptr(), dv.scratch.data_ptr(), self.tri, dv.stream()),
+                      "df3d_ba_trf_trial")
+        return list(self.tri)
+
+
+def solve_trf(prob, x0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, lsmr_form=_native.LSMR_AUTO, device_scalars=None):
+    """Trust-region-reflective least squares without bounds, LSMR subspace step, x_scale='jac'.
+    x0: device float64 [n].  Returns dict(x=device tensor, cost, nfev, njev, status, lsmr_iters, optimality).
+    lsmr_form: DF3D_LSMR_* of include/df3d_hip.h (AUTO: one persistent data-local kernel per inner solve; LAUNCHES when the adjustment
+    runs beside other work on the device).
+    device_scalars (default True; DF3D_TRF_HOST_SCALARS=1 in the environment turns it off): the driver's scalars stay on the device -- one
+    read-back per outer iteration and one per trial step (df3d_ba_trf_* of include/df3d_hip.h) instead of seven and one; the same
+    arithmetic, the same iterates (tests/test_gpu_ba.py compares the two).  Either way the host keeps the trust radius, the 2x2
     subproblem and the acceptance logic -- everything that decides what is enqueued next."""
+    if device_scalars is None:
+        device_scalars = os.environ.get("DF3D_TRF_HOST_SCALARS", "0") in ("", "0")
     dv = _Dev(prob)
-    lib, P, st = dv.lib, ctypes.byref(prob.c), dv.stream()
-    m, n, nobs = prob.m, prob.n, prob.nobs
-    x = x0.clone()
-    f, f_new, Js0, Js1, tmp_m = (dv.new(m) for _ in range(5))
-    Jc, Jp = dv.new(12 * nobs), dv.new(6 * nobs)
-    g, g_h, gn_h, scale, scale_inv, tmp_n, step, s0, s1, step_h, x_new = (dv.new(n) for _ in range(11))
-    work = dv.new(lib.df3d_ba_lsmr_work_doubles(P))
-    scratch = dv.scratch
-
-    def linearize(xv, fv, eval_f, first):
-        _native.check(lib.df3d_ba_trf_linearize(P, xv.data_ptr(), fv.data_ptr(), 1 if eval_f else 0, Jc.data_ptr(), Jp.data_ptr(), g.data_ptr(), tmp_n.data_ptr(),
-                                                scale_inv.data_ptr(), scale.data_ptr(), 1 if first else 0, scratch.data_ptr(), st), "df3d_ba_trf_linearize")
-
-    linearize(x, f, True, True)
+    be = (_DeviceScalars if device_scalars else _HostScalars)(dv, prob, lsmr_form)
+    x, x_new, f, f_new = x0.clone(), be.x_new, be.f, be.f_new
+    ff0, d2 = be.linearize(x, f, True)
     nfev = njev = 1
-    dv.mul(x, scale_inv, tmp_n)
-    ff0, d2 = dv.dots((f, f), (tmp_n, tmp_n))
     cost = 0.5 * ff0
     Delta = float(np.sqrt(d2))
     if Delta == 0:
         Delta = 1.0
     if max_nfev is None:
-        max_nfev = n * 100
+        max_nfev = prob.n * 100
     status = None
     lsmr_iters = []
     lsmr_fallbacks = 0
-    g_norm = None
-    sub = (ctypes.c_double * 19)()
-    tri = (ctypes.c_double * 6)()
     while True:
         if status is not None or nfev == max_nfev:
-            g_norm = dv.absmax(g)
+            g_norm = dv.absmax(be.g)
             if g_norm < gtol:
                 status = 1
             break
-        _native.check(lib.df3d_ba_trf_subspace(P, Jc.data_ptr(), Jp.data_ptr(), scale.data_ptr(), g.data_ptr(), f.data_ptr(), Delta, g_h.data_ptr(), gn_h.data_ptr(),
-                                               s0.data_ptr(), s1.data_ptr(), Js0.data_ptr(), Js1.data_ptr(), tmp_m.data_ptr(), work.data_ptr(), scratch.data_ptr(),
-                                               sub, st, lsmr_form), "df3d_ba_trf_subspace")
-        g_norm = sub[0]
-        if g_norm < gtol:   # (what was enqueued behind |g|_inf is not looked at)
+        g_norm, B_S, g_S, info = be.subspace(f, Delta, gtol)
+        if g_norm < gtol:
             status = 1
             break
-        lsmr_iters.append(int(sub[12]))
-        lsmr_fallbacks += int(sub[18]) != 0
-        B_S = np.array([[sub[6], sub[7]], [sub[7], sub[8]]])
-        g_S = np.array([sub[9], sub[10]])
+        lsmr_iters.append(int(info[1]))
+        lsmr_fallbacks += int(info[7]) != 0
         actual_reduction = -1.0
         cost_new = cost
         while actual_reduction <= 0 and nfev < max_nfev:
             p_S = _solve_trust_region_2d(B_S, g_S, Delta)
-            _native.check(lib.df3d_ba_trf_trial(P, float(p_S[0]), float(p_S[1]), s0.data_ptr(), s1.data_ptr(), Js0.data_ptr(), Js1.data_ptr(), scale.data_ptr(),
-                                                x.data_ptr(), g_h.data_ptr(), step_h.data_ptr(), tmp_m.data_ptr(), step.data_ptr(), x_new.data_ptr(), f_new.data_ptr(),
-                                                scratch.data_ptr(), tri, st), "df3d_ba_trf_trial")
+            # predicted reduction = -(0.5 |J_h step|^2 + step . g_h)
+            jp2, sg, sh2, ff, st2, xx = be.trial(p_S, x, x_new, f_new)
             nfev += 1
-            jp2, sg, sh2, ff, st2, xx = tri
             predicted_reduction = -(0.5 * jp2 + sg)
             step_h_norm = float(np.sqrt(sh2))
             cost_new = 0.5 * ff
@@ -456,7 +405,7 @@ def _solve_trf_device_scalars(prob, x0, ftol, xtol, gtol, max_nfev, lsmr_form):
             x, x_new = x_new, x
             f, f_new = f_new, f
             cost = cost_new
-            linearize(x, f, False, False)
+            be.linearize(x, f, False)
             njev += 1
     if status is None:
         status = 0

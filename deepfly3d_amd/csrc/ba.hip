@@ -8,8 +8,8 @@
 //                        (camera, chunk) workgroup reduces its slice in a fixed order, a second kernel sums the
 //                        DF3D chunks in order -> bit-reproducible (no floating-point atomics).
 //   * df3d_ba_lsmr       Fong & Saunders LSMR on A = J diag(d) with damping, the inner solver of scipy's
-//                        trust-region-reflective step (oracle/trf_lsmr.py:lsmr).  Vectors stay on the device;
-//                        three scalars (beta, alpha, |x|) come back to the host per iteration.
+//                        trust-region-reflective step (oracle/trf_lsmr.py:lsmr).  Vectors and the recurrence's scalars stay on
+//                        the device (ba_lsmr.h: State, and Work for the layout of the work buffer).
 // All kernels are latency/launch-bound at the reference's sizes (1e5 observations): ~15 MB per Jacobian pass.
 #include <algorithm>
 #include <cmath>
@@ -22,7 +22,7 @@ namespace {
 
 constexpr int MAX_CAM = 8;
 constexpr int NCHUNK = 32;      // chunks per camera in the J^T u / column-norm reductions
-constexpr int RED_BLOCKS = 256;  // partial blocks of the generic sum-of-squares / dot reductions
+using df3d_lsmr::RED_BLOCKS;     // partial blocks of the generic sum-of-squares / dot reductions
 
 struct CamLds {
     double R[MAX_CAM][9];
@@ -322,26 +322,6 @@ __global__ __launch_bounds__(256) void mul_kernel(const double* x, const double*
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = x[i] * y[i];
 }
 
-// LSMR vector update:  hbar = h - c1*hbar ; x += c2*hbar ; h = v - c3*h ; partial sum(x^2)
-__global__ __launch_bounds__(256) void lsmr_update_kernel(double c1, double c2, double c3, double* __restrict__ hbar,
-                                                          double* __restrict__ h, double* __restrict__ x,
-                                                          const double* __restrict__ v, size_t n,
-                                                          double* __restrict__ partial) {
-    __shared__ double lds4[4];
-    double acc = 0.0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const double hi = h[i];
-        const double hb = hi - c1 * hbar[i];
-        const double xi = x[i] + c2 * hb;
-        hbar[i] = hb;
-        x[i] = xi;
-        h[i] = v[i] - c3 * hi;
-        acc += xi * xi;
-    }
-    const double tot = block_reduce_256(acc, lds4);
-    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-}
-
 // x_scale='jac' bookkeeping: scale_inv = sqrt(colsq) (zeros -> 1 on the first call, running max later)
 __global__ __launch_bounds__(256) void update_scale_kernel(const double* __restrict__ colsq, double* __restrict__ scale_inv,
                                                            double* __restrict__ scale, size_t n, int first) {
@@ -423,6 +403,14 @@ inline int grid_for(size_t n) {
     return (int)(b < 1 ? 1 : (b > RED_BLOCKS ? RED_BLOCKS : b));
 }
 
+// ---- the places in scratch_dev (DF3D_BA_SCRATCH_DOUBLES doubles) -----------------------------------------------------------------------
+// [0, MAX_DOTS * RED_BLOCKS): partial sums -- of J^T u per (camera, chunk, column), of one reduction, or of up to MAX_DOTS dot products
+constexpr int MAX_DOTS = 8;
+constexpr int SCRATCH_RESULT = RED_BLOCKS;                  // the finished sum of a single reduction (behind its partials)
+constexpr int SCRATCH_DOTS_RESULT = MAX_DOTS * RED_BLOCKS;  // the MAX_DOTS finished sums of a batch of dot products
+constexpr int TR_OFFSET = SCRATCH_DOTS_RESULT + 16;         // the trust-region driver's block of scalars (TR_* below)
+static_assert(MAX_CAM * NCHUNK * 6 <= df3d_lsmr::CAM_PARTIAL_DOUBLES && df3d_lsmr::CAM_PARTIAL_DOUBLES <= SCRATCH_DOTS_RESULT, "camera partials");
+
 int check_problem(const df3d_ba_problem* p) {
     DF3D_CHECK_ARG(p != nullptr, "null problem");
     DF3D_CHECK_ARG(p->ncam >= 1 && p->ncam <= MAX_CAM, "ncam must be in [1, 8]");
@@ -456,27 +444,21 @@ int launch_matvec(const df3d_ba_problem* p, const double* Jc, const double* Jp, 
     return DF3D_OK;
 }
 
-void sym_ortho(double a, double b, double& c, double& s, double& r) {
-    auto sgn = [](double v) { return (v > 0) - (v < 0); };
-    if (b == 0) {
-        c = sgn(a);
-        s = 0;
-        r = std::fabs(a);
-    } else if (a == 0) {
-        c = 0;
-        s = sgn(b);
-        r = std::fabs(b);
-    } else if (std::fabs(b) > std::fabs(a)) {
-        const double tau = a / b;
-        s = sgn(b) / std::sqrt(1 + tau * tau);
-        c = s * tau;
-        r = b / s;
-    } else {
-        const double tau = b / a;
-        c = sgn(a) / std::sqrt(1 + tau * tau);
-        s = c * tau;
-        r = a / c;
+// `count` dot products in one launch, each with dot_kernel's grid and summation order: partials in scratch, sums in result[0 .. count)
+int enqueue_dots(int count, const double* const* a, const double* const* b, const size_t* n, double* scratch, double* result, hipStream_t s) {
+    DotBatch q{};
+    int gmax = 1;
+    for (int j = 0; j < count; ++j) {
+        q.a[j] = a[j];
+        q.b[j] = b[j];
+        q.n[j] = n[j];
+        q.g[j] = grid_for(n[j]);
+        gmax = q.g[j] > gmax ? q.g[j] : gmax;
     }
+    hipLaunchKernelGGL(dots_kernel, dim3(gmax, count), dim3(256), 0, s, q, scratch);
+    hipLaunchKernelGGL(dots_final_kernel, dim3(count), dim3(256), 0, s, q, scratch, result);
+    DF3D_LAUNCH_CHECK();
+    return DF3D_OK;
 }
 
 }  // namespace
@@ -528,29 +510,18 @@ int df3d_vec_dot(const double* a_dev, const double* b_dev, size_t n, double* res
     hipStream_t s = df3d::as_stream(stream);
     const int g = grid_for(n);
     hipLaunchKernelGGL(dot_kernel, dim3(g), dim3(256), 0, s, a_dev, b_dev, n, scratch_dev);
-    hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, scratch_dev, g, scratch_dev + RED_BLOCKS);
+    hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, scratch_dev, g, scratch_dev + SCRATCH_RESULT);
     DF3D_LAUNCH_CHECK();
-    return read_back(scratch_dev + RED_BLOCKS, result_host, s);
+    return read_back(scratch_dev + SCRATCH_RESULT, result_host, s);
 }
 
 int df3d_vec_dots(int count, const double* const* a_dev, const double* const* b_dev, const size_t* n, double* results_host, double* scratch_dev,
                   void* stream) {
     DF3D_CHECK_ARG(count >= 1 && count <= 8 && a_dev && b_dev && n && results_host && scratch_dev, "1..8 products, no null pointer");
+    for (int j = 0; j < count; ++j) DF3D_CHECK_ARG(a_dev[j] && b_dev[j], "null vector");
     hipStream_t s = df3d::as_stream(stream);
-    DotBatch q{};
-    int gmax = 1;
-    for (int j = 0; j < count; ++j) {
-        DF3D_CHECK_ARG(a_dev[j] && b_dev[j], "null vector");
-        q.a[j] = a_dev[j];
-        q.b[j] = b_dev[j];
-        q.n[j] = n[j];
-        q.g[j] = grid_for(n[j]);
-        gmax = q.g[j] > gmax ? q.g[j] : gmax;
-    }
-    double* const result = scratch_dev + 8 * RED_BLOCKS;
-    hipLaunchKernelGGL(dots_kernel, dim3(gmax, count), dim3(256), 0, s, q, scratch_dev);
-    hipLaunchKernelGGL(dots_final_kernel, dim3(count), dim3(256), 0, s, q, scratch_dev, result);
-    DF3D_LAUNCH_CHECK();
+    double* const result = scratch_dev + SCRATCH_DOTS_RESULT;
+    if (int rc = enqueue_dots(count, a_dev, b_dev, n, scratch_dev, result, s)) return rc;
     DF3D_HIP(hipMemcpyAsync(results_host, result, count * sizeof(double), hipMemcpyDeviceToHost, s));
     DF3D_HIP(hipStreamSynchronize(s));
     return DF3D_OK;
@@ -561,9 +532,9 @@ int df3d_vec_pairnorm_sum(const double* r_dev, size_t npairs, double* result_hos
     hipStream_t s = df3d::as_stream(stream);
     const int g = grid_for(npairs);
     hipLaunchKernelGGL(pairnorm_kernel, dim3(g), dim3(256), 0, s, r_dev, npairs, scratch_dev);
-    hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, scratch_dev, g, scratch_dev + RED_BLOCKS);
+    hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, scratch_dev, g, scratch_dev + SCRATCH_RESULT);
     DF3D_LAUNCH_CHECK();
-    return read_back(scratch_dev + RED_BLOCKS, result_host, s);
+    return read_back(scratch_dev + SCRATCH_RESULT, result_host, s);
 }
 
 int df3d_vec_axpby(double a, const double* x_dev, double b, const double* y_dev, double* out_dev, size_t n,
@@ -587,9 +558,9 @@ int df3d_vec_absmax(const double* a_dev, size_t n, double* result_host, double* 
     hipStream_t s = df3d::as_stream(stream);
     const int g = grid_for(n);
     hipLaunchKernelGGL(absmax_kernel, dim3(g), dim3(256), 0, s, a_dev, n, scratch_dev);
-    hipLaunchKernelGGL(absmax_kernel, dim3(1), dim3(256), 0, s, scratch_dev, (size_t)g, scratch_dev + RED_BLOCKS);
+    hipLaunchKernelGGL(absmax_kernel, dim3(1), dim3(256), 0, s, scratch_dev, (size_t)g, scratch_dev + SCRATCH_RESULT);
     DF3D_LAUNCH_CHECK();
-    return read_back(scratch_dev + RED_BLOCKS, result_host, s);
+    return read_back(scratch_dev + SCRATCH_RESULT, result_host, s);
 }
 
 int df3d_ba_update_scale(const double* colsq_dev, double* scale_inv_dev, double* scale_dev, size_t n, int first,
@@ -603,89 +574,98 @@ int df3d_ba_update_scale(const double* colsq_dev, double* scale_inv_dev, double*
 
 size_t df3d_ba_lsmr_work_doubles(const df3d_ba_problem* p) {
     if (!p) return 0;
-    const size_t m = 2 * (size_t)p->nobs, n = 6 * (size_t)p->ncam + 3 * (size_t)p->npts;
-    // u, tmp_m (m each); v, h, hbar, tmp_n (n each); scratch; round 4 (fused iteration): two state slots, |u|^2 / |x|^2 partials, |v|^2 partials
-    // round 5 (persistent run): 8 doubles for the grid barrier's two words
-    //          + the data-local form's ranges, granules and state
-    return 2 * m + 4 * n + DF3D_BA_SCRATCH_DOUBLES + 64 + 2 * df3d_lsmr::FUSED_DOUBLES + 3 * df3d_lsmr::FUSED_RED + 8 + (df3d_lsmr::local_scratch_bytes() + 7) / 8 + 64;
+    return df3d_lsmr::Work(nullptr, 2 * (size_t)p->nobs, 6 * (size_t)p->ncam + 3 * (size_t)p->npts).doubles;
 }
 
 }  // extern "C"
 
+// ---- LSMR: one run in one of four forms (DF3D_LSMR_* of include/df3d_hip.h) --------------------------------------------------------------
 namespace {
-// form: 0 = one persistent kernel per run (round 5, the default), 2 = two kernels per iteration (round 4), 11 = round 3's eleven
-int lsmr_run(const df3d_ba_problem* p, const double* Jc, const double* Jp, const double* d_dev,
-             const double* b_dev, double damp, double atol, double btol, double conlim, int maxiter,
-             double* x_dev, double* work_dev, double* info_host, void* stream, int form) {
-    if (int rc = check_problem(p)) return rc;
-    DF3D_CHECK_ARG(Jc && Jp && b_dev && x_dev && work_dev && info_host, "null pointer");
-    hipStream_t s = df3d::as_stream(stream);
-    const size_t m = 2 * (size_t)p->nobs, n = 6 * (size_t)p->ncam + 3 * (size_t)p->npts;
-    if (maxiter <= 0) maxiter = (int)(m < n ? m : n);
-    if (form == 3) {
-        // round 5: the data-local run (ba_lsmr.hip: lsmr_local_kernel) -- the whole solve, its set-up included, in ONE launch and ONE read-back
-        double* const lscratch = work_dev + (2 * m + 4 * n + DF3D_BA_SCRATCH_DOUBLES + 64 + 2 * df3d_lsmr::FUSED_DOUBLES + 3 * df3d_lsmr::FUSED_RED + 8);
-        double* const lstate = lscratch + (df3d_lsmr::local_scratch_bytes() + 7) / 8;
-        const int rc = df3d_lsmr::launch_local(*p, Jc, Jp, d_dev, b_dev, x_dev, damp, atol, btol, conlim > 0 ? 1.0 / conlim : 0.0, maxiter, lscratch, lstate, s);
-        if (rc < 0) {
-            info_host[0] = -2;   // does not fit this form: the caller takes another
-            return DF3D_OK;
-        }
-        DF3D_LAUNCH_CHECK();
-        df3d_lsmr::State now{};
-        DF3D_HIP(hipMemcpyAsync(&now, lstate, sizeof(now), hipMemcpyDeviceToHost, s));
-        DF3D_HIP(hipStreamSynchronize(s));
-        info_host[0] = now.istop;
-        info_host[1] = now.itn;
-        info_host[2] = now.normr;
-        info_host[3] = now.normar;
-        info_host[4] = now.normA;
-        info_host[5] = now.condA;
-        info_host[6] = now.normx;
-        info_host[7] = 0;
+using df3d_lsmr::State, df3d_lsmr::Work;
+
+// what one run is given (df3d_ba_lsmr_form's arguments)
+struct LsmrArgs {
+    const df3d_ba_problem* p;
+    const double *Jc, *Jp, *d, *b;
+    double damp, atol, btol, conlim;
+    int maxiter;
+    double *x, *work_dev; void* stream;
+};
+
+void info_from_state(const State& f, double* info) {
+    info[0] = f.istop;
+    info[1] = f.itn;
+    info[2] = f.normr;
+    info[3] = f.normar;
+    info[4] = f.normA;
+    info[5] = f.condA;
+    info[6] = f.normx;
+    info[7] = 0;
+}
+
+int check_form(const char* who, int form_arg) {
+    if (form_arg == DF3D_LSMR_AUTO || form_arg == DF3D_LSMR_BARRIERS || form_arg == DF3D_LSMR_LAUNCHES || form_arg == DF3D_LSMR_LOCAL || form_arg == DF3D_LSMR_ELEVEN)
+        return DF3D_OK;
+    df3d::set_error("%s: %s", who, "unknown LSMR form");
+    return DF3D_EINVAL;
+}
+
+// AUTO: the environment may name a form (A/B runs; tests/test_gpu_ba.py compares them): DF3D_LSMR_KERNELS = 0 (the data-local form) | 1 | 2 | 11
+int resolve_form(int form_arg) {
+    if (form_arg != DF3D_LSMR_AUTO) return form_arg;
+    const char* e = getenv("DF3D_LSMR_KERNELS");
+    const int k = e ? atoi(e) : 0;
+    return k == 11 ? DF3D_LSMR_ELEVEN : k == 2 ? DF3D_LSMR_LAUNCHES : k == 1 ? DF3D_LSMR_BARRIERS : DF3D_LSMR_LOCAL;
+}
+
+// why a run was repeated as LAUNCHES (info[7]), from the istop < 0 it left: a persistent kernel timed out waiting for its peers (its workgroups
+// were not all resident: a device full of other persistent work), or the problem does not fit the data-local form
+int fallback_reason(double istop) { return istop == -1 ? 1 : 2; }
+
+// the data-local run (ba_lsmr.hip: lsmr_local_kernel): the whole solve, its set-up included, in ONE launch and ONE read-back
+int run_local(const LsmrArgs& a, const Work& w, hipStream_t s, double* info_host) {
+    const int rc = df3d_lsmr::launch_local(*a.p, a.Jc, a.Jp, a.d, a.b, a.x, a.damp, a.atol, a.btol, a.conlim > 0 ? 1.0 / a.conlim : 0.0, a.maxiter, w.local_scratch,
+                                           w.local_state, s);
+    if (rc < 0) {
+        info_host[0] = -2;   // does not fit this form: the caller takes another
         return DF3D_OK;
     }
-    double* u = work_dev;
-    double* tmp_m = u + m;
-    double* v = tmp_m + m;
-    double* h = v + n;
-    double* hbar = h + n;
-    double* tmp_n = hbar + n;
-    double* scratch = tmp_n + n;                  // DF3D_BA_SCRATCH_DOUBLES: camera partials
-    double* red = scratch + 2048;                 // RED_BLOCKS partials + result slot
-    double* result = red + RED_BLOCKS;
-    const int gm = grid_for(m), gn = grid_for(n);
+    DF3D_LAUNCH_CHECK();
+    State now{};
+    DF3D_HIP(hipMemcpyAsync(&now, w.local_state, sizeof(now), hipMemcpyDeviceToHost, s));
+    DF3D_HIP(hipStreamSynchronize(s));
+    info_from_state(now, info_host);
+    return DF3D_OK;
+}
 
-    auto sumsq_axpby = [&](double a, const double* x, double bb, const double* y, double* out, size_t len, int g,
-                           double* host) -> int {
-        hipLaunchKernelGGL(axpby_kernel<true>, dim3(g), dim3(256), 0, s, a, x, bb, y, out, len, red);
-        hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, red, g, result);
+// the set-up the other three forms share, with its scalars on the host: u = b / |b|, v = A^T u / |A^T u|, x = hbar = 0, h = v, the initial State
+int lsmr_setup(const LsmrArgs& a, const Work& w, size_t m, size_t n, hipStream_t s, State& init) {
+    auto sumsq_axpby = [&](const double* x, double* out, size_t len, double* host) -> int {
+        const int g = grid_for(len);
+        hipLaunchKernelGGL(axpby_kernel<true>, dim3(g), dim3(256), 0, s, 1.0, x, 0.0, nullptr, out, len, w.red);
+        hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(256), 0, s, w.red, g, w.result);
         DF3D_LAUNCH_CHECK();
-        return read_back(result, host, s);
+        return read_back(w.result, host, s);
     };
-
     double ss = 0.0;
     // u = b ; normb
-    if (int rc = sumsq_axpby(1.0, b_dev, 0.0, nullptr, u, m, gm, &ss)) return rc;
+    if (int rc = sumsq_axpby(a.b, w.u, m, &ss)) return rc;
     const double normb = std::sqrt(ss);
     double beta = normb, alpha = 0.0;
-    DF3D_HIP(hipMemsetAsync(x_dev, 0, n * sizeof(double), s));
-    DF3D_HIP(hipMemsetAsync(hbar, 0, n * sizeof(double), s));
+    DF3D_HIP(hipMemsetAsync(a.x, 0, n * sizeof(double), s));
+    DF3D_HIP(hipMemsetAsync(w.hbar, 0, n * sizeof(double), s));
     if (beta > 0) {
-        if (int rc = df3d_vec_axpby(1.0 / beta, u, 0.0, nullptr, u, m, stream)) return rc;
-        if (int rc = launch_rmatvec(p, Jc, Jp, d_dev, u, tmp_n, scratch, s)) return rc;
-        if (int rc = sumsq_axpby(1.0, tmp_n, 0.0, nullptr, v, n, gn, &ss)) return rc;
+        if (int rc = df3d_vec_axpby(1.0 / beta, w.u, 0.0, nullptr, w.u, m, a.stream)) return rc;
+        if (int rc = launch_rmatvec(a.p, a.Jc, a.Jp, a.d, w.u, w.tmp_n, w.cam_partial, s)) return rc;
+        if (int rc = sumsq_axpby(w.tmp_n, w.v, n, &ss)) return rc;
         alpha = std::sqrt(ss);
     } else {
-        DF3D_HIP(hipMemsetAsync(v, 0, n * sizeof(double), s));
+        DF3D_HIP(hipMemsetAsync(w.v, 0, n * sizeof(double), s));
     }
     if (alpha > 0)
-        if (int rc = df3d_vec_axpby(1.0 / alpha, v, 0.0, nullptr, v, n, stream)) return rc;
+        if (int rc = df3d_vec_axpby(1.0 / alpha, w.v, 0.0, nullptr, w.v, n, a.stream)) return rc;
 
-    // ---- iterations: every scalar of the recurrence lives in `st` on the device; the host only enqueues kernels and
-    // looks at (istop, itn) once per CHUNK iterations (kernels of iterations past the stop are no-ops), instead of three
-    // synchronous read-backs per iteration
-    df3d_lsmr::State init{};
+    init = State{};
     init.alpha = alpha;
     init.beta = beta;
     init.rho = init.rhobar = init.cbar = 1;
@@ -706,169 +686,193 @@ int lsmr_run(const df3d_ba_problem* p, const double* Jc, const double* Jp, const
     init.normr = beta;
     init.normar = alpha * beta;
     init.normb = normb;
-    init.damp = damp;
-    init.atol = atol;
-    init.btol = btol;
-    init.ctol = conlim > 0 ? 1.0 / conlim : 0.0;
+    init.damp = a.damp;
+    init.atol = a.atol;
+    init.btol = a.btol;
+    init.ctol = a.conlim > 0 ? 1.0 / a.conlim : 0.0;
     init.inv_beta = init.inv_alpha = 1.0;
     init.itn = 0;
     init.istop = 0;
-    init.maxiter = maxiter;
+    init.maxiter = a.maxiter;
     init.beta_pos = 1;
-    DF3D_HIP(hipMemcpyAsync(h, v, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    DF3D_HIP(hipMemcpyAsync(w.h, w.v, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return DF3D_OK;
+}
 
-    auto finish = [&](const df3d_lsmr::State& f) {
-        info_host[0] = f.istop;
-        info_host[1] = f.itn;
-        info_host[2] = f.normr;
-        info_host[3] = f.normar;
-        info_host[4] = f.normA;
-        info_host[5] = f.condA;
-        info_host[6] = f.normx;
-        info_host[7] = 0;
-        return DF3D_OK;
-    };
-    if (init.normar == 0 || normb == 0) {
-        DF3D_HIP(hipStreamSynchronize(s));
-        return finish(init);
-    }
-    // round 4: the iteration is TWO kernels (ba_lsmr.hip: fused_ka / fused_kb; the scalar steps run in every workgroup's prologue, the
-    // state alternates between two slots, u and v stay un-normalised with 1 / beta, 1 / alpha in the state) instead of eleven
-    double* const fbase = work_dev + (2 * m + 4 * n + DF3D_BA_SCRATCH_DOUBLES + 64);
-    df3d_lsmr::FusedArgs fa{};
-    fa.Jc = Jc; fa.Jp = Jp; fa.d = d_dev;
-    fa.u = u; fa.v = v; fa.h = h; fa.hbar = hbar; fa.x = x_dev;
-    fa.cam_partial = scratch;
-    fa.st = fbase;
-    fa.red1 = fbase + 2 * df3d_lsmr::FUSED_DOUBLES;
-    fa.red3 = fa.red1 + df3d_lsmr::FUSED_RED;
-    fa.red2 = fa.red3 + df3d_lsmr::FUSED_RED;
-    fa.nchunk = NCHUNK;
-    fa.g1 = gm;    // round 3's grids: the grouping of the sums of squares is part of the arithmetic
-    fa.g2p = gn;
-    fa.g3 = gn;
+// the two-kernel and persistent forms' arguments, and their initial state in slot 0.  The iteration is TWO kernels (ba_lsmr.hip: fused_ka /
+// fused_kb; the scalar steps run in every workgroup's prologue, the state alternates between two slots, u and v stay un-normalised with
+// 1 / beta, 1 / alpha in the state) instead of eleven
+int fused_setup(const LsmrArgs& a, const Work& w, size_t m, size_t n, hipStream_t s, const State& init, df3d_lsmr::FusedArgs& fa) {
+    fa = df3d_lsmr::FusedArgs{};
+    fa.Jc = a.Jc; fa.Jp = a.Jp; fa.d = a.d;
+    fa.u = w.u; fa.v = w.v; fa.h = w.h; fa.hbar = w.hbar; fa.x = a.x;
+    fa.cam_partial = w.cam_partial; fa.st = w.fused; fa.nchunk = NCHUNK;
+    fa.red1 = w.red1; fa.red3 = w.red3; fa.red2 = w.red2;
+    fa.g1 = grid_for(m);    // the eleven-kernel form's grids: the grouping of the sums of squares is part of the arithmetic
+    fa.g2p = grid_for(n);
+    fa.g3 = grid_for(n);
     df3d_lsmr::Fused finit{};
     finit.s = init;
-    finit.pending_c = 0;
-    finit.pending_b = 0;
+    finit.pending_c = finit.pending_b = 0;
     DF3D_HIP(hipMemcpyAsync(fa.st, &finit, sizeof(finit), hipMemcpyHostToDevice, s));
-    DF3D_HIP(hipMemcpyAsync(reinterpret_cast<unsigned char*>(fa.st) + offsetof(df3d_lsmr::Fused, vcam), v, 6 * (size_t)p->ncam * sizeof(double),
+    DF3D_HIP(hipMemcpyAsync(reinterpret_cast<unsigned char*>(fa.st) + offsetof(df3d_lsmr::Fused, vcam), w.v, 6 * (size_t)a.p->ncam * sizeof(double),
                             hipMemcpyDeviceToDevice, s));
     DF3D_HIP(hipStreamSynchronize(s));  // `finit` is on the stack
+    return DF3D_OK;
+}
 
-    // round 3's form (eleven kernels per iteration, one state, u and v normalised in place) stays selectable for A/B runs and as the
-    // arithmetic reference: DF3D_LSMR_KERNELS=11 in the environment
-    const bool r3_form = form == 11;
-    static_assert(sizeof(df3d_lsmr::State) <= 64 * sizeof(double), "state must fit behind the reduction scratch");
-    df3d_lsmr::State* st = reinterpret_cast<df3d_lsmr::State*>(result + 8);
-    if (r3_form) {
-        DF3D_HIP(hipMemcpyAsync(st, &init, sizeof(init), hipMemcpyHostToDevice, s));
+// the whole run in ONE launch (ba_lsmr.hip: fused_persistent) -- grid-wide barriers where the two-kernel form has kernel boundaries, ONE
+// read-back.  Grid: a quarter of the largest phase's virtual workgroups, 8..128 (DF3D_LSMR_GRID overrides): the barrier's price grows with
+// the arrivals, the phases' time shrinks with them; measured in profiles/r05_ba_timings.txt
+int run_persistent(const LsmrArgs& a, const Work& w, const df3d_lsmr::FusedArgs& fa, hipStream_t s, State& now) {
+    const char* const ge = getenv("DF3D_LSMR_GRID");
+    const int grid_env = ge ? atoi(ge) : 0;
+    const int vmax = std::max(std::max(fa.g1, fa.g3), a.p->ncam * fa.nchunk + fa.g2p);
+    int grid = grid_env > 0 ? grid_env : std::min(128, std::max(8, (vmax + 3) / 4));
+    grid = std::min(grid, 256);
+    df3d_lsmr::launch_fused_persistent(*a.p, fa, w.bar, a.maxiter, grid, s);
+    DF3D_LAUNCH_CHECK();
+    DF3D_HIP(hipMemcpyAsync(&now, fa.st, sizeof(now), hipMemcpyDeviceToHost, s));
+    DF3D_HIP(hipStreamSynchronize(s));
+    return DF3D_OK;
+}
+
+// One chunk of CHUNK iterations = 2 x CHUNK small dependent kernels (eleven-kernel form: 11 x CHUNK): launch-bound when enqueued one by one.
+// On a capturable stream (not the legacy default stream) the chunk is recorded once into a HIP graph and replayed -- every scalar the
+// kernels need lives in the device-resident state, so the recording is valid for every chunk of every LSMR run on the same problem and
+// buffers (the three or four runs of one trust-region solve); otherwise the kernels are enqueued directly.
+// The recorded kernels take *p BY VALUE, so the key is every field of the problem (all index tables and the ncam / nobs / npts split, not
+// only their sum) plus every buffer the chunk touches: a recording is replayed only against exactly the arguments it was made with.
+constexpr int CHUNK = 16;
+struct ChunkGraph {
+    static constexpr int NKEY = 12, NDIM = 5;
+    hipGraphExec_t exec = nullptr;
+    const void* key[NKEY] = {};
+    long long dims[NDIM] = {0, 0, 0, 0, 0};
+
+    // the recording of CHUNK x enqueue_iteration() for (key, dims): the one at hand, or a new one in its place; nullptr when the stream
+    // refuses the capture (the caller then enqueues directly)
+    template <class Enqueue>
+    hipGraphExec_t lookup_or_record(const void* const (&k)[NKEY], const long long (&d)[NDIM], hipStream_t s, Enqueue enqueue_iteration) {
+        bool same = exec != nullptr;
+        for (int i = 0; i < NDIM && same; ++i) same = dims[i] == d[i];
+        for (int i = 0; i < NKEY && same; ++i) same = key[i] == k[i];
+        if (same) return exec;
+        if (exec) (void)hipGraphExecDestroy(exec);
+        exec = nullptr;
+        hipGraph_t graph = nullptr;
+        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            int rc = DF3D_OK;
+            for (int it = 0; it < CHUNK && rc == DF3D_OK; ++it) rc = enqueue_iteration();
+            const hipError_t e = hipStreamEndCapture(s, &graph);
+            if (rc == DF3D_OK && e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+                for (int i = 0; i < NKEY; ++i) key[i] = k[i];
+                for (int i = 0; i < NDIM; ++i) dims[i] = d[i];
+            } else {
+                exec = nullptr;
+            }
+            if (graph) (void)hipGraphDestroy(graph);
+        }
+        (void)hipGetLastError();   // a refused capture is not an error of this call: the direct path takes over
+        return exec;
+    }
+};
+thread_local ChunkGraph chunk_graph;
+
+// the launch-based run: every scalar of the recurrence lives in the state on the device; the host only enqueues kernels, CHUNK iterations
+// at a time, and looks at (istop, itn) once per chunk (kernels of iterations past the stop are no-ops).  eleven: the eleven-kernel form
+// (one state, u and v normalised in place), selectable for A/B runs and as the arithmetic reference; otherwise two kernels per iteration
+int run_chunked(const LsmrArgs& a, const Work& w, const df3d_lsmr::FusedArgs& fa, size_t m, size_t n, hipStream_t s, bool eleven, State& now) {
+    const df3d_ba_problem* const p = a.p;
+    State* const st = w.state;
+    if (eleven) {
+        DF3D_HIP(hipMemcpyAsync(st, &now, sizeof(now), hipMemcpyHostToDevice, s));
         DF3D_HIP(hipStreamSynchronize(s));
     }
-
-    if (form == 0) {
-        // round 5: the whole run in ONE launch (ba_lsmr.hip: fused_persistent) -- grid-wide barriers where the two-kernel form has kernel
-        // boundaries, ONE read-back.  Grid: a quarter of the largest phase's virtual workgroups, 8..128 (DF3D_LSMR_GRID overrides): the
-        // barrier's price grows with the arrivals, the phases' time shrinks with them; measured in profiles/r05_ba_timings.txt
-        const char* const ge = getenv("DF3D_LSMR_GRID");
-        const int grid_env = ge ? atoi(ge) : 0;
-        const int vmax = std::max(std::max(fa.g1, fa.g3), p->ncam * fa.nchunk + fa.g2p);
-        int grid = grid_env > 0 ? grid_env : std::min(128, std::max(8, (vmax + 3) / 4));
-        grid = std::min(grid, 256);
-        unsigned* const bar = reinterpret_cast<unsigned*>(fa.red2 + df3d_lsmr::FUSED_RED);
-        df3d_lsmr::launch_fused_persistent(*p, fa, bar, maxiter, grid, s);
-        DF3D_LAUNCH_CHECK();
-        df3d_lsmr::State now = init;
-        DF3D_HIP(hipMemcpyAsync(&now, fa.st, sizeof(now), hipMemcpyDeviceToHost, s));
-        DF3D_HIP(hipStreamSynchronize(s));
-        return finish(now);
-    }
-
-    constexpr int CHUNK = 16;
-    df3d_lsmr::State now = init;
+    const int gm = grid_for(m), gn = grid_for(n);
     auto enqueue_iteration = [&]() -> int {
-        if (r3_form) {
+        if (eleven) {
             // u = A v - alpha u ; beta = |u| ; u /= beta
-            if (int rc = launch_matvec(p, Jc, Jp, d_dev, v, tmp_m, s)) return rc;
-            hipLaunchKernelGGL(lsmr_bidiag_kernel<0>, dim3(gm), dim3(256), 0, s, st, tmp_m, u, m, red);
-            df3d_lsmr::launch_step_a(st, red, gm, s);
-            hipLaunchKernelGGL(lsmr_scale_kernel<0>, dim3(gm), dim3(256), 0, s, st, u, m);
+            if (int rc = launch_matvec(p, a.Jc, a.Jp, a.d, w.v, w.tmp_m, s)) return rc;
+            hipLaunchKernelGGL(lsmr_bidiag_kernel<0>, dim3(gm), dim3(256), 0, s, st, w.tmp_m, w.u, m, w.red);
+            df3d_lsmr::launch_step_a(st, w.red, gm, s);
+            hipLaunchKernelGGL(lsmr_scale_kernel<0>, dim3(gm), dim3(256), 0, s, st, w.u, m);
             // v = A^T u - beta v ; alpha = |v| ; rotations ; v /= alpha
-            if (int rc = launch_rmatvec(p, Jc, Jp, d_dev, u, tmp_n, scratch, s)) return rc;
-            hipLaunchKernelGGL(lsmr_bidiag_kernel<1>, dim3(gn), dim3(256), 0, s, st, tmp_n, v, n, red);
-            df3d_lsmr::launch_step_b(st, red, gn, s);
-            hipLaunchKernelGGL(lsmr_scale_kernel<1>, dim3(gn), dim3(256), 0, s, st, v, n);
+            if (int rc = launch_rmatvec(p, a.Jc, a.Jp, a.d, w.u, w.tmp_n, w.cam_partial, s)) return rc;
+            hipLaunchKernelGGL(lsmr_bidiag_kernel<1>, dim3(gn), dim3(256), 0, s, st, w.tmp_n, w.v, n, w.red);
+            df3d_lsmr::launch_step_b(st, w.red, gn, s);
+            hipLaunchKernelGGL(lsmr_scale_kernel<1>, dim3(gn), dim3(256), 0, s, st, w.v, n);
             // hbar, x, h ; |x| ; stopping tests
-            hipLaunchKernelGGL(lsmr_update_dev_kernel, dim3(gn), dim3(256), 0, s, st, hbar, h, x_dev, v, n, red);
-            df3d_lsmr::launch_step_c(st, red, gn, s);
+            hipLaunchKernelGGL(lsmr_update_dev_kernel, dim3(gn), dim3(256), 0, s, st, w.hbar, w.h, a.x, w.v, n, w.red);
+            df3d_lsmr::launch_step_c(st, w.red, gn, s);
             return DF3D_OK;
         }
         df3d_lsmr::launch_fused_iteration(*p, fa, s);   // (ka: state slot 0 -> 1, kb: 1 -> 0)
         DF3D_LAUNCH_CHECK();
         return DF3D_OK;
     };
-    // One chunk of CHUNK iterations = 2 x CHUNK small dependent kernels (round 3: 11 x CHUNK): launch-bound when enqueued one by one.  On a
-    // capturable stream (not the legacy default stream) the chunk is recorded once into a HIP graph and replayed -- every
-    // scalar the kernels need lives in `st`, so the recording is valid for every chunk of every LSMR run on the same problem
-    // and buffers (the three or four runs of one trust-region solve); otherwise the kernels are enqueued directly.
-    // The recorded kernels take *p BY VALUE, so the key is every field of the problem (all index tables and the ncam / nobs /
-    // npts split, not only their sum) plus every buffer the chunk touches: a recording is replayed only against exactly the
-    // arguments it was made with.
-    constexpr int NKEY = 12;
-    struct ChunkGraph {
-        hipGraphExec_t exec = nullptr;
-        const void* key[NKEY] = {};
-        long long dims[5] = {0, 0, 0, 0, 0};
-    };
-    static thread_local ChunkGraph cache;
-    const void* key[NKEY] = {p->obs_xy, Jc, Jp, d_dev, x_dev, work_dev, p->cam_idx, p->pt_idx, p->intr4, p->pt_start, p->cam_perm, p->cam_start};
-    const long long dims[5] = {(long long)m, (long long)n, p->ncam, p->nobs, p->npts};
-    bool use_graph = s != nullptr && maxiter >= CHUNK;
-    if (use_graph) {
-        bool same = cache.exec != nullptr;
-        for (int k = 0; k < 5 && same; ++k) same = cache.dims[k] == dims[k];
-        for (int k = 0; k < NKEY && same; ++k) same = cache.key[k] == key[k];
-        if (!same) {
-            if (cache.exec) (void)hipGraphExecDestroy(cache.exec);
-            cache.exec = nullptr;
-            hipGraph_t graph = nullptr;
-            if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                int rc = DF3D_OK;
-                for (int it = 0; it < CHUNK && rc == DF3D_OK; ++it) rc = enqueue_iteration();
-                const hipError_t e = hipStreamEndCapture(s, &graph);
-                if (rc == DF3D_OK && e == hipSuccess && graph && hipGraphInstantiate(&cache.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    for (int k = 0; k < NKEY; ++k) cache.key[k] = key[k];
-                    for (int k = 0; k < 5; ++k) cache.dims[k] = dims[k];
-                } else {
-                    cache.exec = nullptr;
-                }
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            (void)hipGetLastError();   // a refused capture is not an error of this call: the direct path below takes over
-            if (!cache.exec) use_graph = false;
-        }
+    hipGraphExec_t graph = nullptr;
+    if (s != nullptr && a.maxiter >= CHUNK) {
+        const void* key[ChunkGraph::NKEY] = {p->obs_xy, a.Jc, a.Jp, a.d, a.x, a.work_dev, p->cam_idx, p->pt_idx, p->intr4, p->pt_start, p->cam_perm, p->cam_start};
+        const long long dims[ChunkGraph::NDIM] = {(long long)m, (long long)n, p->ncam, p->nobs, p->npts};
+        graph = chunk_graph.lookup_or_record(key, dims, s, enqueue_iteration);
     }
-    for (int done = 0; done < maxiter && now.istop == 0; done += CHUNK) {
-        const int todo = maxiter - done < CHUNK ? maxiter - done : CHUNK;
-        if (use_graph && todo == CHUNK) {
-            DF3D_HIP(hipGraphLaunch(cache.exec, s));
+    for (int done = 0; done < a.maxiter && now.istop == 0; done += CHUNK) {
+        const int todo = a.maxiter - done < CHUNK ? a.maxiter - done : CHUNK;
+        if (graph && todo == CHUNK) {
+            DF3D_HIP(hipGraphLaunch(graph, s));
         } else {
             for (int it = 0; it < todo; ++it)
                 if (int rc = enqueue_iteration()) return rc;
             DF3D_LAUNCH_CHECK();
         }
-        DF3D_HIP(hipMemcpyAsync(&now, r3_form ? reinterpret_cast<const double*>(st) : fa.st, sizeof(now), hipMemcpyDeviceToHost,
+        DF3D_HIP(hipMemcpyAsync(&now, eleven ? reinterpret_cast<const double*>(st) : fa.st, sizeof(now), hipMemcpyDeviceToHost,
                                 s));   // (two-kernel form: an iteration leaves the state in slot 0; State leads Fused)
         DF3D_HIP(hipStreamSynchronize(s));
     }
-    if (now.istop == 0 && !r3_form) {
+    if (now.istop == 0 && !eleven) {
         // maxiter reached: the last iteration's steps B and C (and its update of x) are still pending -- one more ka and the scalar half of
         // kb take them; a run that stopped earlier was settled by the kernels behind its last iteration
         df3d_lsmr::launch_fused_flush(*p, fa, s);
         DF3D_HIP(hipMemcpyAsync(&now, fa.st, sizeof(now), hipMemcpyDeviceToHost, s));
         DF3D_HIP(hipStreamSynchronize(s));
     }
-    return finish(now);
+    return DF3D_OK;
+}
+
+// one run in `form` (not AUTO).  A form that cannot take the run leaves info_host[0] < 0 (fallback_reason) and x_dev undefined
+int lsmr_run(LsmrArgs a, double* info_host, int form) {
+    if (int rc = check_problem(a.p)) return rc;
+    DF3D_CHECK_ARG(a.Jc && a.Jp && a.b && a.x && a.work_dev && info_host, "null pointer");
+    hipStream_t s = df3d::as_stream(a.stream);
+    const size_t m = 2 * (size_t)a.p->nobs, n = 6 * (size_t)a.p->ncam + 3 * (size_t)a.p->npts;
+    if (a.maxiter <= 0) a.maxiter = (int)(m < n ? m : n);
+    const Work w(a.work_dev, m, n);
+    if (form == DF3D_LSMR_LOCAL) return run_local(a, w, s, info_host);
+    State now{};
+    if (int rc = lsmr_setup(a, w, m, n, s, now)) return rc;
+    if (now.normar == 0 || now.normb == 0) {
+        DF3D_HIP(hipStreamSynchronize(s));
+        info_from_state(now, info_host);
+        return DF3D_OK;
+    }
+    df3d_lsmr::FusedArgs fa;
+    if (int rc = fused_setup(a, w, m, n, s, now, fa)) return rc;
+    if (int rc = form == DF3D_LSMR_BARRIERS ? run_persistent(a, w, fa, s, now) : run_chunked(a, w, fa, m, n, s, form == DF3D_LSMR_ELEVEN, now)) return rc;
+    info_from_state(now, info_host);
+    return DF3D_OK;
+}
+
+// Runs `form`; when it reports that it could not take the run (the problem does not fit the data-local form, or a persistent kernel timed
+// out), the run is repeated from its inputs as LAUNCHES, which needs no co-residency, and info_host[7] says so, and why
+int lsmr_run_or_launches(const LsmrArgs& a, double* info_host, int form) {
+    int rc = lsmr_run(a, info_host, form);
+    if (rc == DF3D_OK && (form == DF3D_LSMR_BARRIERS || form == DF3D_LSMR_LOCAL) && info_host[0] < 0) {
+        const int why = fallback_reason(info_host[0]);
+        rc = lsmr_run(a, info_host, DF3D_LSMR_LAUNCHES);
+        if (rc == DF3D_OK) info_host[7] = why;
+    }
+    return rc;
 }
 }  // namespace
 
@@ -877,26 +881,8 @@ extern "C" {
 int df3d_ba_lsmr_form(const df3d_ba_problem* p, const double* Jc, const double* Jp, const double* d_dev,
                       const double* b_dev, double damp, double atol, double btol, double conlim, int maxiter,
                       double* x_dev, double* work_dev, double* info_host, void* stream, int form_arg) {
-    DF3D_CHECK_ARG(form_arg == DF3D_LSMR_AUTO || form_arg == DF3D_LSMR_BARRIERS || form_arg == DF3D_LSMR_LAUNCHES || form_arg == DF3D_LSMR_LOCAL ||
-                       form_arg == DF3D_LSMR_ELEVEN, "unknown LSMR form");
-    // AUTO: the environment may name a form (A/B runs; tests/test_gpu_ba.py compares them): DF3D_LSMR_KERNELS = 0 (AUTO) | 1 | 2 | 11
-    int want = form_arg;
-    if (want == DF3D_LSMR_AUTO) {
-        const char* e = getenv("DF3D_LSMR_KERNELS");
-        const int k = e ? atoi(e) : 0;
-        want = k == 11 ? DF3D_LSMR_ELEVEN : k == 2 ? DF3D_LSMR_LAUNCHES : k == 1 ? DF3D_LSMR_BARRIERS : DF3D_LSMR_LOCAL;
-    }
-    const int form = want == DF3D_LSMR_ELEVEN ? 11 : want == DF3D_LSMR_LAUNCHES ? 2 : want == DF3D_LSMR_BARRIERS ? 0 : 3;   // (lsmr_run's numbering)
-    int rc = lsmr_run(p, Jc, Jp, d_dev, b_dev, damp, atol, btol, conlim, maxiter, x_dev, work_dev, info_host, stream, form);
-    if (rc == DF3D_OK && (form == 0 || form == 3) && info_host[0] < 0) {
-        // the problem does not fit the data-local form, or a persistent kernel timed out waiting for its peers (its workgroups were not
-        // all resident: a device full of other persistent work): the run is repeated from its inputs in the two-kernel form, which
-        // needs no co-residency
-        const bool timeout = info_host[0] == -1;
-        rc = lsmr_run(p, Jc, Jp, d_dev, b_dev, damp, atol, btol, conlim, maxiter, x_dev, work_dev, info_host, stream, 2);
-        if (rc == DF3D_OK) info_host[7] = timeout ? 1 : 2;   // (reported: the fallback was taken, and why)
-    }
-    return rc;
+    if (int rc = check_form(__func__, form_arg)) return rc;
+    return lsmr_run_or_launches({p, Jc, Jp, d_dev, b_dev, damp, atol, btol, conlim, maxiter, x_dev, work_dev, stream}, info_host, resolve_form(form_arg));
 }
 
 int df3d_ba_lsmr(const df3d_ba_problem* p, const double* Jc, const double* Jp, const double* d_dev,
@@ -907,17 +893,17 @@ int df3d_ba_lsmr(const df3d_ba_problem* p, const double* Jc, const double* Jp, c
 
 }  // extern "C"
 
-// ---- round 6: the trust-region driver's scalars stay on the device ------------------------------------------------------------------
-// One outer iteration of bundle_adjust.py:solve_trf used to read back seven groups of scalars (|g|_inf; the Cauchy model's two dots; the
-// LSMR state; r01; |s1|; the 2x2 model's five dots; the trial step's six): each a stream synchronisation with the device idle behind it.
+// ---- the trust-region driver's scalars stay on the device -----------------------------------------------------------------------------
+// One outer iteration of bundle_adjust.py:solve_trf, with its scalars on the host, reads back seven groups of scalars (|g|_inf; the Cauchy
+// model's two dots; the LSMR state; r01; |s1|; the 2x2 model's five dots; the trial step's six): each a stream synchronisation with the
+// device idle behind it.
 // df3d_ba_trf_subspace enqueues everything between "g is known" and "the 2-D model is known" -- the damping, the LSMR solve that reads it
 // from device memory, the QR of [g_h, gn_h], J_h S and the model's dots -- and reads ONE block back; df3d_ba_trf_trial is a trial step with
-// its one read-back; df3d_ba_trf_linearize the re-linearisation (no read-back).  The arithmetic is the Python driver's, operation for
+// its one read-back; df3d_ba_trf_linearize the re-linearisation (no read-back).  The arithmetic is the host-scalar back end's, operation for
 // operation (same kernels for every vector operation and reduction; the scalar expressions below are written without contraction), so
-// the iterate sequence -- nfev, LSMR counts, every bit of x -- is unchanged (tests/test_gpu_ba.py compares the two drivers).
+// the iterate sequence -- nfev, LSMR counts, every bit of x -- is unchanged (tests/test_gpu_ba.py compares the two back ends).
 namespace {
 enum { TR_GNORM = 0, TR_JG2, TR_GH2, TR_DAMP, TR_CS0, TR_R01, TR_MR01, TR_N1SQ, TR_CS1, TR_B00, TR_B01, TR_B11, TR_GS0, TR_GS1, TR_ONE, TR_SLOTS };
-constexpr int TR_OFFSET = 8 * RED_BLOCKS + 16;   // the block's place in scratch_dev (behind the dots' partials and results)
 static_assert(TR_OFFSET + TR_SLOTS <= DF3D_BA_SCRATCH_DOUBLES, "scratch");
 
 // out = (*ca) x + (*cb) y (y / cb may be null): axpby_kernel with its coefficients in device memory
@@ -955,30 +941,6 @@ __global__ void trf_scalar_kernel(double* __restrict__ tr, double Delta) {
     }
 }
 
-int enqueue_dots(int count, const double* const* a, const double* const* b, const size_t* n, double* scratch, double* result, hipStream_t s) {
-    DotBatch q{};
-    int gmax = 1;
-    for (int j = 0; j < count; ++j) {
-        q.a[j] = a[j];
-        q.b[j] = b[j];
-        q.n[j] = n[j];
-        q.g[j] = grid_for(n[j]);
-        gmax = q.g[j] > gmax ? q.g[j] : gmax;
-    }
-    hipLaunchKernelGGL(dots_kernel, dim3(gmax, count), dim3(256), 0, s, q, scratch);
-    hipLaunchKernelGGL(dots_final_kernel, dim3(count), dim3(256), 0, s, q, scratch, result);
-    DF3D_LAUNCH_CHECK();
-    return DF3D_OK;
-}
-int resolve_form(int form_arg) {   // df3d_ba_lsmr_form's rule: lsmr_run's numbering
-    int want = form_arg;
-    if (want == DF3D_LSMR_AUTO) {
-        const char* e = getenv("DF3D_LSMR_KERNELS");
-        const int k = e ? atoi(e) : 0;
-        want = k == 11 ? DF3D_LSMR_ELEVEN : k == 2 ? DF3D_LSMR_LAUNCHES : k == 1 ? DF3D_LSMR_BARRIERS : DF3D_LSMR_LOCAL;
-    }
-    return want == DF3D_LSMR_ELEVEN ? 11 : want == DF3D_LSMR_LAUNCHES ? 2 : want == DF3D_LSMR_BARRIERS ? 0 : 3;
-}
 }  // namespace
 
 extern "C" {
@@ -988,8 +950,7 @@ int df3d_ba_trf_subspace(const df3d_ba_problem* p, const double* Jc, const doubl
                          double* scratch_dev, double* out_host, void* stream, int form_arg) {
     if (int rc = check_problem(p)) return rc;
     DF3D_CHECK_ARG(Jc && Jp && scale_dev && g_dev && f_dev && g_h && gn_h && s0 && s1 && Js0 && Js1 && tmp_m && work_dev && scratch_dev && out_host, "null pointer");
-    DF3D_CHECK_ARG(form_arg == DF3D_LSMR_AUTO || form_arg == DF3D_LSMR_BARRIERS || form_arg == DF3D_LSMR_LAUNCHES || form_arg == DF3D_LSMR_LOCAL ||
-                       form_arg == DF3D_LSMR_ELEVEN, "unknown LSMR form");
+    if (int rc = check_form(__func__, form_arg)) return rc;
     DF3D_CHECK_ARG(Delta > 0, "the trust radius must be positive");
     hipStream_t s = df3d::as_stream(stream);
     const size_t m = 2 * (size_t)p->nobs, n = 6 * (size_t)p->ncam + 3 * (size_t)p->npts;
@@ -1009,29 +970,25 @@ int df3d_ba_trf_subspace(const df3d_ba_problem* p, const double* Jc, const doubl
     DF3D_LAUNCH_CHECK();
 
     double info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const int maxiter = (int)(m < n ? m : n);
-    const double atol = 1e-6, btol = 1e-6, conlim = 1e8;   // solve_trf's (scipy's tr_options defaults for lsmr inside least_squares)
-    int form = resolve_form(form_arg);
-    bool local = form == 3 && df3d_lsmr::local_fits(*p);
-    double* const lscratch = work_dev + (2 * m + 4 * n + DF3D_BA_SCRATCH_DOUBLES + 64 + 2 * df3d_lsmr::FUSED_DOUBLES + 3 * df3d_lsmr::FUSED_RED + 8);
-    double* const lstate = lscratch + (df3d_lsmr::local_scratch_bytes() + 7) / 8;
+    // solve_trf's tolerances (scipy's tr_options defaults for lsmr inside least_squares); the damping is filled in where it is known
+    LsmrArgs lsmr{p, Jc, Jp, scale_dev, f_dev, 0.0, 1e-6, 1e-6, 1e8, (int)(m < n ? m : n), gn_h, work_dev, stream};
+    const int form = resolve_form(form_arg);
+    bool local = form == DF3D_LSMR_LOCAL && df3d_lsmr::local_fits(*p);
+    const Work w(work_dev, m, n);
     auto lsmr_on_host_damp = [&](int f) -> int {   // the forms whose set-up runs on the host: one more read-back for the damping
-        double damp = 0.0;
-        if (int rc = read_back(tr + TR_DAMP, &damp, s)) return rc;
-        int rc = lsmr_run(p, Jc, Jp, scale_dev, f_dev, damp, atol, btol, conlim, maxiter, gn_h, work_dev, info, stream, f);
-        if (rc == DF3D_OK && f == 0 && info[0] < 0) {
-            rc = lsmr_run(p, Jc, Jp, scale_dev, f_dev, damp, atol, btol, conlim, maxiter, gn_h, work_dev, info, stream, 2);
-            if (rc == DF3D_OK) info[7] = 1;
-        }
-        return rc;
+        if (int rc = read_back(tr + TR_DAMP, &lsmr.damp, s)) return rc;
+        return lsmr_run_or_launches(lsmr, info, f);
     };
     if (local) {
-        if (df3d_lsmr::launch_local(*p, Jc, Jp, scale_dev, f_dev, gn_h, 0.0, atol, btol, 1.0 / conlim, maxiter, lscratch, lstate, s, tr + TR_DAMP) < 0) local = false;
+        // the data-local kernel reads the damping from device memory: it is launched before anything is read back
+        if (df3d_lsmr::launch_local(*p, Jc, Jp, scale_dev, f_dev, gn_h, 0.0, lsmr.atol, lsmr.btol, 1.0 / lsmr.conlim, lsmr.maxiter, w.local_scratch, w.local_state, s,
+                                    tr + TR_DAMP) < 0)
+            local = false;
         DF3D_LAUNCH_CHECK();
     }
     if (!local) {
-        if (int rc = lsmr_on_host_damp(form == 3 ? 2 : form)) return rc;
-        if (form == 3) info[7] = 2;
+        if (int rc = lsmr_on_host_damp(form == DF3D_LSMR_LOCAL ? DF3D_LSMR_LAUNCHES : form)) return rc;
+        if (form == DF3D_LSMR_LOCAL) info[7] = fallback_reason(-2);   // (does not fit)
     }
     // S = qr([g_h, gn_h]) with LAPACK's signs, J_h S, the 2x2 model
     auto subspace = [&]() -> int {
@@ -1060,29 +1017,21 @@ int df3d_ba_trf_subspace(const df3d_ba_problem* p, const double* Jc, const doubl
     };
     if (int rc = subspace()) return rc;
     double host[TR_SLOTS];
-    df3d_lsmr::State now{};
+    State now{};
     DF3D_HIP(hipMemcpyAsync(host, tr, sizeof(host), hipMemcpyDeviceToHost, s));
-    if (local) DF3D_HIP(hipMemcpyAsync(&now, lstate, sizeof(now), hipMemcpyDeviceToHost, s));
+    if (local) DF3D_HIP(hipMemcpyAsync(&now, w.local_state, sizeof(now), hipMemcpyDeviceToHost, s));
     DF3D_HIP(hipStreamSynchronize(s));
     if (local) {
         if (now.istop < 0) {
-            // the layout check on the device refused the problem, or the persistent kernel timed out waiting for its peers: the solve is
-            // repeated from its inputs in the two-kernel form (df3d_ba_lsmr_form's rule), and what was built on its result with it
-            const bool timeout = now.istop == -1;
-            if (int rc = lsmr_on_host_damp(2)) return rc;
-            info[7] = timeout ? 1 : 2;
+            // the layout check on the device refused the problem, or the kernel timed out waiting for its peers: the solve is repeated from
+            // its inputs as LAUNCHES (lsmr_run_or_launches's rule), and what was built on its result with it
+            if (int rc = lsmr_on_host_damp(DF3D_LSMR_LAUNCHES)) return rc;
+            info[7] = fallback_reason(now.istop);
             if (int rc = subspace()) return rc;
             DF3D_HIP(hipMemcpyAsync(host, tr, sizeof(host), hipMemcpyDeviceToHost, s));
             DF3D_HIP(hipStreamSynchronize(s));
         } else {
-            info[0] = now.istop;
-            info[1] = now.itn;
-            info[2] = now.normr;
-            info[3] = now.normar;
-            info[4] = now.normA;
-            info[5] = now.condA;
-            info[6] = now.normx;
-            info[7] = 0;
+            info_from_state(now, info);
         }
     }
     out_host[0] = host[TR_GNORM];
@@ -1112,7 +1061,7 @@ int df3d_ba_trf_trial(const df3d_ba_problem* p, double p0, double p1, const doub
     const double* a[6] = {tmp_m, step_h, step_h, f_new, step, x_dev};
     const double* b[6] = {tmp_m, g_h, step_h, f_new, step, x_dev};
     const size_t len[6] = {m, n, n, m, n, n};
-    double* const result = scratch_dev + 8 * RED_BLOCKS;
+    double* const result = scratch_dev + SCRATCH_DOTS_RESULT;
     if (int rc = enqueue_dots(6, a, b, len, scratch_dev, result, s)) return rc;
     DF3D_HIP(hipMemcpyAsync(out_host, result, 6 * sizeof(double), hipMemcpyDeviceToHost, s));
     DF3D_HIP(hipStreamSynchronize(s));

@@ -1060,6 +1060,45 @@ size_t local_scratch_bytes() { return (size_t)(LMAXG + 1) * sizeof(int) + 64 + 2
 
 bool local_fits(const df3d_ba_problem& p) { return local_workgroups_for(p.nobs) <= LMAXG && 1 + 6 * p.ncam <= 49; }
 
+// development (DF3D_LSMR_DEBUG): every all-reduce's inputs and outputs of every workgroup of the run just launched, checked on the host
+static void check_local_debug_log(const double* dbg, int G, hipStream_t s) {
+    std::vector<double> hbuf((size_t)LDBG_CALLS * G * 98);
+    (void)hipStreamSynchronize(s);
+    (void)hipMemcpy(hbuf.data(), dbg, hbuf.size() * sizeof(double), hipMemcpyDeviceToHost);
+    double tacc[10];
+    (void)hipMemcpy(tacc, dbg + (size_t)LDBG_CALLS * G * 98, sizeof(tacc), hipMemcpyDeviceToHost);
+    fprintf(stderr, "lsmr dbg: cycles of workgroup 0 summed over the run (100 MHz s_memtime ticks?): A+reduce %.0f | AR1 %.0f | steps C,A %.0f | scale u + J^T u passes %.0f | AR2 %.0f | vcam + step B %.0f | scale v + update %.0f\n",
+            tacc[0], tacc[1], tacc[2], tacc[3], tacc[4], tacc[5], tacc[6]);
+    static std::vector<double> first;
+    int bad_sum = 0, bad_agree = 0, bad_repro = 0, calls = 0;
+    for (int c = 0; c < LDBG_CALLS; ++c) {
+        const double* base = hbuf.data() + (size_t)c * G * 98;
+        bool any = false;
+        for (int k = 0; k < 49 && !any; ++k) any = base[49 + k] != 0.0;
+        if (!any) continue;
+        ++calls;
+        for (int k = 0; k < 49; ++k) {
+            double t = 0.0;
+            for (int w = 0; w < G; ++w) t += base[(size_t)w * 98 + k];
+            for (int w = 0; w < G; ++w) {
+                bad_agree += base[(size_t)w * 98 + 49 + k] != base[49 + k];
+                bad_sum += base[(size_t)w * 98 + 49 + k] != t;
+            }
+        }
+    }
+    if (first.empty()) first = hbuf;
+    else {
+        for (size_t i = 0; i < hbuf.size() && i < first.size(); ++i)
+            if (hbuf[i] != first[i]) {
+                if (bad_repro < 6) fprintf(stderr, "lsmr dbg: first difference from run 0: call %zu wg %zu slot %zu (%s): %.17g vs %.17g\n", i / ((size_t)G * 98), (i / 98) % G, i % 98,
+                                           (i % 98) < 49 ? "own" : "res", hbuf[i], first[i]);
+                ++bad_repro;
+            }
+    }
+    fprintf(stderr, "lsmr dbg: G %d, %d all-reduces logged: results != ordered sum of inputs: %d, workgroups disagreeing: %d, values differing from the first run: %d\n", G, calls, bad_sum,
+            bad_agree, bad_repro);
+}
+
 // the whole run in one launch; `scratch`: local_scratch_bytes() bytes of device memory (zeroed here); state_out: >= sizeof(State)
 int launch_local(const df3d_ba_problem& p, const double* Jc, const double* Jp, const double* d, const double* b, double* x, double damp, double atol,
                  double btol, double ctol, int maxiter, void* scratch, double* state_out, hipStream_t s, const double* damp_dev) {
@@ -1086,43 +1125,7 @@ int launch_local(const df3d_ba_problem& p, const double* Jc, const double* Jp, c
         }
     }
     hipLaunchKernelGGL(lsmr_local_kernel, dim3(G), dim3(LT), sizeof(LocalLds), s, p, a);
-    if (want_dbg) {   // development: every all-reduce's inputs and outputs of every workgroup, checked on the host
-        std::vector<double> hbuf((size_t)LDBG_CALLS * G * 98);
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(hbuf.data(), dbg, hbuf.size() * sizeof(double), hipMemcpyDeviceToHost);
-        double tacc[10];
-        (void)hipMemcpy(tacc, dbg + (size_t)LDBG_CALLS * G * 98, sizeof(tacc), hipMemcpyDeviceToHost);
-        fprintf(stderr, "lsmr dbg: cycles of workgroup 0 summed over the run (100 MHz s_memtime ticks?): A+reduce %.0f | AR1 %.0f | steps C,A %.0f | scale u + J^T u passes %.0f | AR2 %.0f | vcam + step B %.0f | scale v + update %.0f\n",
-                tacc[0], tacc[1], tacc[2], tacc[3], tacc[4], tacc[5], tacc[6]);
-        static std::vector<double> first;
-        int bad_sum = 0, bad_agree = 0, bad_repro = 0, calls = 0;
-        for (int c = 0; c < LDBG_CALLS; ++c) {
-            const double* base = hbuf.data() + (size_t)c * G * 98;
-            bool any = false;
-            for (int k = 0; k < 49 && !any; ++k) any = base[49 + k] != 0.0;
-            if (!any) continue;
-            ++calls;
-            for (int k = 0; k < 49; ++k) {
-                double t = 0.0;
-                for (int w = 0; w < G; ++w) t += base[(size_t)w * 98 + k];
-                for (int w = 0; w < G; ++w) {
-                    bad_agree += base[(size_t)w * 98 + 49 + k] != base[49 + k];
-                    bad_sum += base[(size_t)w * 98 + 49 + k] != t;
-                }
-            }
-        }
-        if (first.empty()) first = hbuf;
-        else {
-            for (size_t i = 0; i < hbuf.size() && i < first.size(); ++i)
-                if (hbuf[i] != first[i]) {
-                    if (bad_repro < 6) fprintf(stderr, "lsmr dbg: first difference from run 0: call %zu wg %zu slot %zu (%s): %.17g vs %.17g\n", i / ((size_t)G * 98), (i / 98) % G, i % 98,
-                                               (i % 98) < 49 ? "own" : "res", hbuf[i], first[i]);
-                    ++bad_repro;
-                }
-        }
-        fprintf(stderr, "lsmr dbg: G %d, %d all-reduces logged: results != ordered sum of inputs: %d, workgroups disagreeing: %d, values differing from the first run: %d\n", G, calls, bad_sum,
-                bad_agree, bad_repro);
-    }
+    if (want_dbg) check_local_debug_log(dbg, G, s);
     return 0;
 }
 

@@ -303,15 +303,17 @@ int df3d_ba_rmatvec(const df3d_ba_problem* p, const double* Jc_dev, const double
  * work_dev: at least df3d_ba_lsmr_work_doubles(p) doubles (includes the scratch).  info_host[8] =
  * {istop, itn, normr, normar, normA, condA, normx, fallback} (fallback: 0, or why a persistent form handed the run to the launch-based
  * one: 1 its workgroups never became co-resident, 2 the problem does not fit it).
- * Forms (df3d_ba_lsmr_form; df3d_ba_lsmr = DF3D_LSMR_AUTO, the environment variable DF3D_LSMR_KERNELS = 0 | 1 | 2 | 11 overrides AUTO):
+ * Forms (df3d_ba_lsmr_form; df3d_ba_lsmr = DF3D_LSMR_AUTO, the environment variable DF3D_LSMR_KERNELS = 0 | 1 | 2 | 11 overrides AUTO).
+ * The values below are the only numbering: AUTO is resolved once per call (csrc/ba.hip: resolve_form), every other value names the code
+ * that runs (lsmr_run), and one rule (lsmr_run_or_launches) repeats as LAUNCHES a run that LOCAL or BARRIERS could not take:
  *   DF3D_LSMR_LOCAL     ONE persistent kernel per solve: every workgroup owns a range of points with their observations, Jacobian slice and
- *                       vectors in registers, two small all-reduces per iteration, one read-back per solve (round 5).  Up to 128 ranges of
+ *                       vectors in registers, two small all-reduces per iteration, one read-back per solve.  Up to 128 ranges of
  *                       1 024 observations (every window of <= 1 000 frames); wants the device to itself: up to 128 workgroups of 512
  *                       threads and 96 KB of LDS have to be resident at once.  Sums grouped per range: last-bit differences from the others.
- *   DF3D_LSMR_LAUNCHES  two kernels per iteration, 16 iterations per host read-back (round 4): needs no co-residency -- the form to use
+ *   DF3D_LSMR_LAUNCHES  two kernels per iteration, 16 iterations per host read-back: needs no co-residency -- the form to use
  *                       when the solve runs BESIDE other work on the device (a re-calibration next to the frame pipeline).
- *   DF3D_LSMR_BARRIERS  the launch-based arithmetic in one persistent kernel with grid-wide barriers (round 5; measured slower than
- *                       LAUNCHES: profiles/r05_ba_timings.txt);  DF3D_LSMR_ELEVEN  round 3's eleven kernels per iteration.
+ *   DF3D_LSMR_BARRIERS  the launch-based arithmetic in one persistent kernel with grid-wide barriers (measured slower than
+ *                       LAUNCHES: profiles/r05_ba_timings.txt);  DF3D_LSMR_ELEVEN  eleven kernels per iteration, the arithmetic reference.
  *                       LAUNCHES, BARRIERS and ELEVEN produce the same bits.
  *   DF3D_LSMR_AUTO      LOCAL where the problem fits, else LAUNCHES. */
 #define DF3D_LSMR_AUTO 0
