@@ -15,7 +15,7 @@
 //   * the only consumer of layer1's output is the 2x2 max-pool in front of layer2: with out == nullptr the kernel writes the
 //     pooled tensor only (the full-resolution tensor, 2/3 of the block's traffic, never exists).
 //
-// Same arithmetic as hg_kernels.h:bottleneck_kernel<bf16, 64, 64, true>: same K order in every accumulator (phase 1: 16-channel
+// Same arithmetic as hg_bt_reg.h:bottleneck_kernel<bf16, 64, 64, true>: same K order in every accumulator (phase 1: 16-channel
 // chunks ascending; phase 2: tap-major, chunks ascending; phase 3: bias b3 + bd, then W3 t2 in the host's K order, then Wd x),
 // products formed transposed where that only swaps the MFMA operands -- bit-identical results.
 //
@@ -23,7 +23,10 @@
 // the 16 lanes of a fragment read hit 16 different slots of the 256-byte bank row) | coefficients | masks.  The epilogue's
 // transposition slices (one per wave, 32 px x 64 channels at a time) reuse the t1 region.
 #pragma once
+#include "hg_bt_reg.h"
 #include "hg_bt_ring.h"
+#include "hg_pool.h"
+#include "hg_types.h"
 
 namespace hgk {
 
@@ -366,7 +369,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck_l1_kernel(BtL1Args p) {
                 if (pp) {
 #pragma unroll
                     for (int c = 0; c < 2; ++c) {   // pixels 8 c + (lane >> 3) of tile row 0 and the one below; the column partner sits 8 lanes away
-                        // in the ordered-integer domain (hg_kernels.h: bf16x2_key); lane ^ 8 = a rotation by 8 inside the row of 16: one DPP move
+                        // in the ordered-integer domain (hg_pool.h: bf16x2_key); lane ^ 8 = a rotation by 8 inside the row of 16: one DPP move
                         u32x4 m = bf16_key_max_chunk(bf16_key_chunk(fin[c]), bf16_key_chunk(fin[c + 2]));
                         u32x4 o;
 #pragma unroll

@@ -1,8 +1,8 @@
-// 16-bit (T = __hip_bfloat16 or _Float16: hg_kernels.h Lp<T>; "bf16" below stands for either) fused pre-activation bottleneck
+// 16-bit (T = __hip_bfloat16 or _Float16: hg_types.h Lp<T>; "bf16" below stands for either) fused pre-activation bottleneck
 // 256 -> 128 -> 128 -> 256 (identity skip) with the WEIGHTS streamed by LDS-DMA.
 //
 // Same tile (8 x 16 output pixels, 10 x 18 halo), same wave -> tile mapping, same MFMA K order as
-// hg_kernels.h:bottleneck_kernel<bf16, 256, 128, false, UP> -- the results are bit-identical -- but the 416 KB of
+// hg_bt_reg.h:bottleneck_kernel<bf16, 256, 128, false, UP> -- the results are bit-identical -- but the 416 KB of
 // weights a tile consumes (W1 64 KB, W2 288 KB, W3 64 KB: 2.7 x the activation bytes of the tile) no longer travel
 // global -> VGPR -> ds_write behind two barriers per K-step.  Instead:
 //
@@ -32,7 +32,9 @@
 #pragma once
 #include <type_traits>
 
-#include "hg_kernels.h"
+#include "hg_bt_reg.h"
+#include "hg_pool.h"
+#include "hg_types.h"
 #ifndef BR_ABLM
 #define BR_ABLM 0   // development builds: ablation mask (1 no MFMAs, 2 no weight DMA, 4 no x loads, 8 no residual loads, 16 no output stores, 512 no phase-2 MFMAs of the W2D form)
 #endif
@@ -127,50 +129,6 @@ __global__ __launch_bounds__(256) void bt_w2d_pack_kernel(const unsigned short* 
     *reinterpret_cast<u32x4*>(out + (size_t)idx * 16) = *reinterpret_cast<const u32x4*>(src);
 }
 
-// LDS-DMA of one 8 KB stage: this wave's two 1 KB pieces (lane l's 16 bytes land at dst + 16 l; dst wave-uniform, in M0).
-// sbase (uniform) + voff (per lane, 32 bit) is the source address.  The instruction's immediate offset is added to the
-// global address AND to the LDS address, so the second piece needs no second M0 value.  M0 is saved and restored inside
-// the statement.
-__device__ __forceinline__ void br_glds_stage(const void* sbase, unsigned voff, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(dst)
-                 : "memory");
-}
-// one 1 KB LDS-DMA piece: lane l's 16 bytes, read from sbase + voff (voff per lane, 32 bit), land at dst + 16 l (dst wave-uniform)
-__device__ __forceinline__ void br_glds_piece(const void* sbase, unsigned voff, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(dst)
-                 : "memory");
-}
-// the same with a full 64-bit address per lane (lanes of one piece may read from unrelated places)
-__device__ __forceinline__ void br_glds_piece64(const void* vaddr, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(vaddr), "s"(dst)
-                 : "memory");
-}
-// s_waitcnt vmcnt(n) for a value that is a compile-time constant after unrolling (the switch folds away)
-__device__ __forceinline__ void br_wait_vm(int n) {
-#define BR_W(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-    switch (n) {
-        BR_W(0) BR_W(1) BR_W(2) BR_W(3) BR_W(4) BR_W(5) BR_W(6) BR_W(7) BR_W(8) BR_W(9) BR_W(10) BR_W(11) BR_W(12) BR_W(13)
-        BR_W(14) BR_W(15) BR_W(16) BR_W(17) BR_W(18) BR_W(19) BR_W(20) BR_W(21) BR_W(22) BR_W(23) BR_W(24) BR_W(25) BR_W(26)
-        BR_W(27) BR_W(28) BR_W(29) BR_W(30) BR_W(31) BR_W(32) BR_W(33) BR_W(34) BR_W(35) BR_W(36) BR_W(37) BR_W(38) BR_W(39) BR_W(40)
-        BR_W(41) BR_W(42) BR_W(43) BR_W(44) BR_W(45) BR_W(46) BR_W(47) BR_W(48) BR_W(49) BR_W(50) BR_W(51) BR_W(52) BR_W(53) BR_W(54)
-        BR_W(55) BR_W(56) BR_W(57) BR_W(58) BR_W(59) BR_W(60) BR_W(61) BR_W(62) BR_W(63)
-        default:   // (the counter has six bits; a smaller count is always safe)
-            if (n > 63) asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            break;
-    }
-#undef BR_W
-}
 // 16-byte global store with a cache policy: 0 plain, 1 sc1 (written through, the line dropped from this XCD's L2), 2 nt (streaming), 3 sc0 sc1.
 // Measured in round 4 on the identity-skip kernel, same box: sc1 -0.7 %, nt -1.2 % of the kernel's time, HBM-side bytes unchanged; MODE 2 stores
 // nt (development switch BR_ST_POLICY >= 0 overrides the choice for every mode)

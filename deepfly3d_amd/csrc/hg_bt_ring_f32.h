@@ -1,7 +1,7 @@
 // fp32 fused pre-activation bottleneck 256 -> 128 -> 128 -> 256 (identity skip) with the weights streamed by LDS-DMA:
 // the fp32 sibling of hg_bt_ring.h (same 4-slot ring of 8 KB stage images, same swizzles, same barrier discipline).
 //
-// Same tile, wave -> tile mapping and MFMA K order as hg_kernels.h:bottleneck_kernel<float, 256, 128, false, UP>, whose
+// Same tile, wave -> tile mapping and MFMA K order as hg_bt_reg.h:bottleneck_kernel<float, 256, 128, false, UP>, whose
 // results it reproduces bit for bit.  As there, the t1 tile is built and consumed in two 64-channel halves (kh), so a tile
 // walks the stage sequence
 //     kh = 0:  8 x W1 (two 16-float K steps of the half's 64 rows per stage), 36 x W2 (tap, 16-float K slice of the half)
@@ -15,7 +15,9 @@
 // loads issued in between only make that wait conservative (steps are 1 500-2 000 cycles long, so that costs nothing).
 // gfx950 retires vector-memory operations in issue order (see hg_bt_ring.h).
 #pragma once
+#include "hg_bt_reg.h"
 #include "hg_bt_ring.h"
+#include "hg_types.h"
 
 #ifndef BRF_ABLM
 #define BRF_ABLM 0   // development builds (scripts/build_variant.sh): ablation mask of the fp32 / f32s ring kernels, see the uses below

@@ -32,7 +32,9 @@
 // Not bit-identical to the direct form (different products): the engine option `wino` selects it, the tests hold it to the
 // fp32 tolerance against the torch oracle on every plan step, and `wino=0` keeps the direct kernels as the bit-identity reference.
 #pragma once
+#include "hg_bt_reg.h"
 #include "hg_bt_ring_f32.h"
+#include "hg_types.h"
 
 #ifndef WN_ABL
 #define WN_ABL 0   // development builds (scripts/build_variant.sh): ablation mask -- phase 2: 1 no U loads, 2 no input transform, 4 no chunk barrier; the rest of a tile: 512 no patch reads, 1024 no V stores, 2048 no packed ops of the input transform; 16 no output transform, 32 no halo DMA for the next tile, 64 no residual / operand loads, 128 no output stores, 256 no phase-3 MFMAs

@@ -16,6 +16,7 @@
 // bn1 + ReLU -> LDS three K steps ahead, exactly like phase 1 of the fused kernel.
 #pragma once
 #include "hg_bt_ring_f32.h"
+#include "hg_types.h"
 
 namespace hgk {
 

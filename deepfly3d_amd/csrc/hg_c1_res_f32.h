@@ -16,6 +16,7 @@
 #pragma once
 #include "hg_bt_wino_f32.h"
 #include "hg_c1_f32.h"
+#include "hg_types.h"
 
 namespace hgk {
 

@@ -1,7 +1,8 @@
-// Fused stack head of the hourglass (fc -> score -> fc_ / score_ + skip), moved out of hg_kernels.h because its bf16 form takes
+// Fused stack head of the hourglass (fc -> score -> fc_ / score_ + skip), kept apart from the single-convolution kernels (hg_conv.h) because its bf16 form takes
 // Wfc through the LDS-DMA stage ring of hg_bt_ring.h.
 #pragma once
 #include "hg_bt_ring.h"
+#include "hg_types.h"
 
 namespace hgk {
 

@@ -6,7 +6,7 @@
 //                                          max-pool on 8 x 16 tiles; the t1 halo tile arrives by LDS-DMA, the weights through the
 //                                          4-slot LDS-DMA ring, the skip convolution's x operand straight from global memory
 //
-// It replaces hg_kernels.h:bottleneck_kernel<float, 64, 64, true> (register-staged weights, two barriers per K step, conv1
+// It replaces hg_bt_reg.h:bottleneck_kernel<float, 64, 64, true> (register-staged weights, two barriers per K step, conv1
 // recomputed on the halo: 122 TFLOP/s) and reproduces it bit for bit: same products in the same K order in every accumulator
 // (t2: bias, then tap-major, 8-float chunks ascending; out: b3 + bd, W3 over t2's channels ascending, then Wd over x's).
 //
@@ -15,7 +15,9 @@
 // A double-step (one barrier) consumes two stages = 64 MFMAs per wave; the next pair is requested right behind the barrier and
 // awaited with vmcnt(0) a whole double-step (4 096 MFMA cycles) later.
 #pragma once
+#include "hg_bt_reg.h"
 #include "hg_c1_f32.h"
+#include "hg_types.h"
 
 namespace hgk {
 

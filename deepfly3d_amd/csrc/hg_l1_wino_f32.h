@@ -9,7 +9,9 @@
 //     channel 4 l + i) so that outputs and pooled outputs move as 16-byte accesses; bias b3 + bd as one float add.
 // LDS: V 2 x 32 KB (ring later) | t1 halo 10 x 34 pixels x 256 B = 85 KB (t2 later) | b3 + bd [128], b2 [64].
 #pragma once
+#include "hg_bt_reg.h"
 #include "hg_bt_wino_f32.h"
+#include "hg_types.h"
 
 namespace hgk {
 

@@ -283,7 +283,7 @@ int launch_stem_step(const StepRun<T>& c, const Step& st) {
     a.out = c.tptr(st.out);
     a.w = h->blob + st.conv.w_off;
     // 16-bit: the [64][184] tile; f32s: the hi / lo half tiles in the stem's slot of the pre-split copy (stem_relayout_f32s_kernel)
-    a.w_bf16 = std::is_same<T, float>::value ? nullptr : c.weights(st.conv.w_off);
+    a.w_lp = std::is_same<T, float>::value ? nullptr : c.weights(st.conv.w_off);
     a.bias = h->blob + st.conv.b_off;
     a.V = c.n;
     a.H = h->H;
@@ -293,16 +293,16 @@ int launch_stem_step(const StepRun<T>& c, const Step& st) {
         a.u8.frames += (size_t)c.v0 * a.u8.FH * a.u8.FW * a.u8.FC;
         if (a.u8.flip) a.u8.flip += c.v0;
     }
-    const int blocks = c.n * (h->H / 2 / 8) * (h->W / 2 / 16);
+    const int blocks = c.n * (h->H / 2 / STEM_TH) * (h->W / 2 / STEM_TW);
     const double opx = (double)c.n * (h->H / 2) * (h->W / 2);
     const Work w{2.0 * opx * 147 * 64, opx * (12.0 * 4 + 64.0 * eb), c.m1(st)};
-    // persistent: the weights once per workgroup
+    // persistent: the weights once per workgroup; as many workgroups per CU as each kernel's LDS lets it hold (hg_stem.h)
     if constexpr (eb == 2) {
-        return launch_kernel<stem_lp_kernel<T>>(h, kname("stem_lp_kernel", TypeName<T>::value), w, dim3(std::min(blocks, 4 * cu_count())), 256, 0, c.s, a);
+        return launch_kernel<stem_lp_kernel<T>>(h, kname("stem_lp_kernel", TypeName<T>::value), w, dim3(std::min(blocks, STEM_LP_WGS_PER_CU * cu_count())), 256, 0, c.s, a);
     } else if constexpr (std::is_same<T, F32S>::value) {
-        return launch_kernel<stem_f32s_kernel>(h, kname("stem_f32s_kernel"), w, dim3(std::min(blocks, 2 * cu_count())), 256, 0, c.s, a);   // 57 KB of LDS: two per CU
+        return launch_kernel<stem_f32s_kernel>(h, kname("stem_f32s_kernel"), w, dim3(std::min(blocks, STEM_F32S_WGS_PER_CU * cu_count())), 256, 0, c.s, a);
     } else {
-        return launch_kernel<stem_kernel<T>>(h, kname("stem_kernel", TypeName<T>::value), w, dim3(std::min(blocks, 3 * cu_count())), 256, 0, c.s, a);
+        return launch_kernel<stem_kernel<T>>(h, kname("stem_kernel", TypeName<T>::value), w, dim3(std::min(blocks, STEM_F32_WGS_PER_CU * cu_count())), 256, 0, c.s, a);
     }
 }
 

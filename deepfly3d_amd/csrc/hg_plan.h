@@ -17,7 +17,11 @@
 #include <vector>
 
 #include "common.h"
-#include "hg_kernels.h"
+#include "hg_types.h"
+#include "hg_conv.h"
+#include "hg_stem.h"
+#include "hg_pool.h"
+#include "hg_bt_reg.h"
 #include "hg_bt_ring.h"
 #include "hg_bt_l1.h"
 #include "hg_head.h"
@@ -37,7 +41,7 @@ enum StepKind { ST_STEM, ST_CONV, ST_POOL, ST_UPADD, ST_BOTTLENECK, ST_HEAD };
 // The kernels an ST_BOTTLENECK step runs as, fixed when the plan is built.  The weight streams (Step::wstream*) each form reads, and
 // so the ones set_weights packs for it, are listed with it.
 enum BtForm {
-    BT_REG,         // bottleneck_kernel (hg_kernels.h): weights straight from the blob; no streams
+    BT_REG,         // bottleneck_kernel (hg_bt_reg.h): weights straight from the blob; no streams
     BT_L1_LP,       // 16-bit layer1, bottleneck_l1_kernel (hg_bt_l1.h): wstream = its LDS weight image
     BT_RING_LP,     // 16-bit identity block or layer2, bottleneck_ring_kernel (hg_bt_ring.h): wstream, wstream_w2 (option w2d)
     BT_RING_F32,    // fp32 / f32s identity block, unsplit: bottleneck_ring_f32_kernel (hg_bt_ring_f32.h): wstream
@@ -203,7 +207,7 @@ struct df3d_hg {
     bool lp() const { return dtype == DF3D_DTYPE_BF16 || dtype == DF3D_DTYPE_F16; }   // a 16-bit engine (bf16 or f16: same plan, same kernels, other element type)
     int elem_bytes() const { return lp() ? 2 : 4; }
     // byte offset of the weight streams in the caller's "lowp" buffer: behind the 16-bit copy of the blob (bf16 / f16), at its start (f32)
-    // (f32s: behind the pre-split float32 copy of the blob, hg_kernels.h f32s_presplit_kernel)
+    // (f32s: behind the pre-split float32 copy of the blob, hg_types.h f32s_presplit_kernel)
     size_t stream_base() const { return lp() ? (blob_floats * 2 + 255) & ~size_t(255) : dtype == DF3D_DTYPE_F32S ? (blob_floats * 4 + 255) & ~size_t(255) : 0; }
 
     // every step-creating site brackets its accounting: m1_open() before the first elems_per_view update that belongs to the
@@ -331,7 +335,7 @@ struct df3d_hg {
             x2 = -1;
         }
         if (fused_here) {
-            // the whole block in one kernel (hg_kernels.h: bottleneck_kernel); algorithmic work is accounted
+            // the whole block in one kernel (hg_bt_reg.h: bottleneck_kernel); algorithmic work is accounted
             // exactly as for the separate convolutions (model M1), although far fewer bytes really move
             const bool ds = cin != cout;
             m1_open();
@@ -515,7 +519,7 @@ struct df3d_hg {
         // stem
         Step st = new_step(ST_STEM, "conv1", -1, -1);
         st.conv = ConvPlan{49, 3, 64, 3, 64, false, true, false, 0, 0, 0, 0};
-        st.conv.w_off = add_param("conv1", 0, 49, 3, 64, 3, 64, 64 * 184);  // [148][64] f32 used; slot sized for the bf16 [64][184] tile
+        st.conv.w_off = add_param("conv1", 0, 49, 3, 64, 3, 64, STEM_LP_TILE_ELEMS);  // [148][64] f32 used; slot sized for the 16-bit [64][184] tile (hg_stem.h)
         st.conv.b_off = add_param("conv1", 1, 49, 3, 64, 3, 64, 64);
         st.out = new_tensor(H / 2, W / 2, 64);
         m1_open();

@@ -133,7 +133,7 @@ int df3d_hg_set_weights(df3d_hg* h, const float* blob_dev, void* lowp_dev, hipSt
             if constexpr (sizeof(T) == 2) {
                 unsigned short* const copy = reinterpret_cast<unsigned short*>(lowp_dev);
                 hipLaunchKernelGGL((f32_to_lp_kernel<T>), dim3(1024), dim3(256), 0, s, blob_dev, copy, h->blob_floats);
-                hipLaunchKernelGGL((stem_relayout_kernel<T>), dim3((64 * 184 + 255) / 256), dim3(256), 0, s, blob_dev + h->steps[0].conv.w_off,
+                hipLaunchKernelGGL((stem_relayout_kernel<T>), dim3(STEM_RELAYOUT_BLOCKS), dim3(256), 0, s, blob_dev + h->steps[0].conv.w_off,
                                    copy + h->steps[0].conv.w_off);
             }
         });
@@ -152,13 +152,13 @@ int df3d_hg_set_weights(df3d_hg* h, const float* blob_dev, void* lowp_dev, hipSt
     } else if (h->stream_bytes || h->dtype == DF3D_DTYPE_F32S) {
         DF3D_CHECK_ARG((reinterpret_cast<uintptr_t>(lowp_dev) & 255) == 0, "lowp buffer must be 256-byte aligned");
         if (h->dtype == DF3D_DTYPE_F32S) {
-            // f32s: the weights pre-split per 16-float K step (hg_kernels.h f32s_presplit_kernel) -- a float32-sized copy of the blob in front of
+            // f32s: the weights pre-split per 16-float K step (hg_types.h f32s_presplit_kernel) -- a float32-sized copy of the blob in front of
             // the streams; the packers below then read THAT copy (they move whole 16-byte chunks and keep a chunk's index inside its step).
             // Biases and BatchNorm vectors are transformed along with the rest and never read from the copy.
             hipLaunchKernelGGL(f32s_presplit_kernel, dim3(1024), dim3(256), 0, s, reinterpret_cast<const u32x4*>(blob_dev),
                                reinterpret_cast<u32x4*>(lowp_dev), h->blob_floats / 16);
-            // the stem's weights: two half-precision [64][184] tiles (hi, lo) in its slot of the copy (exactly the slot's 47 104 bytes)
-            hipLaunchKernelGGL(stem_relayout_f32s_kernel, dim3((64 * 184 + 255) / 256), dim3(256), 0, s, blob_dev + h->steps[0].conv.w_off,
+            // the stem's weights: two half-precision [64][184] tiles (hi, lo) in its slot of the copy (exactly the slot's STEM_F32S_W_BYTES)
+            hipLaunchKernelGGL(stem_relayout_f32s_kernel, dim3(STEM_RELAYOUT_BLOCKS), dim3(256), 0, s, blob_dev + h->steps[0].conv.w_off,
                                reinterpret_cast<unsigned short*>(reinterpret_cast<float*>(lowp_dev) + h->steps[0].conv.w_off));
             blob_dev = reinterpret_cast<const float*>(lowp_dev);   // (restored below: h->blob stays the caller's float32 blob)
         }

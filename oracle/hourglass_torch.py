@@ -215,17 +215,17 @@ class Arith:
     """The engine's arithmetic for forward_traced: parameters as the engine stores them, evaluated in `dtype`.
 
     storage "f32" (the f32 / f32s engines): no rounding inside a convolution; pools and up-adds round to float32.
-    storage "bf16" / "f16": the operand-rounding model of deepfly3d_amd/csrc/hg_kernels.h -- conversions are
-    round-to-nearest-even (hg_kernels.h:62, Lp<T>::from_f32 / pack2), the pre-activation is fmaxf(fmaf(x, s, t), 0)
-    rounded to T (hg_kernels.h:159-168; hg_kernels.h:1329 for the up-add input), weights are the float32 blob
-    rounded to T (hg_kernels.h:1143), the stem's image patch is rounded to T (stem_lp_kernel, hg_kernels.h:696),
+    storage "bf16" / "f16": the operand-rounding model of deepfly3d_amd/csrc/hg_types.h -- conversions are
+    round-to-nearest-even (hg_types.h:27, Lp<T>::from_f32 / pack2), the pre-activation is fmaxf(fmaf(x, s, t), 0)
+    rounded to T (hg_types.h:124-133; hg_bt_reg.h:186 for the up-add input), weights are the float32 blob
+    rounded to T (hg_pool.h:122), the stem's image patch is rounded to T (stem_lp_kernel, hg_stem.h),
     accumulation is exact here (fp32 on the device), and a single-convolution step stores round_T(accumulator + bias (+ residual)).
     Roundings inside fused kernels, made at the same points:
-      * bottleneck kernels (hg_kernels.h bottleneck_kernel, hg_bt_ring.h, hg_bt_l1.h): t1 and t2 are T operands of the next
-        GEMM (rounded); the downsample is summed into conv3's accumulator (hg_kernels.h:1454-1462, bias b3 + bd) and NOT
-        rounded on its own; with an identity skip the output is round_T(round_T(accumulator + bias) + x) (hg_bt_ring.h:752-765,
-        hg_kernels.h:1655-1672: the accumulator is packed to T, then add_chunk adds the residual and rounds again);
-      * ADD2 epilogue (fuse_upadd=1): the rounded block output + the low-resolution tensor, rounded again (hg_kernels.h:1674);
+      * bottleneck kernels (hg_bt_reg.h bottleneck_kernel, hg_bt_ring.h, hg_bt_l1.h): t1 and t2 are T operands of the next
+        GEMM (rounded); the downsample is summed into conv3's accumulator (hg_bt_reg.h:311-319, bias b3 + bd) and NOT
+        rounded on its own; with an identity skip the output is round_T(round_T(accumulator + bias) + x) (hg_bt_ring.h:710-723,
+        hg_bt_reg.h:512-529: the accumulator is packed to T, then add_chunk adds the residual and rounds again);
+      * ADD2 epilogue (fuse_upadd=1): the rounded block output + the low-resolution tensor, rounded again (hg_bt_reg.h:531);
       * head_kernel (hg_head.h:317, 430): y and score are rounded to T as operands; x_new = round_T(x + fc_(y) + score_(score))
         from ONE accumulator (hg_head.h:505-517), so fc_'s sum is not rounded when it is not a step of its own;
       * the final heat-maps are float32 planes: score of the last stack is never rounded to T.
@@ -325,7 +325,7 @@ def forward_traced(net, images_nhwc, forced=None, arith=None, steps=None):
         else:   # fused: summed into conv3's accumulator unrounded; unfused: a stored step, forced
             skip = keep(ds, layer(ds, operand(x), rnd=ds in stored, inputs=(x,)))
         # the fused bottleneck with an identity skip rounds conv3's accumulator (bias included) to T, then adds the skip and
-        # rounds again: hg_bt_ring.h:752-765 and hg_kernels.h:1655-1672 (Lp<T>::pack2 into the epilogue slice, then add_chunk);
+        # rounds again: hg_bt_ring.h:710-723 and hg_bt_reg.h:512-529 (Lp<T>::pack2 into the epilogue slice, then add_chunk);
         # the single-convolution kernel adds the residual to the accumulator (one rounding)
         twice = A.storage != "f32" and b.downsample is None and name + ".conv2" not in stored
         return keep(name + ".conv3", layer(name + ".conv3", operand(t), skip=skip, skip_in_acc=ds not in stored, round_before_skip=twice,
