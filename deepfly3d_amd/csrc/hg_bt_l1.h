@@ -23,6 +23,7 @@
 // the 16 lanes of a fragment read hit 16 different slots of the 256-byte bank row) | coefficients | masks.  The epilogue's
 // transposition slices (one per wave, 32 px x 64 channels at a time) reuse the t1 region.
 #pragma once
+#include "hg_bt_common.h"
 #include "hg_bt_reg.h"
 #include "hg_bt_ring.h"
 #include "hg_pool.h"
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(512, 1) void bottleneck_l1_kernel(BtL1Args p) {
     unsigned char* const t1_lds = smem + L1_W_BYTES;
     float* const coef_lds = reinterpret_cast<float*>(smem + L1_W_BYTES + L1_T1_BYTES);   // [0..63] s1 [64..127] t1 [128..191] b1 [192..255] b2 [256..383] b3 + bd
     unsigned long long* const valid_lds = reinterpret_cast<unsigned long long*>(smem + L1_W_BYTES + L1_T1_BYTES + L1_COEF_FLOATS * 4);
-    const unsigned w_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)w_lds;
+    const unsigned w_addr = lds_addr(w_lds);
 
     const int tid = threadIdx.x, lane = tid & 63;
 #ifdef DF3D_BT_TIMING

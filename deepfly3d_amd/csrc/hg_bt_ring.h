@@ -32,6 +32,7 @@
 #pragma once
 #include <type_traits>
 
+#include "hg_bt_common.h"
 #include "hg_bt_reg.h"
 #include "hg_pool.h"
 #include "hg_types.h"
@@ -63,27 +64,19 @@ struct BtRingArgs {
     int V, H, W;
 };
 
-constexpr int BR_STAGE_BYTES = 8192;                     // 128 rows x 64 bytes (32 bf16 of K)
-constexpr int BR_RING = 4;
+// (the stage image, ring and t1 tile geometry -- BR_STAGE_BYTES, BR_RING, BR_T1_PITCH, br_swz, br_t1_swz -- is hg_bt_common.h's)
 constexpr int BR_W1_STAGES = 8, BR_W2_STAGES = 36, BR_W3_STAGES = 8;
 constexpr int BR_NSTAGE = BR_W1_STAGES + BR_W2_STAGES + BR_W3_STAGES;   // 52
-constexpr int BR_T1_PITCH = 128 * 2;                    // bytes per halo pixel of the t1 tile: no padding, 16-byte chunks XOR-swizzled
-constexpr int BR_T1_BYTES = BT_HALO * BR_T1_PITCH;      // 46 080 (the 12 pad rows of the sixth MFMA row tile are not stored)
 constexpr int BR_XPITCH = 64;                           // staged x rows: one 64-byte K step, no padding: 16-byte chunk c of row r sits in slot
                                                         // c ^ ((r >> 2) & 3) (br_xslot), which makes the 32-row fragment reads and the row-pair
                                                         // stores bank-conflict-free (round 3: the padded 80-byte rows cost 13-15 % of the LDS cycles)
 constexpr int BR_XSTAGE = BT_HROWS * BR_XPITCH;         // 12 288; three of them inside the t1 region
-constexpr int BR_RING_BYTES = BR_RING * BR_STAGE_BYTES;
 constexpr int BR_COEF_BYTES = 512 * 4 + 128 * 4;        // phase 1: bn1 scale [256] | shift [256]; afterwards b2 [128] | b3 [256]; then b1 [128]
 constexpr int BR_LDS_BYTES = BR_RING_BYTES + BR_T1_BYTES + BR_COEF_BYTES + 64;
-// chunk k (8 channels) of halo pixel hp sits in 16-byte slot k ^ ((hp % 18) & 15) of its 256-byte row: the 16 lanes of a
-// ds_read_b128 lane group read 16 different tile columns, hence 16 different slots
-__device__ __forceinline__ int br_t1_swz(int hp) { return (hp % BT_HW) & 15; }
 static_assert(3 * BR_XSTAGE <= BR_T1_BYTES, "the x ring lives inside the t1 region");
 static_assert(2 * BR_LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 
 __device__ __forceinline__ int br_xslot(int row, int chunk) { return ((chunk ^ ((row >> 2) & 3)) << 4); }   // byte offset inside a staged x row
-__host__ __device__ constexpr int br_swz(int r, int c) { return (r >> 2) * 256 + (((((r & 3) << 2) | c) ^ ((r >> 3) & 3)) << 4); }
 
 // stages of one bottleneck's stream: W1 (CIN / 32) | W2 (36) | per 128-channel output half: W3 (4) and, with the 1x1 skip
 // convolution (DS: CIN != 256), Wd (CIN / 32)
@@ -147,8 +140,6 @@ __device__ __forceinline__ void br_store16(void* dst, u32x4 v) {
                    // first output half's K loop, 5 after its epilogue, 6 after the second half's K loop): where an ablated kernel's time goes, by wall clock
 #endif
 #define BR_CHECKPOINT(n) do { if (BR_RET == n && p.V > 0) return; } while (0)
-// workgroup barrier that does NOT drain the vector-memory queue (a __syncthreads() beside pending LDS-DMA waits vmcnt(0))
-__device__ __forceinline__ void br_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // max(x, 0) on two packed 16-bit floats (bf16 or half: both are sign-magnitude): as signed 16-bit integers a negative float is a negative integer, so one v_pk_max_i16 does
 // both halves (and needs no NaN-canonicalising v_max before it, which hipcc puts in front of every fmaxf on an MFMA result).
@@ -220,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_ring_kernel(BtRingArgs p) {
     unsigned char* const t1_lds = smem + BR_RING_BYTES;
     float* const coef_lds = reinterpret_cast<float*>(smem + BR_RING_BYTES + BR_T1_BYTES);
     unsigned long long* const valid_lds = reinterpret_cast<unsigned long long*>(smem + BR_RING_BYTES + BR_T1_BYTES + BR_COEF_BYTES);
-    const unsigned ring_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)ring;
+    const unsigned ring_addr = lds_addr(ring);
 
     const int tid = threadIdx.x, lane = tid & 63;
 #ifdef DF3D_BT_TIMING
@@ -232,17 +223,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck_ring_kernel(BtRingArgs p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
     const int tiles_x = p.W / BT_TW, tiles_y = p.H / BT_TH;
-    // XCD-aware tile order (speed only): workgroup b runs on XCD b % 8, so XCD x takes the x-th contiguous eighth of the tiles and
-    // the 64 workgroups resident on it work on neighbouring tiles, whose halos then meet in that XCD's L2 (bijective for any grid)
-    int b;
-    {
-        const int nwg = gridDim.x, xcd = blockIdx.x & 7, q = nwg >> 3, r = nwg & 7;
-        b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
-    const int tx0 = (b % tiles_x) * BT_TW;
-    b /= tiles_x;
-    const int ty0 = (b % tiles_y) * BT_TH;
-    const int view = b / tiles_y;
+    const BtTile tile = bt_tile<BT_TW, BT_TH>(blockIdx.x, (int)gridDim.x, tiles_x, tiles_y);   // XCD-aware order
+    const int tx0 = tile.tx0, ty0 = tile.ty0, view = tile.view;
     const unsigned char* const xin = reinterpret_cast<const unsigned char*>(p.in) + (size_t)view * p.H * p.W * CIN * 2;
     const unsigned char* const xin2 = UP ? reinterpret_cast<const unsigned char*>(p.in2) + (size_t)view * (p.H / 2) * (p.W / 2) * CIN * 2
                                     : ADD2 ? reinterpret_cast<const unsigned char*>(p.add2) + (size_t)view * (p.H / 2) * (p.W / 2) * CO * 2 : nullptr;
@@ -251,6 +233,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_ring_kernel(BtRingArgs p) {
     const unsigned wvoff = (unsigned)wave * 2048u + (unsigned)lane * 16u;
     auto ring_issue = [&](int s) {   // stage s -> ring slot s % 4; this wave copies pieces 2 wave, 2 wave + 1
         if (BR_ABLM & 2) return;   // (ablation mask, development builds only: no weight DMA)
+        // (written out, destination first: br_ring_issue forms the source address first, which orders this kernel's scalar adds otherwise)
         const unsigned dst = ring_addr + (unsigned)(s % BR_RING) * BR_STAGE_BYTES + (unsigned)wave * 2048;
         const int si = (W2D && s >= NS1) ? s + BR_W2_STAGES : s;   // W2D: the ring sequence is W1 | W3 (| Wd), the stream keeps W2 in between
         br_glds_stage(reinterpret_cast<const unsigned char*>(p.wstream) + (size_t)si * BR_STAGE_BYTES, wvoff, dst);

@@ -15,6 +15,7 @@
 // loads issued in between only make that wait conservative (steps are 1 500-2 000 cycles long, so that costs nothing).
 // gfx950 retires vector-memory operations in issue order (see hg_bt_ring.h).
 #pragma once
+#include "hg_bt_common.h"
 #include "hg_bt_reg.h"
 #include "hg_bt_ring.h"
 #include "hg_types.h"
@@ -56,17 +57,9 @@ __global__ __launch_bounds__(256) void bt_ring_pack_f32_kernel(const float* __re
     *reinterpret_cast<u32x4*>(stream + (size_t)s * BR_STAGE_BYTES + dst) = *reinterpret_cast<const u32x4*>(src);
 }
 
-// max(x, 0) without the NaN-canonicalising v_max hipcc puts in front of fmaxf on MFMA results: as a signed integer a negative
-// float is negative, so v_max_i32(bits, 0) is the ReLU (-0 -> +0).  A builtin, not inline assembly -- see br_relu_pk.
-__device__ __forceinline__ float br_relu(float x) {
-    const int b = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, b > 0 ? b : 0);
-}
-
 // TAIL (hg_c1_f32.h): phase 1 is not computed here -- t1 = relu(W1' relu(bn1 x) + b1') was written to HBM for every pixel by
-// conv1_ring_f32_kernel and its 10 x 18 halo tile arrives by LDS-DMA, one 64-channel half at a time (lane -> (halo pixel,
-// 16-byte slot), fetching the chunk that belongs in that slot of the swizzled tile; halo pixels outside the image fetch from a
-// page of zeros = the 3x3 convolution's padding).  The W1 stages of the stream are skipped: the tail walks 88 of the 104.
+// conv1_ring_f32_kernel and its 10 x 18 halo tile arrives by LDS-DMA, one 64-channel half at a time (hg_bt_common.h bt_t1_issue).
+// The W1 stages of the stream are skipped: the tail walks 88 of the 104.
 template <bool UP, bool ADD2 = false, bool TAIL = false, typename T = float>   // T: float (exact-fp32 MFMA) or F32S (the same kernel, split products)
 __global__ __launch_bounds__(256, 2) void bottleneck_ring_f32_kernel(BtRingArgs p) {
     static_assert(!(UP && ADD2), "the fused up-path sum is written by plain blocks");
@@ -76,7 +69,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_ring_f32_kernel(BtRingArgs 
     unsigned char* const t1_lds = smem + BR_RING_BYTES;
     float* const coef_lds = reinterpret_cast<float*>(smem + BR_RING_BYTES + BR_T1_BYTES);   // [0..255] bn1 scale, [256..511] shift (later b3), [512..639] b1
     unsigned long long* const valid_lds = reinterpret_cast<unsigned long long*>(smem + BR_RING_BYTES + BR_T1_BYTES + BR_COEF_BYTES);
-    const unsigned ring_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)ring;
+    const unsigned ring_addr = lds_addr(ring);
 
     const int tid = threadIdx.x, lane = tid & 63;
 #ifdef DF3D_BT_TIMING
@@ -85,17 +78,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck_ring_f32_kernel(BtRingArgs 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
     const int tiles_x = p.W / BT_TW, tiles_y = p.H / BT_TH;
-    // XCD-aware tile order (speed only): workgroup b runs on XCD b % 8, so XCD x takes the x-th contiguous eighth of the tiles and
-    // the 64 workgroups resident on it work on neighbouring tiles, whose halos then meet in that XCD's L2 (bijective for any grid)
-    int b;
-    {
-        const int nwg = gridDim.x, xcd = blockIdx.x & 7, q = nwg >> 3, r = nwg & 7;
-        b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
-    const int tx0 = (b % tiles_x) * BT_TW;
-    b /= tiles_x;
-    const int ty0 = (b % tiles_y) * BT_TH;
-    const int view = b / tiles_y;
+    const BtTile tile = bt_tile<BT_TW, BT_TH>(blockIdx.x, (int)gridDim.x, tiles_x, tiles_y);   // XCD-aware order
+    const int tx0 = tile.tx0, ty0 = tile.ty0, view = tile.view;
     const unsigned char* const xin = reinterpret_cast<const unsigned char*>(p.in) + (size_t)view * p.H * p.W * CIN * 4;
     const unsigned char* const xin2 = UP ? reinterpret_cast<const unsigned char*>(p.in2) + (size_t)view * (p.H / 2) * (p.W / 2) * CIN * 4 : nullptr;
 
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_ring_f32_kernel(BtRingArgs 
     auto stream_index = [](int q) { return !TAIL ? q : q < BRF_W2_STAGES ? BRF_W1_STAGES + q : q < 2 * BRF_W2_STAGES ? 2 * BRF_W1_STAGES + q : 2 * BRF_W1_STAGES + q; };
     auto ring_issue = [&](int q) {   // this wave copies pieces 2 wave, 2 wave + 1
         if ((BRF_ABLM & 2) && q >= 3) return;   // (ablation mask 2: no weight DMA after the prologue's stages)
-        if (q < NQ) {
+        if (q < NQ) {   // (written out, destination first: br_ring_issue forms the source address first, which orders this kernel's scalar adds otherwise)
             const unsigned dst = ring_addr + (unsigned)(q % BR_RING) * BR_STAGE_BYTES + (unsigned)wave * 2048;
             br_glds_stage(reinterpret_cast<const unsigned char*>(p.wstream) + (size_t)stream_index(q) * BR_STAGE_BYTES, wvoff, dst);
         }
@@ -115,27 +99,10 @@ __global__ __launch_bounds__(256, 2) void bottleneck_ring_f32_kernel(BtRingArgs 
     const unsigned char* const wf1 = ring + br_swz(l31, 2 + half);
 
     // coefficients -> LDS, t2 start values (b2) straight into the accumulators, b3 waits in a register until bn1 is dead
-    // TAIL: the t1 halo tile of half kh by LDS-DMA.  Piece pc (1 KB) = halo pixels 4 pc .. 4 pc + 3, lane -> (pixel 4 pc + (lane >> 4),
-    // slot lane & 15), fetching chunk slot ^ swizzle(pixel) of that pixel's 256-byte half row; this wave copies pieces wave, wave + 4, ...
-    const unsigned t1_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)t1_lds;
+    // TAIL: the t1 halo tile of half kh by LDS-DMA
+    const unsigned t1_addr = lds_addr(t1_lds);
     auto t1_issue = [&](int kh) {
-#ifdef BRF_NO_T1DMA   // development builds: the tail without its t1 halo DMA (what that traffic and its exposed latency cost)
-        return;
-#endif
-        const unsigned char* const tin = reinterpret_cast<const unsigned char*>(p.t1in) + (size_t)view * p.H * p.W * 512;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            const int pc = wave + 4 * k;
-            if (pc < BT_HALO / 4) {
-                const int hp = 4 * pc + (lane >> 4);
-                const int hy = hp / BT_HW, hx = hp % BT_HW;
-                const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
-                const bool ok = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-                const unsigned chunk = (unsigned)((lane & 15) ^ br_t1_swz(hp));
-                const unsigned char* const src = ok ? tin + ((size_t)y * p.W + x) * 512 + kh * 256 + chunk * 16 : reinterpret_cast<const unsigned char*>(p.zeros) + chunk * 16;
-                br_glds_piece64(src, t1_addr + (unsigned)pc * 1024u);
-            }
-        }
+        bt_t1_issue<BT_HW, BT_HALO, 512>(reinterpret_cast<const unsigned char*>(p.t1in) + (size_t)view * p.H * p.W * 512, p.zeros, tx0, ty0, p.H, p.W, kh * 256, t1_addr, wave, lane);
     };
     if constexpr (TAIL) t1_issue(0);   // first of all: its latency runs under the rest of the prologue (nobody else touches the t1 region yet)
     // (loaded now, stored to LDS behind the first DMA requests: a store in front of them would make the wave sit out the

@@ -32,6 +32,7 @@
 // Not bit-identical to the direct form (different products): the engine option `wino` selects it, the tests hold it to the
 // fp32 tolerance against the torch oracle on every plan step, and `wino=0` keeps the direct kernels as the bit-identity reference.
 #pragma once
+#include "hg_bt_common.h"
 #include "hg_bt_reg.h"
 #include "hg_bt_ring_f32.h"
 #include "hg_types.h"
@@ -163,37 +164,6 @@ __device__ __forceinline__ void wn_xload4s(f32x4 (&d)[4], const void* sbase, uns
                  : "memory");
 }
 
-// The F(2x2, 3x3) input transform of one (patch, channel) -- layer1_wino_f32_kernel's (hg_l1_wino_f32.h; its U' = s_i s_j U with s_2 = -1):
-// V' = B'^T d B' as SIXTEEN packed adds in one statement (one VALU clump per chunk).
-// In: P[b] = (d[0][b], d[1][b]), Q[b] = (d[2][b], d[3][b]) -- the register pairs the two ds_read2st64_b32 of patch column b deliver.
-// Rows first: per column b,  T[b] = (d0 - d2, d1 + d2),  S[b] = (d1 - d2, d1 - d3)   [row 2 with the opposite sign: see bt_wino_pack_kernel];
-// then columns, on whole pairs: j = 0: X0 - X2, 1: X1 + X2, 2: X1 - X2 (opposite sign), 3: X1 - X3 for X = T (rows 0, 1) and X = S (rows 2, 3).
-// Out: VT[j] = (V'[0][j], V'[1][j]), VS[j] = (V'[2][j], V'[3][j]).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void wn_transform(const f32x2 (&P)[4], const f32x2 (&Q)[4], f32x2 (&VT)[4], f32x2 (&VS)[4]) {
-    f32x2 T0, T1, T2, T3, S0, S1, S2, S3;
-    asm volatile(
-        "v_pk_add_f32 %8, %16, %20 op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
-        "v_pk_add_f32 %12, %16, %20 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"
-        "v_pk_add_f32 %9, %17, %21 op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
-        "v_pk_add_f32 %13, %17, %21 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"
-        "v_pk_add_f32 %10, %18, %22 op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
-        "v_pk_add_f32 %14, %18, %22 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"
-        "v_pk_add_f32 %11, %19, %23 op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
-        "v_pk_add_f32 %15, %19, %23 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"
-        "v_pk_add_f32 %0, %8, %10 neg_lo:[0,1] neg_hi:[0,1]\n\t"
-        "v_pk_add_f32 %1, %9, %10\n\t"
-        "v_pk_add_f32 %2, %9, %10 neg_lo:[0,1] neg_hi:[0,1]\n\t"
-        "v_pk_add_f32 %3, %9, %11 neg_lo:[0,1] neg_hi:[0,1]\n\t"
-        "v_pk_add_f32 %4, %12, %14 neg_lo:[0,1] neg_hi:[0,1]\n\t"
-        "v_pk_add_f32 %5, %13, %14\n\t"
-        "v_pk_add_f32 %6, %13, %14 neg_lo:[0,1] neg_hi:[0,1]\n\t"
-        "v_pk_add_f32 %7, %13, %15 neg_lo:[0,1] neg_hi:[0,1]"
-        : "=&v"(VT[0]), "=&v"(VT[1]), "=&v"(VT[2]), "=&v"(VT[3]), "=&v"(VS[0]), "=&v"(VS[1]), "=&v"(VS[2]), "=&v"(VS[3]),
-          "=&v"(T0), "=&v"(T1), "=&v"(T2), "=&v"(T3), "=&v"(S0), "=&v"(S1), "=&v"(S2), "=&v"(S3)
-        : "v"(P[0]), "v"(P[1]), "v"(P[2]), "v"(P[3]), "v"(Q[0]), "v"(Q[1]), "v"(Q[2]), "v"(Q[3]));
-}
-
 // L2: fp32 layer2 (128 -> 128 -> 128 -> 256 with a 1x1 SKIP CONVOLUTION instead of the identity skip): the same phases 1-2 on its t1, and in
 // phase 3 the skip convolution accumulated into the same accumulators behind W3 (as layer2_tail_f32_kernel does): per output half eight more ring
 // stages (Wd, rows permuted like W3's) whose A operand is the raw x of the lane's pixel, prefetched from global memory in MFMA layout; no residual.
@@ -208,54 +178,26 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
     unsigned char* const t1_lds = smem + WN_T1_OFF;
     float* const b3_lds = reinterpret_cast<float*>(smem + WN_B3_OFF);
     float* const b2_lds = b3_lds + 256;
-    const unsigned ring_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)ring;
-    const unsigned t1_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)t1_lds;
+    const unsigned ring_addr = lds_addr(ring), t1_addr = lds_addr(t1_lds);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tiles_x = p.W / BT_TW, tiles_y = p.H / BT_TH;
     const int ntiles = p.V * tiles_y * tiles_x;
     // PERSISTENT: one workgroup per CU walks tiles vb = blockIdx.x, + gridDim.x, ... (a single resident workgroup has nobody to hide its
-    // prologue behind: the next tile's t1 halo is requested while this tile's phase 3 runs).  XCD-aware order as in bottleneck_ring_f32_kernel:
+    // prologue behind: the next tile's t1 halo is requested while this tile's phase 3 runs).  XCD-aware order (hg_bt_common.h bt_tile):
     // virtual block vb runs on XCD vb % 8 (the grid is a multiple of 8, or one tile per workgroup) and XCD x takes the x-th contiguous eighth.
     auto tile_of = [&](int vb, int& tx0, int& ty0, int& view) {
-        const int xcd = vb & 7, q = ntiles >> 3, r = ntiles & 7;
-        int b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-        tx0 = (b % tiles_x) * BT_TW;
-        b /= tiles_x;
-        ty0 = (b % tiles_y) * BT_TH;
-        view = b / tiles_y;
+        const BtTile t = bt_tile<BT_TW, BT_TH>(vb, ntiles, tiles_x, tiles_y);
+        tx0 = t.tx0, ty0 = t.ty0, view = t.view;
     };
-    // the t1 halo tile by LDS-DMA, both 64-channel halves (hg_bt_ring_f32.h t1_issue; half kh at t1 + kh * BR_T1_BYTES)
+    // the t1 halo tile by LDS-DMA, both 64-channel halves (hg_bt_common.h bt_t1_issue_persistent; half kh at t1 + kh * BR_T1_BYTES)
     // ONE lane-derived register lives across phase 2 (uoff, the U loads' lane offset, opaque to the compiler); whatever else a tile derives from the
     // lane index is recomputed from it where it is needed -- kept alive, `lane` itself sat in scratch and every reload was a vmcnt(0)
     unsigned uoff = (unsigned)(lane * 16);
     asm volatile("" : "+v"(uoff));
     auto t1_issue = [&](int tx0, int ty0, int view) {
-        // the per-piece lane values (halo pixel, swizzled chunk) and the per-piece uniform values (piece index, LDS address) are recomputed at every
-        // call: hoisted out of the tile loop they are ~70 registers and ~50 spill lanes alive across phase 2 (the empty asms hide their loop invariance)
-        int lane_ = (int)(uoff >> 4);
-        asm volatile("" : "+v"(lane_));
-        int wave_ = wave;
-        asm volatile("" : "+s"(wave_));
-        const unsigned char* const tin = reinterpret_cast<const unsigned char*>(p.t1in) + (size_t)view * p.H * p.W * 512;
-        const unsigned char* const zer = reinterpret_cast<const unsigned char*>(p.zeros);
-        const int q = lane_ >> 4, slot = lane_ & 15;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            const int pc = wave_ + 4 * k;
-            if (pc < BT_HALO / 4) {
-                const int hp = 4 * pc + q;
-                const int hy = hp / BT_HW, hx = hp - hy * BT_HW;
-                const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
-                const bool ok = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-                const unsigned c16 = (unsigned)((slot ^ (hx & 15)) << 4);               // br_t1_swz(hp) = hx & 15
-                const unsigned in_view = (unsigned)((y * p.W + x) * 512) + c16;         // (a view's t1 is < 4 GB: 32-bit offsets, ONE 64-bit add per piece)
-                const unsigned char* const base = ok ? tin : zer;                       // pixels outside the image: the 256 zero bytes
-                br_glds_piece64(base + (ok ? in_view : c16), t1_addr + (unsigned)(pc * 1024));
-                br_glds_piece64(base + (ok ? in_view + 256u : c16), t1_addr + (unsigned)(BR_T1_BYTES + pc * 1024));
-            }
-        }
+        bt_t1_issue_persistent<BT_HW, BT_HALO, 512, 2>(p.t1in, p.zeros, view, tx0, ty0, p.H, p.W, t1_addr, wave, uoff);
     };
 
 
@@ -372,8 +314,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
         asm volatile("" : "+v"(wvoff));   // (per call: not one more register across phase 2)
 #pragma unroll
         for (int k = 8 * set; k < 8 * set + 8; ++k)
-            br_glds_stage(reinterpret_cast<const unsigned char*>(p.w2d) + WN_U_BYTES + (size_t)k * BR_STAGE_BYTES, wvoff,
-                          ring_addr + (unsigned)ring_slot(k) + (unsigned)wave * 2048);
+            br_ring_issue(reinterpret_cast<const unsigned char*>(p.w2d) + WN_U_BYTES, k, ring_addr + (unsigned)ring_slot(k), wave, wvoff);
     };
 
 #ifdef DF3D_BT_TIMING

@@ -15,6 +15,7 @@
 // W1' streams through the 4-slot LDS-DMA ring as 16 stages (K slice of 16 floats x 128 rows); x is staged global -> registers ->
 // bn1 + ReLU -> LDS three K steps ahead, exactly like phase 1 of the fused kernel.
 #pragma once
+#include "hg_bt_common.h"
 #include "hg_bt_ring_f32.h"
 #include "hg_types.h"
 
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void conv1_ring_f32_kernel(Conv1Args p) {
     unsigned char* const ring = smem;
     unsigned char* const xr = smem + BR_RING_BYTES;
     float* const coef_lds = reinterpret_cast<float*>(smem + BR_RING_BYTES + C1_XSLOTS * C1_XSTAGE);   // [0..255] scale, [256..511] shift, [512..639] b1
-    const unsigned ring_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)ring;
+    const unsigned ring_addr = lds_addr(ring);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -88,8 +89,7 @@ __global__ __launch_bounds__(256, 2) void conv1_ring_f32_kernel(Conv1Args p) {
     auto ring_issue = [&](int s) {   // stage s (the same for every tile) -> ring slot s % 4
         if (C1_ABLM & 2) return;
         if constexpr (COUT == 128)
-            br_glds_stage(reinterpret_cast<const unsigned char*>(p.wstream) + (size_t)s * BR_STAGE_BYTES, wvoff,
-                          ring_addr + (unsigned)(s % BR_RING) * BR_STAGE_BYTES + (unsigned)wave * 2048);
+            br_ring_issue(p.wstream, s, ring_addr + (unsigned)(s % BR_RING) * BR_STAGE_BYTES, wave, wvoff);
         else   // 64 rows = the stage image's lower 4 KB: one 1 KB piece per wave
             br_glds_piece(reinterpret_cast<const unsigned char*>(p.wstream) + (size_t)s * BR_STAGE_BYTES, (unsigned)wave * 1024u + (unsigned)lane * 16u,
                           ring_addr + (unsigned)(s % BR_RING) * BR_STAGE_BYTES + (unsigned)wave * 1024);

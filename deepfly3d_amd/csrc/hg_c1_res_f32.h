@@ -14,6 +14,7 @@
 //     consecutive channels of one pixel -- sixteen 16-byte stores per lane and tile.
 // Arithmetic: the bias is the accumulators' start value and K ascends exactly as in conv1_ring_f32_kernel (stage s, half j2, e): BIT-IDENTICAL t1.
 #pragma once
+#include "hg_bt_common.h"
 #include "hg_bt_wino_f32.h"
 #include "hg_c1_f32.h"
 #include "hg_types.h"
@@ -41,7 +42,7 @@ __global__ __launch_bounds__(256) void c1r_pack_kernel(const float* __restrict__
 __global__ __launch_bounds__(256, 1) void conv1_res_f32_kernel(Conv1Args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* const coef_lds = reinterpret_cast<float*>(smem + C1R_W_BYTES);   // [0..255] scale, [256..511] shift, [512..639] b1
-    const unsigned w_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
+    const unsigned w_addr = lds_addr(smem);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(256, 1) void conv1_res_f32_kernel(Conv1Args p) {
         const unsigned wvoff = (unsigned)wave * 2048u + (unsigned)lane * 16u;
 #pragma unroll
         for (int k = 0; k < C1_NSTAGE; ++k)
-            br_glds_stage(reinterpret_cast<const unsigned char*>(p.wstream) + (size_t)k * BR_STAGE_BYTES, wvoff, w_addr + (unsigned)(k * BR_STAGE_BYTES + wave * 2048));
+            br_ring_issue(p.wstream, k, w_addr + (unsigned)(k * BR_STAGE_BYTES), wave, wvoff);
         coef_lds[tid] = p.s1[tid];
         coef_lds[256 + tid] = p.t1c[tid];
         if (tid < 128) coef_lds[512 + tid] = p.b1[tid];

@@ -1,6 +1,7 @@
 // Fused stack head of the hourglass (fc -> score -> fc_ / score_ + skip), kept apart from the single-convolution kernels (hg_conv.h) because its bf16 form takes
 // Wfc through the LDS-DMA stage ring of hg_bt_ring.h.
 #pragma once
+#include "hg_bt_common.h"
 #include "hg_bt_ring.h"
 #include "hg_types.h"
 
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs p) {
         constexpr int NSTEP = 256 * EB / 64;
         constexpr int NSLOT = 6, RSLOT = C::R_SLOTS;
         static_assert(!RDMA || (NSLOT + RSLOT) * BR_STAGE_BYTES <= C::STAGE_BYTES, "the rings live in the stage area");
-        const unsigned ring_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)stage;
+        const unsigned ring_addr = lds_addr(stage);
         const unsigned wuni = (unsigned)__builtin_amdgcn_readfirstlane(wave);
         const unsigned wvoff = wuni * 2048u + (unsigned)lane * 16u;
         // r pieces: lane -> (pixel 16 q + (lane >> 2) of the wave, chunk (lane & 3) ^ ((pixel >> 2) & 3)); rows past the end read the last pixel
@@ -162,8 +163,7 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs p) {
 #pragma unroll
             for (int rh = 0; rh < 2; ++rh) {
                 const int st = 2 * s + rh;
-                br_glds_stage(reinterpret_cast<const unsigned char*>(p.fcstream) + (size_t)st * BR_STAGE_BYTES, wvoff,
-                              ring_addr + (unsigned)(st % NSLOT) * BR_STAGE_BYTES + wuni * 2048u);
+                br_ring_issue(p.fcstream, st, ring_addr + (unsigned)(st % NSLOT) * BR_STAGE_BYTES, (int)wuni, wvoff);
             }
             if constexpr (RDMA) {
 #pragma unroll
@@ -441,14 +441,14 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs p) {
                 // steps 0, 1 | per step t: wait, barrier, step t + 2 | after step 4: 8 stores | ... | after step 9: 8 stores;
                 // a step is two stages (four pieces per wave), the score steps 4 and 9 one.
                 constexpr int NSLOT = C::RING_SLOTS, SP = C::SLICE_PITCH;
-                const unsigned ring_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)stage;
-                const unsigned wpiece = (unsigned)__builtin_amdgcn_readfirstlane(wave) * 2048u;
+                const unsigned ring_addr = lds_addr(stage);
+                const int wuni = __builtin_amdgcn_readfirstlane(wave);
+                const unsigned wpiece = (unsigned)wuni * 2048u;
                 auto issue_step = [&](int t) {
                     const int base = 9 * (t / 5) + 2 * (t % 5), cnt = (t % 5 == 4) ? 1 : 2;
 #pragma unroll
                     for (int k = 0; k < cnt; ++k)
-                        br_glds_stage(reinterpret_cast<const unsigned char*>(p.fc2stream) + (size_t)(base + k) * BR_STAGE_BYTES, wpiece + (unsigned)lane * 16u,
-                                      ring_addr + (unsigned)((base + k) % NSLOT) * BR_STAGE_BYTES + wpiece);
+                        br_ring_issue(p.fc2stream, base + k, ring_addr + (unsigned)((base + k) % NSLOT) * BR_STAGE_BYTES, wuni, wpiece + (unsigned)lane * 16u);
                 };
                 u32x4 xch[2][2][4];
 #pragma unroll

@@ -15,6 +15,7 @@
 // A double-step (one barrier) consumes two stages = 64 MFMAs per wave; the next pair is requested right behind the barrier and
 // awaited with vmcnt(0) a whole double-step (4 096 MFMA cycles) later.
 #pragma once
+#include "hg_bt_common.h"
 #include "hg_bt_reg.h"
 #include "hg_c1_f32.h"
 #include "hg_types.h"
@@ -54,34 +55,24 @@ __global__ __launch_bounds__(256, 2) void layer1_tail_f32_kernel(BtRingArgs p) {
     unsigned char* const ring = smem;
     unsigned char* const t1_lds = smem + BR_RING_BYTES;
     float* const b3_lds = reinterpret_cast<float*>(smem + BR_RING_BYTES + BR_T1_BYTES);
-    const unsigned ring_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)ring;
-    const unsigned t1_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)t1_lds;
+    const unsigned ring_addr = lds_addr(ring), t1_addr = lds_addr(t1_lds);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
     const int tiles_x = p.W / BT_TW, tiles_y = p.H / BT_TH;
-    int b;   // XCD-aware tile order, as in the ring kernels
-    {
-        const int nwg = gridDim.x, xcd = blockIdx.x & 7, q = nwg >> 3, r = nwg & 7;
-        b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
-    const int tx0 = (b % tiles_x) * BT_TW;
-    b /= tiles_x;
-    const int ty0 = (b % tiles_y) * BT_TH;
-    const int view = b / tiles_y;
+    const BtTile tile = bt_tile<BT_TW, BT_TH>(blockIdx.x, (int)gridDim.x, tiles_x, tiles_y);   // XCD-aware order
+    const int tx0 = tile.tx0, ty0 = tile.ty0, view = tile.view;
 
     const unsigned wvoff = (unsigned)wave * 2048u + (unsigned)lane * 16u;
     auto ring_issue = [&](int q) {   // stage q -> ring slot q % 4; this wave copies pieces 2 wave, 2 wave + 1
-        if (q < L1F_NSTAGE)
-            br_glds_stage(reinterpret_cast<const unsigned char*>(p.wstream) + (size_t)q * BR_STAGE_BYTES, wvoff,
-                          ring_addr + (unsigned)(q % BR_RING) * BR_STAGE_BYTES + (unsigned)wave * 2048);
+        if (q < L1F_NSTAGE) br_ring_issue(p.wstream, q, ring_addr + (unsigned)(q % BR_RING) * BR_STAGE_BYTES, wave, wvoff);
     };
     const unsigned char* const wf0 = ring + br_swz(l31, half);
     const unsigned char* const wf1 = ring + br_swz(l31, 2 + half);
 
-    // the t1 halo tile by LDS-DMA: piece pc (1 KB) = halo pixels 4 pc .. 4 pc + 3, lane -> (pixel 4 pc + (lane >> 4), slot lane & 15),
-    // fetching the chunk that belongs in that slot of the swizzled tile; pixels outside the image fetch zeros (the 3x3's padding)
+    // the t1 halo tile by LDS-DMA (64 channels: one half; the map is hg_bt_common.h bt_t1_issue's -- written out here because this kernel issues it from
+    // its body, not from a lambda, and the shared form compiles to other instructions for the division by the halo width)
     {
         const unsigned char* const tin = reinterpret_cast<const unsigned char*>(p.t1in) + (size_t)view * p.H * p.W * 256;
 #pragma unroll
@@ -103,14 +94,7 @@ __global__ __launch_bounds__(256, 2) void layer1_tail_f32_kernel(BtRingArgs p) {
     ring_issue(2);
     const float pre_b = tid < CO ? p.b3[tid] + p.bd[tid] : 0.0f;   // (the register-staged kernel's expression: one float add)
     f32x16 t2[NT];   // t2^T: rows = channels (register 4 q + e <-> channel 32 m + 8 q + 4 half + e), columns = the wave's 32 pixels
-#pragma unroll
-    for (int m = 0; m < NT; ++m)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 bb = *reinterpret_cast<const f32x4*>(p.b2 + 32 * m + 8 * q + 4 * half);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) t2[m][4 * q + e] = bb[e];
-        }
+    bt_t2_start(p.b2, half, t2);
     if (tid < CO) b3_lds[tid] = pre_b;
 
     const int py = 2 * wave + (l31 >> 4), px = l31 & 15;   // this wave's 32 pixels: tile rows 2 wave, 2 wave + 1
@@ -312,47 +296,24 @@ __global__ __launch_bounds__(256, 2) void layer2_tail_f32_kernel(BtRingArgs p) {
     unsigned char* const ring = smem;
     unsigned char* const t1_lds = smem + BR_RING_BYTES;
     float* const b3_lds = reinterpret_cast<float*>(smem + BR_RING_BYTES + BR_T1_BYTES);
-    const unsigned ring_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)ring;
-    const unsigned t1_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)t1_lds;
+    const unsigned ring_addr = lds_addr(ring), t1_addr = lds_addr(t1_lds);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
     const int tiles_x = p.W / BT_TW, tiles_y = p.H / BT_TH;
-    int b;
-    {
-        const int nwg = gridDim.x, xcd = blockIdx.x & 7, q = nwg >> 3, r = nwg & 7;
-        b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
-    const int tx0 = (b % tiles_x) * BT_TW;
-    b /= tiles_x;
-    const int ty0 = (b % tiles_y) * BT_TH;
-    const int view = b / tiles_y;
+    const BtTile tile = bt_tile<BT_TW, BT_TH>(blockIdx.x, (int)gridDim.x, tiles_x, tiles_y);   // XCD-aware order
+    const int tx0 = tile.tx0, ty0 = tile.ty0, view = tile.view;
 
     const unsigned wvoff = (unsigned)wave * 2048u + (unsigned)lane * 16u;
     auto ring_issue = [&](int q) {
-        if (q < L2F_NSTAGE)
-            br_glds_stage(reinterpret_cast<const unsigned char*>(p.wstream) + (size_t)q * BR_STAGE_BYTES, wvoff,
-                          ring_addr + (unsigned)(q % BR_RING) * BR_STAGE_BYTES + (unsigned)wave * 2048);
+        if (q < L2F_NSTAGE) br_ring_issue(p.wstream, q, ring_addr + (unsigned)(q % BR_RING) * BR_STAGE_BYTES, wave, wvoff);
     };
     const unsigned char* const wf0 = ring + br_swz(l31, half);
     const unsigned char* const wf1 = ring + br_swz(l31, 2 + half);
-    // the 64-channel half kh of the t1 halo tile by LDS-DMA (see layer1_tail_f32_kernel; a t1 row is 512 B here)
+    // the 64-channel half kh of the t1 halo tile by LDS-DMA (a t1 row is 512 B here)
     auto t1_issue = [&](int kh) {
-        const unsigned char* const tin = reinterpret_cast<const unsigned char*>(p.t1in) + (size_t)view * p.H * p.W * 512;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            const int pc = wave + 4 * k;
-            if (pc < BT_HALO / 4) {
-                const int hp = 4 * pc + (lane >> 4);
-                const int hy = hp / BT_HW, hx = hp % BT_HW;
-                const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
-                const bool ok = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-                const unsigned chunk = (unsigned)((lane & 15) ^ br_t1_swz(hp));
-                const unsigned char* const src = ok ? tin + ((size_t)y * p.W + x) * 512 + kh * 256 + chunk * 16 : reinterpret_cast<const unsigned char*>(p.zeros) + chunk * 16;
-                br_glds_piece64(src, t1_addr + (unsigned)pc * 1024u);
-            }
-        }
+        bt_t1_issue<BT_HW, BT_HALO, 512>(reinterpret_cast<const unsigned char*>(p.t1in) + (size_t)view * p.H * p.W * 512, p.zeros, tx0, ty0, p.H, p.W, kh * 256, t1_addr, wave, lane);
     };
     t1_issue(0);
     ring_issue(0);
@@ -360,14 +321,7 @@ __global__ __launch_bounds__(256, 2) void layer2_tail_f32_kernel(BtRingArgs p) {
     ring_issue(2);
     const float pre_b = p.b3[tid] + p.bd[tid];   // (the register-staged kernel's expression: one float add)
     f32x16 t2[NT];
-#pragma unroll
-    for (int m = 0; m < NT; ++m)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 bb = *reinterpret_cast<const f32x4*>(p.b2 + 32 * m + 8 * q + 4 * half);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) t2[m][4 * q + e] = bb[e];
-        }
+    bt_t2_start(p.b2, half, t2);
     b3_lds[tid] = pre_b;
 
     const int py = 2 * wave + (l31 >> 4), px = l31 & 15;

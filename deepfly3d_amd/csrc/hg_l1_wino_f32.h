@@ -9,6 +9,7 @@
 //     channel 4 l + i) so that outputs and pooled outputs move as 16-byte accesses; bias b3 + bd as one float add.
 // LDS: V 2 x 32 KB (ring later) | t1 halo 10 x 34 pixels x 256 B = 85 KB (t2 later) | b3 + bd [128], b2 [64].
 #pragma once
+#include "hg_bt_common.h"
 #include "hg_bt_reg.h"
 #include "hg_bt_wino_f32.h"
 #include "hg_types.h"
@@ -69,6 +70,36 @@ __global__ __launch_bounds__(256) void l1_wino_pack_w_kernel(const float* __rest
     *reinterpret_cast<u32x4*>(stream + (size_t)k8 * BR_STAGE_BYTES + br_swz(r, c)) = *reinterpret_cast<const u32x4*>(w + (size_t)ch * 64 + 16 * k8 + 4 * c);
 }
 
+// The F(2x2, 3x3) input transform of one (patch, channel) (U' = s_i s_j U with s_2 = -1):
+// V' = B'^T d B' as SIXTEEN packed adds in one statement (one VALU clump per chunk).
+// In: P[b] = (d[0][b], d[1][b]), Q[b] = (d[2][b], d[3][b]) -- the register pairs the two ds_read2st64_b32 of patch column b deliver.
+// Rows first: per column b,  T[b] = (d0 - d2, d1 + d2),  S[b] = (d1 - d2, d1 - d3)   [row 2 with the opposite sign: see bt_wino_pack_kernel];
+// then columns, on whole pairs: j = 0: X0 - X2, 1: X1 + X2, 2: X1 - X2 (opposite sign), 3: X1 - X3 for X = T (rows 0, 1) and X = S (rows 2, 3).
+// Out: VT[j] = (V'[0][j], V'[1][j]), VS[j] = (V'[2][j], V'[3][j]).
+__device__ __forceinline__ void wn_transform(const f32x2 (&P)[4], const f32x2 (&Q)[4], f32x2 (&VT)[4], f32x2 (&VS)[4]) {
+    f32x2 T0, T1, T2, T3, S0, S1, S2, S3;
+    asm volatile(
+        "v_pk_add_f32 %8, %16, %20 op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
+        "v_pk_add_f32 %12, %16, %20 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %9, %17, %21 op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
+        "v_pk_add_f32 %13, %17, %21 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %10, %18, %22 op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
+        "v_pk_add_f32 %14, %18, %22 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %11, %19, %23 op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
+        "v_pk_add_f32 %15, %19, %23 op_sel:[1,0] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %0, %8, %10 neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %1, %9, %10\n\t"
+        "v_pk_add_f32 %2, %9, %10 neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %3, %9, %11 neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %4, %12, %14 neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %5, %13, %14\n\t"
+        "v_pk_add_f32 %6, %13, %14 neg_lo:[0,1] neg_hi:[0,1]\n\t"
+        "v_pk_add_f32 %7, %13, %15 neg_lo:[0,1] neg_hi:[0,1]"
+        : "=&v"(VT[0]), "=&v"(VT[1]), "=&v"(VT[2]), "=&v"(VT[3]), "=&v"(VS[0]), "=&v"(VS[1]), "=&v"(VS[2]), "=&v"(VS[3]),
+          "=&v"(T0), "=&v"(T1), "=&v"(T2), "=&v"(T3), "=&v"(S0), "=&v"(S1), "=&v"(S2), "=&v"(S3)
+        : "v"(P[0]), "v"(P[1]), "v"(P[2]), "v"(P[3]), "v"(Q[0]), "v"(Q[1]), "v"(Q[2]), "v"(Q[3]));
+}
+
 // BtRingArgs: in = x [V, H, W, 64], t1in [V, H, W, 64], out (may be null: pooled output only) [V, H, W, 128], pool (may be null) [V, H/2, W/2, 128],
 // w2d = U | W3 stages | Wd stages, zeros, b2 [64], b3 [128], bd [128].  H % 8 == 0, W % 32 == 0.
 __global__ __launch_bounds__(256, 1) void layer1_wino_f32_kernel(BtRingArgs p) {
@@ -78,8 +109,7 @@ __global__ __launch_bounds__(256, 1) void layer1_wino_f32_kernel(BtRingArgs p) {
     unsigned char* const t1_lds = smem + L1W_T1_OFF;
     float* const b3_lds = reinterpret_cast<float*>(smem + L1W_B_OFF);
     float* const b2_lds = b3_lds + 128;
-    const unsigned ring_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)ring;
-    const unsigned t1_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)t1_lds;
+    const unsigned ring_addr = lds_addr(ring), t1_addr = lds_addr(t1_lds);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -87,39 +117,15 @@ __global__ __launch_bounds__(256, 1) void layer1_wino_f32_kernel(BtRingArgs p) {
     const int half = lane >> 5, l31 = lane & 31;
     const int tiles_x = p.W / L1W_TW, tiles_y = p.H / BT_TH;
     const int ntiles = p.V * tiles_y * tiles_x;
-    auto tile_of = [&](int vb, int& tx0, int& ty0, int& view) {   // persistent, XCD-aware: as bottleneck_wino_f32_kernel
-        const int xcd = vb & 7, q = ntiles >> 3, r = ntiles & 7;
-        int b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
-        tx0 = (b % tiles_x) * L1W_TW;
-        b /= tiles_x;
-        ty0 = (b % tiles_y) * BT_TH;
-        view = b / tiles_y;
+    auto tile_of = [&](int vb, int& tx0, int& ty0, int& view) {   // persistent, XCD-aware (hg_bt_common.h bt_tile)
+        const BtTile t = bt_tile<L1W_TW, BT_TH>(vb, ntiles, tiles_x, tiles_y);
+        tx0 = t.tx0, ty0 = t.ty0, view = t.view;
     };
-    // the t1 halo tile (10 x 34 pixels x 64 channels) by LDS-DMA: piece pc = halo pixels 4 pc .. 4 pc + 3, lane -> (pixel, 16-byte slot) fetching the
-    // chunk that belongs there (slot ^ (hx & 15)); pixels outside the image from the page of zeros
-    unsigned uoff = (unsigned)(lane * 16);   // the one lane-derived register that lives across phase 2 (see bottleneck_wino_f32_kernel)
+    // the t1 halo tile (10 x 34 pixels x 64 channels) by LDS-DMA (hg_bt_common.h bt_t1_issue_persistent)
+    unsigned uoff = (unsigned)(lane * 16);   // the one lane-derived register that lives across phase 2 (hg_bt_wino_f32.h: why)
     asm volatile("" : "+v"(uoff));
     auto t1_issue = [&](int tx0, int ty0, int view) {
-        int lane_ = (int)(uoff >> 4);
-        asm volatile("" : "+v"(lane_));   // (recomputed per call, lane values and uniform values alike: see bottleneck_wino_f32_kernel)
-        int wave_ = wave;
-        asm volatile("" : "+s"(wave_));
-        const unsigned char* const tin = reinterpret_cast<const unsigned char*>(p.t1in) + (size_t)view * p.H * p.W * 256;
-        const unsigned char* const zer = reinterpret_cast<const unsigned char*>(p.zeros);
-        const int q = lane_ >> 4, slot = lane_ & 15;
-#pragma unroll
-        for (int k = 0; k < 22; ++k) {
-            const int pc = wave_ + 4 * k;
-            if (pc < L1W_HALO / 4) {
-                const int hp = 4 * pc + q;
-                const int hy = hp / L1W_HW, hx = hp - hy * L1W_HW;
-                const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
-                const bool ok = (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-                const unsigned c16 = (unsigned)((slot ^ (hx & 15)) << 4);
-                const unsigned in_view = (unsigned)((y * p.W + x) * 256) + c16;   // (a view's t1 is < 4 GB)
-                br_glds_piece64((ok ? tin : zer) + (ok ? in_view : c16), t1_addr + (unsigned)(pc * 1024));
-            }
-        }
+        bt_t1_issue_persistent<L1W_HW, L1W_HALO, 256, 1>(p.t1in, p.zeros, view, tx0, ty0, p.H, p.W, t1_addr, wave, uoff);
     };
     const unsigned char* const ubase = reinterpret_cast<const unsigned char*>(p.w2d) + (size_t)cb * 4096;
     auto uload = [&](int c, int e, f32x4 (&dst)[4]) { wn_uload4(dst, ubase + (size_t)(c * 4 + e) * 8192, uoff); };
@@ -174,7 +180,7 @@ __global__ __launch_bounds__(256, 1) void layer1_wino_f32_kernel(BtRingArgs p) {
         asm volatile("" : "+v"(wvoff));
 #pragma unroll
         for (int k = 0; k < 8; ++k)
-            br_glds_stage(reinterpret_cast<const unsigned char*>(p.w2d) + L1W_U_BYTES + (size_t)k * BR_STAGE_BYTES, wvoff, ring_addr + (unsigned)(k * BR_STAGE_BYTES + wave * 2048));
+            br_ring_issue(reinterpret_cast<const unsigned char*>(p.w2d) + L1W_U_BYTES, k, ring_addr + (unsigned)(k * BR_STAGE_BYTES), wave, wvoff);
     };
 
     int vb = blockIdx.x;

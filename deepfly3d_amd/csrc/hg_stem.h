@@ -76,12 +76,12 @@ struct StemGrid {
 // ds_write; runs under the patch staging).  A wave's pieces have landed after its s_waitcnt vmcnt(0).
 template <int PIECES>
 __device__ __forceinline__ void stem_copy_weights(const void* src, void* lds, int tid) {
-    const unsigned lds_addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
+    const unsigned dst = lds_addr(lds);
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 #pragma unroll
     for (int k = 0; k < (PIECES + 3) / 4; ++k) {
         const int pc = wv + 4 * k;
-        if (pc < PIECES) br_glds_piece(src, (unsigned)pc * 1024u + (unsigned)(tid & 63) * 16u, lds_addr + (unsigned)pc * 1024u);
+        if (pc < PIECES) br_glds_piece(src, (unsigned)pc * 1024u + (unsigned)(tid & 63) * 16u, dst + (unsigned)pc * 1024u);
     }
 }
 

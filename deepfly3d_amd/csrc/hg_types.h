@@ -1,6 +1,6 @@
 // What every device header of the stacked-hourglass engine builds on: vector types, the 16-bit storage formats (Lp<T>), element sizes
 // (Elem<T>), the input BatchNorm + ReLU on a chunk (PreactCoef), the F32S split-product helpers with their MFMA wrappers, and the
-// LDS-DMA / wait-count primitives (br_glds_*, br_wait_vm).
+// LDS-DMA / wait-count primitives (lds_addr, br_glds_*, br_wait_vm).
 #pragma once
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
@@ -248,6 +248,9 @@ __device__ __forceinline__ void mfma_quad(float a0, float a1, float a2, float a3
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc = A_FIRST ? __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], w[e], acc, 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x2f32(w[e], a[e], acc, 0, 0, 0);
 }
+
+// the LDS byte address of a pointer into __shared__ memory (what M0 takes as an LDS-DMA destination)
+__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char*)p; }
 
 // LDS-DMA of one 8 KB stage: this wave's two 1 KB pieces (lane l's 16 bytes land at dst + 16 l; dst wave-uniform, in M0).
 // sbase (uniform) + voff (per lane, 32 bit) is the source address.  The instruction's immediate offset is added to the
