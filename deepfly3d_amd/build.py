@@ -21,6 +21,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # pose3d.hip and ba_lsmr.hip reproduce float64 scalar recurrences (One-Euro filter, LSMR rotations) exactly as the
 # CPU reference arithmetic rounds them: no multiply-add fusion there
 # render.hip (f4, the video frames): float64 pixel tests restated in numpy by oracle/render.py, compared bit for bit
+#   (and the heat-map overlay of DESIGN.md section 13, restated in tests/heatmap_overlay_oracle.py)
 # smooth.hip keeps the default -ffp-contract=fast on purpose: its test bound is 1e-10 px, not bit parity, fused multiply-adds only
 # tighten the sums, and the pass is bound by float64 vector instructions, which contraction cuts by a quarter
 # subpixel.hip: the float64 sub-pixel rule, compared bit for bit with tests/subpixel_oracle.py

@@ -1,13 +1,16 @@
 """`df3d-cli` on the MI355X back-end: same flags, defaults and exit codes as reference df3d/cli.py:15-358.
 Video rendering flags are accepted and reported as unsupported (visualisation is out of scope)."""
 import argparse
+import glob
 import logging
+import os
 import sys
 from collections import deque
 from pathlib import Path
 
 from . import logger
 from .core import Core
+from .os_util import camera_videos
 
 
 def parse_cli_args(argv=None):
@@ -26,6 +29,10 @@ def parse_cli_args(argv=None):
                    default=[0, 1, 2, 3, 4, 5, 6], type=int, nargs="*")
     p.add_argument("--video-2d", help="Generate pose2d videos", action="store_true")
     p.add_argument("--video-3d", help="Generate pose3d videos", action="store_true")
+    p.add_argument("--video-heatmap", dest="video_heatmap", action="store_true",
+                   help="Generate a video of the 2 x 3 camera grid with the network's heat-maps drawn on the images: every pixel tinted with "
+                        "the colour of the joint whose heat-map is largest there.  Needs only the images and the weights, so it also works "
+                        "with --skip-pose-estimation")
     p.add_argument("--smooth-2d", dest="smooth_2d", action="store_true",
                    help="With --video-2d: draw the temporally smoothed 2-D detections (a 20-frame Gaussian where the detections are "
                         "quiet, the detection itself where they move) instead of the raw ones; results on disk are unchanged")
@@ -85,12 +92,23 @@ def print_debug(args):
     return 0
 
 
+# heat-maps are never stored: once an earlier --delete-images has removed the frames, and they cannot be expanded again
+# from the camera videos, there is nothing to compute them from
+_NO_IMAGES = ("--video-heatmap draws the heat-maps the network computes from the camera images, and {folder} holds none (removed by an earlier "
+              "--delete-images?): heat-maps are recomputed from the images, never stored, so there is nothing to draw")
+
+
 def run(args):
-    if args.skip_estimation and not args.video_2d and not args.video_3d:
+    video_heatmap = getattr(args, "video_heatmap", False)
+    if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap:
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0
     logger.info(f"\nWorking in {args.input_folder}")
+    if video_heatmap and not glob.glob(os.path.join(args.input_folder, "camera_*_img_*.jpg")) and not camera_videos(args.input_folder):
+        raise FileNotFoundError(_NO_IMAGES.format(folder=args.input_folder))   # before Core: neither frames nor videos to expand them from
     core = Core(args.input_folder, args.output_folder, args.num_images_max, args.order, dtype=args.dtype, device=getattr(args, "device", None))
+    if video_heatmap and not core.has_heatmap:
+        raise FileNotFoundError(_NO_IMAGES.format(folder=args.input_folder))
     auto = getattr(args, "auto_correct", False)
     if not args.skip_estimation:
         from .config import PICTORIAL_DEFAULTS
@@ -98,13 +116,16 @@ def run(args):
         core.pose2d_estimation(args.batch_size, args.pin_memory_disabled, num_peaks=PICTORIAL_DEFAULTS["num_peaks"] if auto else 0,
                                subpixel=getattr(args, "subpixel", False))
         core.save()
-    core.calibrate_calc(0, core.max_img_id)
-    if auto and getattr(args, "correct_only_flagged", False):
-        core.auto_correct(flagged_only=True)
-    elif auto:
-        core.auto_correct()
-    core.save()
-    if args.video_2d or args.video_3d:
+    # the heat-map video needs the images and the weights only: without an earlier result to reopen there is no pose to calibrate or save
+    pose_free = args.skip_estimation and core.points2d is None and video_heatmap and not args.video_2d and not args.video_3d
+    if not pose_free:
+        core.calibrate_calc(0, core.max_img_id)
+        if auto and getattr(args, "correct_only_flagged", False):
+            core.auto_correct(flagged_only=True)
+        elif auto:
+            core.auto_correct()
+        core.save()
+    if args.video_2d or args.video_3d or video_heatmap:
         # f4 (reference cli.py:305-321): frames drawn on the GPU (csrc/render.hip), encoded by ffmpeg when present.  Rank 0 draws and
         # encodes; the peers wait for its outcome with a heartbeat (distributed.primary_section), so that an encoder failure moves
         # every rank on to the next folder together and a long encode never holds a peer in one collective
@@ -118,6 +139,8 @@ def run(args):
                 video.make_pose2d_video(core, fps=fps, progress=beat, smooth=getattr(args, "smooth_2d", False))
             if args.video_3d:
                 video.make_pose3d_video(core, fps=fps, progress=beat)
+            if video_heatmap:
+                video.make_heatmap_video(core, fps=fps, progress=beat)
 
         dd.primary_section(videos, "video")
     if args.delete_images:

@@ -113,3 +113,41 @@ _REDS = [(186, 30, 49), (201, 86, 79), (213, 133, 121)]
 _BLUES = [(15, 115, 153), (26, 141, 175), (117, 190, 203)]
 _GREY = (210, 210, 210)
 LIMB_COLORS = _REDS + [_GREY, _GREY] + _BLUES + [_GREY, _GREY]
+
+
+# ---- heat-map overlays: which of a camera's 19 heat-map planes is which joint of the 38-joint layout.  The
+# rule is the re-layout's (reference df3d/core.py:187-203; df3d::relayout_source in csrc/geometry_dev.h), keyed like it on the
+# camera's POSITION in the camera ordering: positions 0-2 fill joints 0..18, positions 4-6 joints 19..37 and are the views the network
+# sees mirrored, positions 2 and 4 leave antenna and stripes out, position 3 (the front camera) fills nothing.
+def camera_position(cam_id, camera_ordering=None):
+    """Position of camera `cam_id` in `camera_ordering` (default: the identity ordering, where it is the camera id)."""
+    order = list(range(config["num_cameras"])) if camera_ordering is None else [int(c) for c in camera_ordering]
+    if int(cam_id) not in order:
+        raise NotImplementedError(f"no camera {cam_id}")
+    return order.index(int(cam_id))
+
+
+def camera_is_flipped(cam_id, camera_ordering=None):
+    """Whether the network sees camera `cam_id` mirrored (Core.pose2d_estimation's flip set: the cameras after position 3)."""
+    return camera_position(cam_id, camera_ordering) > 3
+
+
+def heatmap_planes(cam_id, joints=(), camera_ordering=None):
+    """[(plane, joint), ...]: the heat-map planes (0..18) of camera `cam_id` and the joint of the 38-joint layout each of them becomes
+    under the re-layout, in plane order.  `joints` (plot_2d's ids) keeps only the listed joints; a joint the camera does not fill is
+    dropped, and the front camera has no planes.  A plane's colour is plane_color(joint)."""
+    pos = camera_position(cam_id, camera_ordering)
+    keep = None if not len(joints) else {int(j) for j in joints}
+    pairs = []
+    for plane in range(config["num_predict"]):
+        if pos == 3 or (pos in (2, 4) and plane >= 15):
+            continue
+        joint = plane if pos < 3 else plane + config["num_predict"]
+        if keep is None or joint in keep:
+            pairs.append((plane, joint))
+    return pairs
+
+
+def plane_color(joint):
+    """RGB of the heat-map plane of joint `joint`: its limb's colour, as plot_2d and the pose videos draw the joint."""
+    return LIMB_COLORS[limb_of_joint(joint) % len(LIMB_COLORS)]

@@ -23,10 +23,10 @@ import torch
 
 from . import _native, logger, ops
 from .camera_network import CameraNetwork
-from .config import IGNORE_JOINT_ID, camera_see_joint, config, load_calibration
+from .config import IGNORE_JOINT_ID, camera_is_flipped, camera_see_joint, config, heatmap_planes, load_calibration, plane_color
 from .db import PoseDB
 from .inference import inference_folder
-from .os_util import camera_videos, extract_frames, get_max_img_id, parse_frame_rate, parse_vid_name, probe_frame_rate
+from .os_util import camera_videos, extract_frames, get_max_img_id, image_path_for, parse_frame_rate, parse_vid_name, probe_frame_rate
 from .procrustes import procrustes_separate, video_pose
 
 _KNOWN_ORDERINGS = [
@@ -105,6 +105,8 @@ class Core:
         self.points2d_argmax = None   # the arg-max detections, once auto_correct() has replaced points2d
         self._corrected = False       # every rank: auto_correct() ran (save() then triangulates on rank 0 alone)
         self._subpixel = False        # pose2d_estimation(subpixel=True) ran: save() appends the key "subpixel"
+        self._heatmap_cache = None    # (img_id, luma [7, H, W], heat-maps [7, 19, 64, 128]) device tensors of the last heatmaps() call
+        self._heatmap_proven = False  # a reduced-precision engine passed the canary on this recording's views (heatmaps())
         if os.path.exists(self.save_path):
             self._resume(self.save_path)
 
@@ -582,6 +584,71 @@ class Core:
             keep[list(joints)] = True
             pts = np.where(keep[:, None], pts, 0.0)
         return self.camNet[cam_id].plot_2d(img_id, points2d=pts, bones=skeleton_bones())
+
+    # -- heat-map overlays (the reference's README lists plot_heatmap / has_heatmap, its 1.0.1 has no body for them) ----
+    @property
+    def has_heatmap(self):
+        """Whether plot_heatmap() can draw: true while the image files are present.  Heat-maps are recomputed from the images on demand
+        (heatmaps()), never stored: a recording's heat-maps are 4.3 MB per image, and after delete_images() there is nothing to compute
+        them from."""
+        try:
+            for cam in range(config["num_cameras"]):
+                image_path_for(self.input_folder, cam, 0)
+        except FileNotFoundError:
+            return False
+        return True
+
+    def _heatmap_views(self, img_id):
+        from . import distributed as dd
+        from . import jpeg
+        from .inference import PREPROCESS, get_engine
+
+        if dd.current()[0] != 0:
+            raise RuntimeError("the heat-map queries are rank-0 methods, like the reprojection-error queries")
+        img_id = int(img_id)
+        if not 0 <= img_id < self.num_images:
+            raise IndexError(f"image ids must lie in [0, {self.num_images})")
+        if self._heatmap_cache is not None and self._heatmap_cache[0] == img_id:
+            return self._heatmap_cache
+        ncam = config["num_cameras"]
+        blobs = []
+        for cam in range(ncam):
+            with open(image_path_for(self.input_folder, cam, img_id), "rb") as f:
+                blobs.append(f.read())
+        engine = get_engine(dtype=self.dtype, device=self.device)
+        W, H = self.image_shape
+        luma = jpeg.decode_luma(blobs, W, H, device=engine.device)
+        flip = torch.tensor([1 if camera_is_flipped(cam, self.camera_ordering) else 0 for cam in range(ncam)], dtype=torch.uint8, device=engine.device)
+
+        def forward(e):
+            return e.forward_u8(luma, flip, PREPROCESS["mean"], PREPROCESS["std"], resize=PREPROCESS["resize"])
+
+        if engine.dtype != "f32" and not self._heatmap_proven:   # as inference_folder proves a reduced-precision engine on its first views
+            engine.canary(get_engine(dtype="f32", device=self.device), forward, what=f"image {img_id} of {self.input_folder}")
+            self._heatmap_proven = True
+        self._heatmap_cache = (img_id, luma, forward(engine))
+        return self._heatmap_cache
+
+    def heatmaps(self, img_id):
+        """[7, 19, 64, 128] float32 CUDA tensor: the network's heat-maps of image `img_id`, camera by camera, as the network saw the
+        view (cameras after position 3 of the camera ordering mirrored).  Computed on demand on pose2d_estimation's own path -- the
+        same file bytes, device JPEG decode, flip set, preprocessing and `dtype` engine (a reduced-precision engine first proves itself
+        against the exact one, HourglassEngine.canary) -- so they are the heat-maps the run took its detections from.  The last image's
+        result is kept (a one-entry cache): treat it as read-only.  A rank-0 method."""
+        return self._heatmap_views(img_id)[2]
+
+    def plot_heatmap(self, cam_id, img_id, joints=[], gain=1.0):
+        """Image `img_id` of camera `cam_id` with its heat-maps drawn on it, [H, W, 3] uint8 ndarray (the reference README's
+        `Core.plot_heatmap(cam_id, img_id, joints=[])`; the drawing rule is DESIGN.md section 13): every pixel is tinted with the
+        colour of the joint whose heat-map is largest there, the stronger the larger the value, so a plane's peak lies where plot_2d
+        draws the detection.  `joints` restricts the drawing to the listed ids of the 38-joint layout (plot_2d's); joints the camera
+        does not fill are ignored, and the front camera, which fills none, gives the grey image.  `gain` multiplies the heat-maps before
+        they are clamped to [0, 1]."""
+        _, luma, hm = self._heatmap_views(img_id)
+        pairs = heatmap_planes(cam_id, joints, self.camera_ordering)
+        img = ops.render_heatmap(luma[cam_id], hm[cam_id], [p for p, _ in pairs], [plane_color(j) for _, j in pairs],
+                                 camera_is_flipped(cam_id, self.camera_ordering), gain=gain)
+        return img.cpu().numpy()
 
     def get_image(self, cam_id, img_id):
         return self.camNet.cam_list[cam_id].get_image(img_id)

@@ -133,6 +133,71 @@ __global__ __launch_bounds__(256) void resize_rgb_kernel(const unsigned char* __
     }
 }
 
+// ---- heat-map overlays: Core.plot_heatmap and the --video-heatmap frames ------------------------------------
+// Per slot (one camera view) the host names up to 32 planes of that view's heat-maps and a colour for each; they travel as a kernel
+// argument like the Skeleton.  Every output pixel samples each selected plane bilinearly at its own position under the arg-max
+// convention (pixel = cell * H / Hh, mirrored for a camera the network saw flipped), keeps the plane with the largest clamped value a
+// and shows (1 - a) grey + a colour.  The rule is restated in tests/heatmap_overlay_oracle.py and compared bit for bit.
+constexpr int HM_MAXSLOTS = 8;   // views per launch
+constexpr int HM_MAXSEL = 32;    // selected planes per view
+
+struct HeatTables {
+    int n[HM_MAXSLOTS];
+    int flip[HM_MAXSLOTS];
+    int plane[HM_MAXSLOTS][HM_MAXSEL];
+    unsigned int rgb[HM_MAXSLOTS][HM_MAXSEL];   // r | g << 8 | b << 16
+};
+
+// taps of one axis: s = the coordinate in cells; a coordinate on or past the last cell reads the last cell alone
+__device__ __forceinline__ void heat_taps(double s, int n, int& i0, int& i1, double& f) {
+    const double fl = floor(s);
+    if (fl <= (double)(n - 1)) {
+        i0 = (int)fl;
+        f = s - fl;
+    } else {
+        i0 = n - 1;
+        f = 0.0;
+    }
+    i1 = i0 + 1 < n ? i0 + 1 : n - 1;
+}
+
+__device__ __forceinline__ double heat_tap(float h) { return isfinite(h) ? (double)h : 0.0; }
+
+// grid [rows H, cols W, 3], slot s at (s / cols, s % cols): block (x tile, y, slot)
+__global__ __launch_bounds__(256) void render_heatmap_kernel(const unsigned char* __restrict__ luma, int H, int W, const float* __restrict__ hm, int P,
+                                                             int Hh, int Wh, HeatTables tb, int cols, double gain, unsigned char* __restrict__ out) {
+    const int slot = blockIdx.z;
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    const double g = (double)luma[((size_t)slot * H + y) * W + x];
+    const int xs = tb.flip[slot] ? W - x : x;
+    int i0, i1, j0, j1;
+    double fy, fx;
+    heat_taps((double)y * (double)Hh / (double)H, Hh, i0, i1, fy);
+    heat_taps((double)xs * (double)Wh / (double)W, Wh, j0, j1, fx);
+    const size_t o00 = (size_t)i0 * Wh + j0, o01 = (size_t)i0 * Wh + j1, o10 = (size_t)i1 * Wh + j0, o11 = (size_t)i1 * Wh + j1;
+    double best = 0.0;
+    unsigned int colour = 0;
+    const int n = tb.n[slot];
+    for (int k = 0; k < n; ++k) {
+        const float* p = hm + ((size_t)slot * P + tb.plane[slot][k]) * ((size_t)Hh * Wh);
+        const double h00 = heat_tap(p[o00]), h01 = heat_tap(p[o01]), h10 = heat_tap(p[o10]), h11 = heat_tap(p[o11]);
+        const double top = (1.0 - fx) * h00 + fx * h01;
+        const double bot = (1.0 - fx) * h10 + fx * h11;
+        const double v = (1.0 - fy) * top + fy * bot;
+        double a = gain * v;
+        a = a > 0.0 ? a : 0.0;
+        a = a < 1.0 ? a : 1.0;
+        if (a > best) {   // strict: a tie stays with the earlier plane
+            best = a;
+            colour = tb.rgb[slot][k];
+        }
+    }
+    const int row = slot / cols, col = slot % cols;
+    unsigned char* o = out + (((size_t)row * H + y) * ((size_t)cols * W) + (size_t)col * W + x) * 3;
+    for (int c = 0; c < 3; ++c) o[c] = (unsigned char)floor((1.0 - best) * g + best * (double)((colour >> (8 * c)) & 255u) + 0.5);
+}
+
 int fill_skeleton(Skeleton& sk, int nj, const int* bones, int nb, const unsigned char* joint_rgb) {
     DF3D_CHECK_ARG(nj >= 1 && nj <= MAXJ && nb >= 0 && nb <= MAXB && (nb == 0 || bones) && joint_rgb, "1..64 joints, at most 96 bones, host tables");
     sk.nj = nj;
@@ -187,6 +252,35 @@ int df3d_resize_rgb(const unsigned char* in_dev, int in_h, int in_w, int in_pitc
     DF3D_CHECK_ARG(in_dev && out_dev && in_h > 0 && in_w > 0 && out_h > 0 && out_w > 0 && in_pitch_px >= in_w && out_pitch_px >= out_w, "null pointer or bad size");
     hipLaunchKernelGGL(resize_rgb_kernel, dim3((out_w + 255) / 256, out_h), dim3(256), 0, df3d::as_stream(stream), in_dev, in_h, in_w, in_pitch_px, out_dev,
                        out_h, out_w, out_pitch_px);
+    DF3D_LAUNCH_CHECK();
+    return DF3D_OK;
+}
+
+int df3d_render_heatmap(const unsigned char* luma_dev, int height, int width, const float* heatmaps_dev, int num_planes, int hm_height, int hm_width,
+                        int num_slots, int cols, const int* num_selected_host, const int* planes_host, const unsigned char* rgb_host,
+                        const unsigned char* flip_host, double gain, unsigned char* out_rgb_dev, void* stream) {
+    DF3D_CHECK_ARG(num_slots >= 1 && num_slots <= HM_MAXSLOTS && cols >= 1 && cols <= num_slots, "1..8 slots in 1..slots columns");
+    DF3D_CHECK_ARG(height > 0 && width > 0 && num_planes > 0 && hm_height > 0 && hm_width > 0, "sizes must be positive");
+    DF3D_CHECK_ARG(height <= 65535 && (long long)cols * width <= 0x7fffffffll, "image too large: at most 65535 rows and 2^31 - 1 columns in the grid");
+    DF3D_CHECK_ARG(std::isfinite(gain) && gain >= 0.0, "gain must be finite and >= 0");
+    DF3D_CHECK_ARG(luma_dev && heatmaps_dev && out_rgb_dev && num_selected_host && flip_host, "null pointer");
+    HeatTables tb;
+    memset(&tb, 0, sizeof(tb));
+    int at = 0;
+    for (int s = 0; s < num_slots; ++s) {
+        const int n = num_selected_host[s];
+        DF3D_CHECK_ARG(n >= 0 && n <= HM_MAXSEL, "0..32 selected planes per slot");
+        DF3D_CHECK_ARG(n == 0 || (planes_host && rgb_host), "null pointer");
+        tb.n[s] = n;
+        tb.flip[s] = flip_host[s] ? 1 : 0;
+        for (int k = 0; k < n; ++k, ++at) {
+            DF3D_CHECK_ARG(planes_host[at] >= 0 && planes_host[at] < num_planes, "plane index out of range");
+            tb.plane[s][k] = planes_host[at];
+            tb.rgb[s][k] = (unsigned int)rgb_host[3 * at] | (unsigned int)rgb_host[3 * at + 1] << 8 | (unsigned int)rgb_host[3 * at + 2] << 16;
+        }
+    }
+    hipLaunchKernelGGL(render_heatmap_kernel, dim3((width + 255) / 256, height, num_slots), dim3(256), 0, df3d::as_stream(stream), luma_dev, height, width,
+                       heatmaps_dev, num_planes, hm_height, hm_width, tb, cols, gain, out_rgb_dev);
     DF3D_LAUNCH_CHECK();
     return DF3D_OK;
 }

@@ -397,3 +397,50 @@ def filter_batch_2d(points2d, freq=100.0):
     (mincutoff 1e-4, beta 30, dcutoff 1) and its time stamps, which start at 0 where `filter_batch`'s start at 0.1.
     points2d [T, J, 2] float64 cuda; bit-identical to the reference's float arithmetic."""
     return oneeuro_filter(points2d, freq=freq, mincutoff=1e-4, beta=30.0, dcutoff=1.0, first_stamp=0, stamp_step=0.1)
+
+
+@_on_tensor_device
+def render_heatmap(luma, heatmaps, planes, colors, flip, gain=1.0, cols=None, out=None):
+    """Heat-maps drawn on camera images (df3d_render_heatmap), one launch for all views.
+    luma [S, H, W] uint8 cuda and heatmaps [S, P, Hh, Wh] float32 cuda, one view per slot (1 <= S <= 8); `planes[s]` lists the planes of
+    view s to draw (at most 32, any order), `colors[s]` one RGB triple per listed plane, `flip[s]` whether the network saw view s
+    mirrored.  A single view may be given without the leading axis (luma [H, W], heatmaps [P, Hh, Wh], planes and colors of that view,
+    flip a bool).  Every pixel shows (1 - a) grey + a colour of the plane whose bilinear sample, times `gain` and clamped to [0, 1], is
+    the largest a there.  Returns [ceil(S / cols) H, cols W, 3] uint8 cuda, view s at grid cell (s // cols, s % cols); `cols` defaults
+    to S (one row).  `out`: a contiguous uint8 CUDA tensor of at least that many bytes to draw into (bytes past the frame are not
+    touched); cells of a last row that S does not fill are zero in a tensor made here and untouched in `out`."""
+    lib = _native.load()
+    if isinstance(luma, torch.Tensor) and luma.dim() == 2:
+        luma, heatmaps, planes, colors, flip = luma.unsqueeze(0), heatmaps.unsqueeze(0), [planes], [colors], [flip]
+    _need(luma, torch.uint8, "luma")
+    _need(heatmaps, torch.float32, "heatmaps")
+    if luma.dim() != 3 or heatmaps.dim() != 4 or heatmaps.shape[0] != luma.shape[0] or heatmaps.device != luma.device:
+        raise ValueError("luma must be [S, H, W] and heatmaps [S, P, Hh, Wh] on one device")
+    S, H, W = (int(v) for v in luma.shape)
+    P, Hh, Wh = (int(v) for v in heatmaps.shape[1:])
+    if not (len(planes) == len(colors) == len(flip) == S):
+        raise ValueError("planes, colors and flip need one entry per view")
+    cols = S if cols is None else int(cols)
+    counts = [len(p) for p in planes]
+    flat = np.asarray([int(q) for p in planes for q in p], dtype=np.int32)
+    rgb = np.asarray([c for per_view in colors for c in per_view], dtype=np.int64).reshape(-1, 3)
+    if len(rgb) != len(flat) or any(len(c) != n for c, n in zip(colors, counts)):
+        raise ValueError("colors needs one RGB triple per selected plane")
+    if rgb.size and (rgb.min() < 0 or rgb.max() > 255):
+        raise ValueError("colors must lie in [0, 255]")
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    rows = -(-S // cols) if cols > 0 else 0
+    need = rows * H * cols * W * 3
+    if out is None:
+        out = (torch.empty if rows * cols == S else torch.zeros)((rows * H, cols * W, 3), dtype=torch.uint8, device=luma.device)
+    else:
+        _need(out, torch.uint8, "out")
+        if out.device != luma.device or out.numel() < need:
+            raise ValueError(f"out must hold at least {need} bytes on the images' device")
+    ip, up = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_ubyte)
+    _native.check(
+        lib.df3d_render_heatmap(luma.data_ptr(), H, W, heatmaps.data_ptr(), P, Hh, Wh, S, cols, (ctypes.c_int * S)(*counts), flat.ctypes.data_as(ip),
+                                rgb.ctypes.data_as(up), (ctypes.c_ubyte * S)(*[1 if f else 0 for f in flip]), float(gain), out.data_ptr(), _stream(luma)),
+        "df3d_render_heatmap",
+    )
+    return out if tuple(out.shape) == (rows * H, cols * W, 3) else out.view(-1)[:need].view(rows * H, cols * W, 3)

@@ -24,8 +24,8 @@ import sys
 import numpy as np
 import torch
 
-from . import _native, logger
-from .config import LIMB_COLORS, config, limb_of_joint, skeleton_bones
+from . import _native, logger, ops
+from .config import LIMB_COLORS, camera_is_flipped, config, heatmap_planes, limb_of_joint, plane_color, skeleton_bones
 
 DEFAULT_FPS = 30                     # reference video.py:19
 GRID_CAMERAS = (0, 1, 2, 4, 5, 6)    # reference video.py:35-36: the front camera (3) is not shown
@@ -100,6 +100,14 @@ class FrameRenderer:
                                                    out.stride(0) // 3, self._stream()), "df3d_resize_rgb")
         return out
 
+
+    def heatmap_grid(self, luma6, heatmaps6, camera_ordering=None, joints=(), gain=1.0, out=None):
+        """luma6 [6, H, W] uint8 cuda and heatmaps6 [6, 19, 64, 128] float32 cuda, the views of GRID_CAMERAS as the network saw them
+        -> [2 H, 3 W, 3] uint8 cuda: every camera image with its heat-maps drawn on it (ops.render_heatmap, one launch; DESIGN.md
+        section 13).  `joints` restricts the drawing to those ids of the 38-joint layout."""
+        pairs = [heatmap_planes(c, joints, camera_ordering) for c in GRID_CAMERAS]
+        return ops.render_heatmap(luma6, heatmaps6, [[p for p, _ in pr] for pr in pairs], [[plane_color(j) for _, j in pr] for pr in pairs],
+                                  [camera_is_flipped(c, camera_ordering) for c in GRID_CAMERAS], gain=gain, cols=3, out=out)
 
 # ---- encoders ------------------------------------------------------------------------------------------------------------------------
 class FfmpegWriter:
@@ -288,6 +296,55 @@ def make_pose3d_video(core, fps=None, progress=None):
         for i, grid in _grid_frames(core, renderer):
             renderer.resize(grid, frame[: 2 * sh])
             renderer.panels3d(pose[i].contiguous(), out=frame[2 * sh:])
+            host.copy_(frame)
+            writer.write(host.numpy())
+            if progress is not None:
+                progress()   # (multi-rank: rank 0's heartbeat to the waiting peers, distributed.primary_section)
+    finally:
+        writer.close()
+    logger.info(f"Video created at {path}\n")
+    return path
+
+
+def _heatmap_frames(core, renderer, batch=16, joints=()):
+    """Yield (img_id, [2 H, 3 W, 3] uint8 cuda) for every image: files -> device JPEG decode -> the hourglass on the batch's six views per
+    image -> one drawing launch per frame.  One batch of heat-maps (4.3 MB per frame) lives on the device at a time; none reaches the host."""
+    from . import jpeg
+    from .inference import PREPROCESS, get_engine
+
+    W, H = core.image_shape
+    engine = get_engine(dtype=core.dtype, device=renderer.dev)
+    flip6 = torch.tensor([1 if camera_is_flipped(c, core.camera_ordering) else 0 for c in GRID_CAMERAS], dtype=torch.uint8, device=renderer.dev)
+
+    def forward(e, luma, flip):
+        return e.forward_u8(luma, flip, PREPROCESS["mean"], PREPROCESS["std"], resize=PREPROCESS["resize"])
+
+    for t0 in range(0, core.num_images, batch):
+        ids = range(t0, min(t0 + batch, core.num_images))
+        blobs = [open(p, "rb").read() for i in ids for p in _frame_files(core, i)]
+        luma = jpeg.decode_luma(blobs, W, H, device=renderer.dev)   # [6 n, H, W], image-major
+        flip = flip6.repeat(len(ids))
+        if t0 == 0 and engine.dtype != "f32":   # a reduced-precision engine proves itself on the first image's views (HourglassEngine.canary)
+            engine.canary(get_engine(dtype="f32", device=renderer.dev), lambda e: forward(e, luma[:6], flip[:6]), what=f"the first views of {core.input_folder}")
+        hm = forward(engine, luma, flip)
+        luma, hm = luma.reshape(len(ids), 6, H, W), hm.reshape(len(ids), 6, *hm.shape[1:])
+        for k, i in enumerate(ids):
+            yield i, renderer.heatmap_grid(luma[k], hm[k], core.camera_ordering, joints)
+
+
+def make_heatmap_video(core, fps=None, progress=None, joints=()):
+    """video_heatmap_<folder>: per image the 2 x 3 camera grid of the pose-2d video with the network's heat-maps drawn on the images
+    instead of the pose.  Needs the images and the weights only, not a pose.  `joints` restricts the drawing to
+    those ids of the 38-joint layout.  Returns the path."""
+    if not core.has_heatmap:
+        raise FileNotFoundError(f"the heat-map video is computed from the images, and {core.input_folder} holds none (deleted with --delete-images?)")
+    fps = fps or DEFAULT_FPS
+    W, H = core.image_shape
+    renderer = FrameRenderer(H, W, config["num_joints"], core.device)
+    writer, path = open_writer(_video_stem(core, "heatmap"), 3 * W, 2 * H, fps)
+    host = torch.empty((2 * H, 3 * W, 3), dtype=torch.uint8).pin_memory()
+    try:
+        for _, frame in _heatmap_frames(core, renderer, joints=joints):
             host.copy_(frame)
             writer.write(host.numpy())
             if progress is not None:

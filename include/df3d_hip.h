@@ -505,6 +505,22 @@ int df3d_render_pose3d_panels(const double* points3d_dev, int num_joints, const 
 int df3d_resize_rgb(const unsigned char* in_dev, int in_h, int in_w, int in_pitch_px, unsigned char* out_dev, int out_h, int out_w,
                     int out_pitch_px, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Heat-map overlays: the network's heat-maps drawn on the camera images, one launch per frame.
+ * df3d_render_heatmap: luma_dev [num_slots, height, width] uint8 and heatmaps_dev [num_slots, num_planes, hm_height, hm_width] float32, one
+ *     view per slot (1..8); num_selected_host [num_slots] (0..32 each), planes_host and rgb_host hold the selected plane indices and their
+ *     RGB colours slot after slot ([sum n] and [sum n, 3]; may be null when nothing is selected), flip_host [num_slots] says whether the
+ *     network saw the view mirrored: all HOST tables.  Output pixel (y, x) of a slot samples every selected plane bilinearly at
+ *     (y hm_height / height, xs hm_width / width), xs = x or width - x when flipped (the arg-max convention: a plane's peak lands where
+ *     its detection is drawn), a = clamp(gain * value, 0, 1), a non-finite tap reads as 0; the plane of largest a wins (ties: the
+ *     earliest) and the pixel is floor((1 - a) grey + a colour + 0.5).  out_rgb_dev [ceil(num_slots / cols) height, cols width, 3] uint8,
+ *     slot s at grid cell (s / cols, s % cols); cells past the last slot are not written.  float64 arithmetic without multiply-add
+ *     fusion, restated in tests/heatmap_overlay_oracle.py.  Arguments are validated before the launch (DF3D_EINVAL: slots, columns,
+ *     sizes, a gain that is negative or not finite, a plane index outside [0, num_planes), a null pointer).  Asynchronous on `stream`. */
+int df3d_render_heatmap(const unsigned char* luma_dev, int height, int width, const float* heatmaps_dev, int num_planes, int hm_height,
+                        int hm_width, int num_slots, int cols, const int* num_selected_host, const int* planes_host,
+                        const unsigned char* rgb_host, const unsigned char* flip_host, double gain, unsigned char* out_rgb_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
