@@ -48,6 +48,22 @@ PICTORIAL_DEFAULTS = {
 # exceeds REPROJ_THR[j] pixels.  The reference's `config["reproj_thr"]` (df3d/config.py:41): 40 for each of the 38 joints.
 REPROJ_THR = np.full(38, 40.0, dtype=np.float64)
 
+# ---- leg joint angles.  Leg L = 3 side + l (l = 0, 1, 2: front, mid, hind) owns the five joints
+# 19 side + 5 l + k; its eight angles come in this order: thorax-coxa yaw, pitch and roll, coxa-trochanter pitch and roll,
+# femur-tibia pitch and roll, tibia-tarsus pitch; its four segment lengths are coxa, femur, tibia, tarsus.
+LEG_NAMES = ["side0_front", "side0_mid", "side0_hind", "side1_front", "side1_mid", "side1_hind"]
+LEG_ANGLE_NAMES = ["thc_yaw", "thc_pitch", "thc_roll", "ctr_pitch", "ctr_roll", "fti_pitch", "fti_roll", "tita_pitch"]
+
+
+def leg_joints(leg):
+    """The five joint ids (body-coxa, coxa-femur, femur-tibia, tibia-tarsus, tarsus tip) of leg `leg` (0..5)."""
+    leg = int(leg)
+    if not 0 <= leg < len(LEG_NAMES):
+        raise ValueError(f"no leg {leg}")
+    side, l = divmod(leg, 3)
+    return [config["num_predict"] * side + 5 * l + k for k in range(5)]
+
+
 # ---- which camera sees which joint (reference df3d/skeleton_fly.py:202-250), by camera id: cameras 0-2 look at the side whose
 # joints are 0..18, cameras 4-6 at the side of joints 19..37, camera 3 faces the fly.  Pinned by tests/golden/skeleton_tables.npz.
 # Where df3d::relayout_source (csrc/geometry_dev.h) fills a joint of a side camera under the identity ordering, this table sees it;

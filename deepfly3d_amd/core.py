@@ -343,6 +343,28 @@ class Core:
         """The previous image before `img_id` with a flagged joint, or None (reference df3d/core.py:217-227)."""
         return self.next_error_in_range(range(img_id - 1, -1, -1))
 
+    # -- leg joint angles (DESIGN.md section 14) --------------------------------------------------------------------------------------
+    def joint_angles(self, body_frame="recording"):
+        """(angles [T, 6, 8] radians, lengths [T, 6, 4]) as numpy arrays: the eight joint angles (config.LEG_ANGLE_NAMES) and four
+        segment lengths of every leg (config.LEG_NAMES), ops.joint_angles of the triangulation `camNet.points3d` -- what the result
+        calls points3d_wo_procrustes; the per-side Procrustes result registers the two sides separately and is not the input.
+        Triangulates first when the camera network holds no points3d yet; after editing detections call camNet.triangulate() (save()
+        does).  `body_frame`: "recording" (default), "per_frame" or an explicit [3, 3] / [T, 3, 3] array.  A rank-0 method, like the
+        reprojection-error queries."""
+        from . import distributed as dd
+
+        if dd.current()[0] != 0:
+            raise RuntimeError("joint_angles is a rank-0 method: the camera network lives on rank 0")
+        if self.camNet is None or not self.camNet.has_calibration():
+            raise RuntimeError("joint_angles needs calibrated cameras: run calibrate_calc() first")
+        if self.camNet.points3d is None:
+            self.camNet.triangulate()
+        _native.require_gpu()
+        dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
+        X = torch.from_numpy(np.ascontiguousarray(self.camNet.points3d, dtype=np.float64)).to(dev)
+        angles, lengths = ops.joint_angles(X, body_frame)
+        return angles.cpu().numpy(), lengths.cpu().numpy()
+
     # -- manual corrections (DESIGN.md section 11; reference df3d/core.py:253-296, 477-479, 509-544) ---------------------------------
     _MOVE_THRESHOLD = 30   # pixels, per coordinate: a pose that differs less from the estimate on every checked joint is not stored
 
@@ -501,8 +523,9 @@ class Core:
         dd.agree(bad, "the sharded triangulation")
         return None if full is None else full.cpu().numpy()
 
-    def save(self):
-        """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369)."""
+    def save(self, joint_angles=False):
+        """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
+        keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras)."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
@@ -511,12 +534,12 @@ class Core:
         error = None
         if self.is_primary:
             try:
-                self._write_result(pts3d_sharded)
+                self._write_result(pts3d_sharded, joint_angles)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
-    def _write_result(self, pts3d_sharded=None):
+    def _write_result(self, pts3d_sharded=None, joint_angles=False):
         result = {"points2d": np.copy(self.points2d)}
         if self.camNet is not None and self.camNet.has_calibration():
             if pts3d_sharded is not None:
@@ -535,6 +558,8 @@ class Core:
             result["points2d_argmax"] = np.copy(self.points2d_argmax)
         if getattr(self, "_subpixel", False):   # only when this run refined its detections: without it the schema is the reference's
             result["subpixel"] = True
+        if joint_angles:   # opt-in, like the two keys above: without it the schema is the reference's
+            result["joint_angles"], result["segment_lengths"] = self.joint_angles()
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")

@@ -345,6 +345,70 @@ def reprojection_errors(P, points2d_px, X=None, thresholds=None, frames=None):
     return err, jmax, mask
 
 
+def _need_pose(points3d):
+    _need(points3d, torch.float64, "points3d")
+    if points3d.dim() != 3 or tuple(points3d.shape[1:]) != (38, 3):
+        raise ValueError("points3d must be [T, 38, 3]")
+
+
+@_on_tensor_device
+def body_frame(points3d):
+    """points3d [n, 38, 3] float64 cuda -> [n, 3, 3]: rows ex, ey, ez of every pose's own body frame from its six body-coxa
+    joints (df3d_body_frame); all NaN where one of them is missing or the six are degenerate."""
+    lib = _native.load()
+    _need_pose(points3d)
+    n = points3d.shape[0]
+    out = torch.empty((n, 3, 3), dtype=torch.float64, device=points3d.device)
+    _native.check(lib.df3d_body_frame(points3d.data_ptr(), n, out.data_ptr(), _stream(points3d)), "df3d_body_frame")
+    return out
+
+
+_pose_frames = body_frame   # joint_angles' `body_frame` argument hides the function there
+
+
+def _recording_frame(points3d):
+    """[1, 3, 3]: the body frame of the pose whose 18 body-coxa coordinates are the exact temporal medians (column_median) of those
+    of points3d [T >= 1, 38, 3], taken over all frames as they stand: one frame for a tethered fly's recording."""
+    from .config import leg_joints
+
+    _need_pose(points3d)
+    coxae = torch.tensor([leg_joints(leg)[0] for leg in range(6)], device=points3d.device)
+    cols = points3d.index_select(1, coxae).reshape(points3d.shape[0], 18).t().contiguous()   # the median wants contiguous columns
+    pose = torch.zeros((1, 38, 3), dtype=torch.float64, device=points3d.device)
+    pose[0, coxae] = column_median(cols).reshape(6, 3)
+    return body_frame(pose)
+
+
+@_on_tensor_device
+def joint_angles(points3d, body_frame="recording"):
+    """Leg joint angles and segment lengths, df3d_joint_angles.  points3d [T, 38, 3] float64 cuda, the
+    layout of points3d_wo_procrustes.  `body_frame`: "recording" (one frame for all poses, from the temporal medians of the six
+    body-coxa joints), "per_frame" (every pose's own frame) or an explicit [3, 3] / [T, 3, 3] array or tensor (rows ex, ey, ez),
+    used as given.  Returns (angles [T, 6, 8] radians in the order of config.LEG_ANGLE_NAMES, lengths [T, 6, 4]) on the device;
+    NaN where a joint is missing or a direction is undefined."""
+    lib = _native.load()
+    _need_pose(points3d)
+    T, dev = points3d.shape[0], points3d.device
+    angles = torch.empty((T, 6, 8), dtype=torch.float64, device=dev)
+    lengths = torch.empty((T, 6, 4), dtype=torch.float64, device=dev)
+    if isinstance(body_frame, str):
+        if body_frame not in ("recording", "per_frame"):
+            raise ValueError('body_frame must be "recording", "per_frame" or a [3, 3] / [T, 3, 3] array')
+        frames = None
+    else:
+        frames = body_frame if isinstance(body_frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(body_frame, dtype=np.float64))
+        if tuple(frames.shape) not in ((3, 3), (1, 3, 3), (T, 3, 3)):
+            raise ValueError(f"an explicit body_frame must be [3, 3] or [T, 3, 3] with T = {T}")
+        frames = frames.to(device=dev, dtype=torch.float64).reshape(-1, 3, 3).contiguous()
+    if T == 0:   # no medians to take, nothing to launch
+        return angles, lengths
+    if frames is None:
+        frames = _recording_frame(points3d) if body_frame == "recording" else _pose_frames(points3d)
+    _native.check(lib.df3d_joint_angles(points3d.data_ptr(), T, frames.data_ptr(), frames.shape[0], angles.data_ptr(), lengths.data_ptr(),
+                                        _stream(points3d)), "df3d_joint_angles")
+    return angles, lengths
+
+
 def gaussian_window_taps(window_size, sigma, truncate=4.0):
     """[window_size] float64: what a Gaussian filter of deviation `sigma`, cut at int(truncate * sigma + 0.5) samples and applied
     to a line of `window_size` samples under nearest extension, multiplies each sample by to form output sample window_size // 2.

@@ -257,6 +257,29 @@ int df3d_oneeuro_filter(const double* in_dev, long long T, int nch, double freq,
                         double dcutoff, long long first_stamp, double stamp_step, double* out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a10 leg joint angles and segment lengths from the 3-D pose (the model is this project's own
+ *     specification, restated in float64 by tests/joint_angles_oracle.py).  The reference stops at the pose.
+ * pts_dev [n, 38, 3] float64, the layout of points3d_wo_procrustes.  Leg L = 3 side + l owns joints 19 side + 5 l + k, k = 0..4
+ *     (body-coxa .. tarsus tip).  A joint is missing when its three coordinates are exactly 0 or any of them is not finite.
+ * df3d_body_frame: frame_dev [n, 3, 3], rows ex, ey, ez of each pose's own frame from its six body-coxa joints C[side][l]:
+ *     ey along mean_l C[0][l] - mean_l C[1][l]; ex along the part perpendicular to ey of (C[0][0] + C[1][0]) / 2 -
+ *     (C[0][2] + C[1][2]) / 2 (hind to front); ez = ex x ey.  All NaN when one of the six joints is missing or either squared
+ *     length is at most 1e-18 of the largest squared norm of the six.
+ * df3d_joint_angles: frame_dev holds nframes = 1 frame for all poses or nframes = T, one per pose (taken as given; a frame
+ *     that holds a non-finite number makes its angles NaN).  Segment vectors are taken to leg coordinates (v.ex, s v.ey, v.ez),
+ *     s = +1 on side 0 and -1 on side 1.  angles_dev [T, 6, 8] radians: thc_yaw, thc_pitch, thc_roll, ctr_pitch, ctr_roll,
+ *     fti_pitch, fti_roll, tita_pitch (config.LEG_ANGLE_NAMES; definitions and NaN rules in DESIGN.md section 14); lengths_dev
+ *     [T, 6, 4] = coxa, femur, tibia, tarsus, NaN where an end joint is missing (may be NULL).  Coordinates whose fourth
+ *     powers overflow are outside the model.
+ * n, T >= 0 (0: nothing to do, nothing is launched); outputs overlap neither an input nor each other, and angles_dev and
+ *     lengths_dev are 16-byte aligned (they are written as 16-byte stores).
+ *     Both asynchronous on `stream`; arguments are validated before the device is touched.
+ * ---------------------------------------------------------------------------------------------- */
+int df3d_body_frame(const double* pts_dev, long long n, double* frame_dev, void* stream);
+int df3d_joint_angles(const double* pts_dev, long long T, const double* frame_dev, long long nframes, double* angles_dev,
+                      double* lengths_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
