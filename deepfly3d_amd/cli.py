@@ -64,6 +64,11 @@ def parse_cli_args(argv=None):
                    help="Append the leg joint angles (8 per leg, radians) and segment lengths (4 per leg) of the triangulated pose to the "
                         "result, as the keys joint_angles [T, 6, 8] and segment_lengths [T, 6, 4]; the body frame is the recording's, from "
                         "the temporal medians of the six body-coxa joints.  Works with --skip-pose-estimation on an earlier result")
+    p.add_argument("--rigid-legs", dest="rigid_legs", action="store_true",
+                   help="Fit legs of constant segment lengths (each segment's median over the recording) to the triangulated pose and append "
+                        "the keys points3d_rigid [T, 38, 3], rigid_segment_lengths [6, 4] and rigid_fit_cost [T, 6] to the result; together "
+                        "with --joint-angles also joint_angles_rigid [T, 6, 8], the angles of the fitted pose.  Works with "
+                        "--skip-pose-estimation on an earlier result")
     args = p.parse_args(argv)
     if args.auto_correct and args.skip_estimation:
         p.error("--auto-correct needs the heat-map peaks of this run's pose estimation: it cannot be combined with --skip-pose-estimation")
@@ -105,7 +110,8 @@ _NO_IMAGES = ("--video-heatmap draws the heat-maps the network computes from the
 def run(args):
     video_heatmap = getattr(args, "video_heatmap", False)
     joint_angles = getattr(args, "joint_angles", False)
-    if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not joint_angles:
+    rigid_legs = getattr(args, "rigid_legs", False)
+    if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not joint_angles and not rigid_legs:
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0
     logger.info(f"\nWorking in {args.input_folder}")
@@ -114,8 +120,9 @@ def run(args):
     core = Core(args.input_folder, args.output_folder, args.num_images_max, args.order, dtype=args.dtype, device=getattr(args, "device", None))
     if video_heatmap and not core.has_heatmap:
         raise FileNotFoundError(_NO_IMAGES.format(folder=args.input_folder))
-    if joint_angles and args.skip_estimation and core.points2d is None:
-        raise RuntimeError(f"--joint-angles needs calibrated cameras to triangulate with, and with --skip-pose-estimation {args.output_folder} "
+    if (joint_angles or rigid_legs) and args.skip_estimation and core.points2d is None:
+        flag = "--joint-angles" if joint_angles else "--rigid-legs"
+        raise RuntimeError(f"{flag} needs calibrated cameras to triangulate with, and with --skip-pose-estimation {args.output_folder} "
                            "holds no earlier result to reopen: run the pose estimation first")
     auto = getattr(args, "auto_correct", False)
     if not args.skip_estimation:
@@ -132,7 +139,7 @@ def run(args):
             core.auto_correct(flagged_only=True)
         elif auto:
             core.auto_correct()
-        core.save(joint_angles=joint_angles)
+        core.save(joint_angles=joint_angles, rigid_legs=rigid_legs)
     if args.video_2d or args.video_3d or video_heatmap:
         # f4 (reference cli.py:305-321): frames drawn on the GPU (csrc/render.hip), encoded by ffmpeg when present.  Rank 0 draws and
         # encodes; the peers wait for its outcome with a heartbeat (distributed.primary_section), so that an encoder failure moves

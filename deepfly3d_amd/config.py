@@ -64,6 +64,11 @@ def leg_joints(leg):
     return [config["num_predict"] * side + 5 * l + k for k in range(5)]
 
 
+# ---- constant-length legs: the most Newton iterations ops.fit_legs / --rigid-legs give a leg.  The golden
+# recording needs 5 at the most; a leg that is still moving after 30 reports status 1.
+RIGID_LEGS_MAX_ITER = 30
+
+
 # ---- which camera sees which joint (reference df3d/skeleton_fly.py:202-250), by camera id: cameras 0-2 look at the side whose
 # joints are 0..18, cameras 4-6 at the side of joints 19..37, camera 3 faces the fly.  Pinned by tests/golden/skeleton_tables.npz.
 # Where df3d::relayout_source (csrc/geometry_dev.h) fills a joint of a side camera under the identity ordering, this table sees it;

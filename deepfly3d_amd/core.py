@@ -344,26 +344,46 @@ class Core:
         return self.next_error_in_range(range(img_id - 1, -1, -1))
 
     # -- leg joint angles --------------------------------------------------------------------------------------
-    def joint_angles(self, body_frame="recording"):
-        """(angles [T, 6, 8] radians, lengths [T, 6, 4]) as numpy arrays: the eight joint angles (config.LEG_ANGLE_NAMES) and four
-        segment lengths of every leg (config.LEG_NAMES), ops.joint_angles of the triangulation `camNet.points3d` -- what the result
-        calls points3d_wo_procrustes; the per-side Procrustes result registers the two sides separately and is not the input.
-        Triangulates first when the camera network holds no points3d yet; after editing detections call camNet.triangulate() (save()
-        does).  `body_frame`: "recording" (default), "per_frame" or an explicit [3, 3] / [T, 3, 3] array.  A rank-0 method, like the
-        reprojection-error queries."""
+    def _measured_pose(self, what):
+        """camNet.points3d on the device (triangulating first when there is none), with the refusals of the rank-0 pose queries."""
         from . import distributed as dd
 
         if dd.current()[0] != 0:
-            raise RuntimeError("joint_angles is a rank-0 method: the camera network lives on rank 0")
+            raise RuntimeError(f"{what} is a rank-0 method: the camera network lives on rank 0")
         if self.camNet is None or not self.camNet.has_calibration():
-            raise RuntimeError("joint_angles needs calibrated cameras: run calibrate_calc() first")
+            raise RuntimeError(f"{what} needs calibrated cameras: run calibrate_calc() first")
         if self.camNet.points3d is None:
             self.camNet.triangulate()
         _native.require_gpu()
         dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
-        X = torch.from_numpy(np.ascontiguousarray(self.camNet.points3d, dtype=np.float64)).to(dev)
+        return torch.from_numpy(np.ascontiguousarray(self.camNet.points3d, dtype=np.float64)).to(dev)
+
+    def joint_angles(self, body_frame="recording", rigid=False):
+        """(angles [T, 6, 8] radians, lengths [T, 6, 4]) as numpy arrays: the eight joint angles (config.LEG_ANGLE_NAMES) and four
+        segment lengths of every leg (config.LEG_NAMES), ops.joint_angles of the triangulation `camNet.points3d` -- what the result
+        calls points3d_wo_procrustes; the per-side Procrustes result registers the two sides separately and is not the input.
+        Triangulates first when the camera network holds no points3d yet; after editing detections call camNet.triangulate() (save()
+        does).  `body_frame`: "recording" (default), "per_frame" or an explicit [3, 3] / [T, 3, 3] array.  `rigid=True`: the angles of
+        the constant-length pose rigid_legs() fits, whose lengths are the fixed ones; "recording" is then still
+        the recording frame of the MEASURED pose, so that both sets of angles share one frame.  A rank-0 method, like the
+        reprojection-error queries."""
+        X = self._measured_pose("joint_angles")
+        if rigid:
+            if isinstance(body_frame, str) and body_frame == "recording" and X.shape[0]:
+                body_frame = ops._recording_frame(X)
+            X = ops.fit_legs(X).points
         angles, lengths = ops.joint_angles(X, body_frame)
         return angles.cpu().numpy(), lengths.cpu().numpy()
+
+    # -- constant-length legs (DESIGN.md section 15) ------------------------------------------------------------------------------------
+    def rigid_legs(self, lengths="recording", anchor="per_frame"):
+        """(points [T, 38, 3], lengths [6, 4], cost [T, 6]) as numpy arrays: the triangulation `camNet.points3d` with every leg replaced
+        by the chain of constant segment lengths that lies closest to its measured joints (ops.fit_legs), the lengths used, and each
+        leg's summed squared distance from the measured joints (NaN where a leg misses a joint and is left as measured).  `lengths`:
+        "recording" (every segment's median over the recording) or a [6, 4] array; `anchor`: "per_frame", "recording" or a [6, 3]
+        array.  Triangulates first when there is no points3d yet.  A rank-0 method with joint_angles' refusals."""
+        fit = ops.fit_legs(self._measured_pose("rigid_legs"), lengths, anchor)
+        return fit.points.cpu().numpy(), np.array(fit.lengths), fit.cost.cpu().numpy()
 
     # -- manual corrections (DESIGN.md section 11; reference df3d/core.py:253-296, 477-479, 509-544) ---------------------------------
     _MOVE_THRESHOLD = 30   # pixels, per coordinate: a pose that differs less from the estimate on every checked joint is not stored
@@ -523,9 +543,11 @@ class Core:
         dd.agree(bad, "the sharded triangulation")
         return None if full is None else full.cpu().numpy()
 
-    def save(self, joint_angles=False):
+    def save(self, joint_angles=False, rigid_legs=False):
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
-        keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras)."""
+        keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras).
+        `rigid_legs=True` appends, after those, "points3d_rigid", "rigid_segment_lengths" and "rigid_fit_cost" (Core.rigid_legs()) and,
+        together with joint_angles, "joint_angles_rigid" (Core.joint_angles(rigid=True)[0])."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
@@ -534,12 +556,12 @@ class Core:
         error = None
         if self.is_primary:
             try:
-                self._write_result(pts3d_sharded, joint_angles)
+                self._write_result(pts3d_sharded, joint_angles, rigid_legs)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
-    def _write_result(self, pts3d_sharded=None, joint_angles=False):
+    def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False):
         result = {"points2d": np.copy(self.points2d)}
         if self.camNet is not None and self.camNet.has_calibration():
             if pts3d_sharded is not None:
@@ -560,6 +582,10 @@ class Core:
             result["subpixel"] = True
         if joint_angles:   # opt-in, like the two keys above: without it the schema is the reference's
             result["joint_angles"], result["segment_lengths"] = self.joint_angles()
+        if rigid_legs:
+            result["points3d_rigid"], result["rigid_segment_lengths"], result["rigid_fit_cost"] = self.rigid_legs()
+            if joint_angles:
+                result["joint_angles_rigid"] = self.joint_angles(rigid=True)[0]
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")

@@ -366,16 +366,23 @@ def body_frame(points3d):
 _pose_frames = body_frame   # joint_angles' `body_frame` argument hides the function there
 
 
-def _recording_frame(points3d):
-    """[1, 3, 3]: the body frame of the pose whose 18 body-coxa coordinates are the exact temporal medians (column_median) of those
-    of points3d [T >= 1, 38, 3], taken over all frames as they stand: one frame for a tethered fly's recording."""
+def _coxa_medians(points3d):
+    """(the six body-coxa joint ids, [6, 3] the exact temporal medians (column_median) of their 18 coordinates over all frames of
+    points3d [T >= 1, 38, 3] as they stand)."""
     from .config import leg_joints
 
     _need_pose(points3d)
     coxae = torch.tensor([leg_joints(leg)[0] for leg in range(6)], device=points3d.device)
     cols = points3d.index_select(1, coxae).reshape(points3d.shape[0], 18).t().contiguous()   # the median wants contiguous columns
+    return coxae, column_median(cols).reshape(6, 3)
+
+
+def _recording_frame(points3d):
+    """[1, 3, 3]: the body frame of the pose whose 18 body-coxa coordinates are the temporal medians of those of points3d
+    [T >= 1, 38, 3]: one frame for a tethered fly's recording."""
+    coxae, medians = _coxa_medians(points3d)
     pose = torch.zeros((1, 38, 3), dtype=torch.float64, device=points3d.device)
-    pose[0, coxae] = column_median(cols).reshape(6, 3)
+    pose[0, coxae] = medians
     return body_frame(pose)
 
 
@@ -407,6 +414,88 @@ def joint_angles(points3d, body_frame="recording"):
     _native.check(lib.df3d_joint_angles(points3d.data_ptr(), T, frames.data_ptr(), frames.shape[0], angles.data_ptr(), lengths.data_ptr(),
                                         _stream(points3d)), "df3d_joint_angles")
     return angles, lengths
+
+
+@_on_tensor_device
+def segment_length_medians(points3d):
+    """points3d [T, 38, 3] float64 cuda -> [6, 4]: the median over the frames of every leg segment's length (coxa, femur, tibia,
+    tarsus), the fixed lengths `fit_legs` uses by default.  The lengths are df3d_joint_angles' (they do not depend on the body
+    frame); a frame in which an end joint is missing does not count, so each median is numpy.nanmedian's value, taken by
+    column_median over the column's finite entries.  A segment without a finite length in any frame raises ValueError."""
+    from .config import LEG_NAMES
+
+    _need_pose(points3d)
+    T, dev = points3d.shape[0], points3d.device
+    names = ("coxa", "femur", "tibia", "tarsus")
+    if T == 0:
+        raise ValueError(f"leg 0 ({LEG_NAMES[0]}), segment 0 (coxa) has no finite length in any frame: there are no frames")
+    lengths = joint_angles(points3d, torch.eye(3, dtype=torch.float64, device=dev))[1]
+    cols = lengths.reshape(T, 24).t().contiguous()
+    finite = torch.isfinite(cols)
+    counts = finite.sum(dim=1).cpu()
+    if int(counts.min()) == T:
+        return column_median(cols).reshape(6, 4)
+    out = torch.empty((24,), dtype=torch.float64, device=dev)
+    for c in range(24):   # columns of different heights: one median each
+        if int(counts[c]) == 0:
+            raise ValueError(f"leg {c // 4} ({LEG_NAMES[c // 4]}), segment {c % 4} ({names[c % 4]}) has no finite length in any frame")
+        out[c] = column_median(cols[c][finite[c]].reshape(1, -1).contiguous())[0]
+    return out.reshape(6, 4)
+
+
+class LegFitResult:
+    """What `fit_legs` returns: points [T, 38, 3] float64 (the pose with every fitted leg replaced by its constant-length chain),
+    cost [T, 6] float64 (each leg's summed squared distance from the measured joints, NaN where the leg was not fitted),
+    status [T, 6] and iters [T, 6] int32 (0 converged, 1 max_iter reached, 2 the damping ran out, -1 not fitted; accepted
+    iterations, -1 where not fitted) -- device tensors -- and lengths [6, 4], the fixed lengths as used (a host numpy array)."""
+
+    def __init__(self, points, cost, status, iters, lengths):
+        self.points, self.cost, self.status, self.iters, self.lengths = points, cost, status, iters, lengths
+
+
+def _leg_table(value, shape, name):
+    """A host float64 array of `shape` from an array or tensor."""
+    a = value.detach().cpu().numpy() if isinstance(value, torch.Tensor) else np.asarray(value)
+    if a.shape != shape or a.dtype.kind not in "fiu":
+        raise ValueError(f"an explicit {name} must be a numeric {list(shape)} array")
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+@_on_tensor_device
+def fit_legs(points3d, lengths="recording", anchor="per_frame", max_iter=None):
+    """Fit a chain of constant segment lengths to every leg of every pose, df3d_leg_fit.  points3d
+    [T, 38, 3] float64 cuda, the layout of points3d_wo_procrustes.  `lengths`: "recording" (segment_length_medians(points3d)) or a
+    [6, 4] array.  `anchor`: "per_frame" (each leg starts at its own measured body-coxa joint), "recording" (at the temporal
+    median of that joint, one point per leg for the whole recording) or a [6, 3] array.  `max_iter` defaults to
+    config.RIGID_LEGS_MAX_ITER; 0 replays the measured directions with the fixed lengths.  Returns a LegFitResult; the input is
+    not changed, and the eight joints that belong to no leg are copied."""
+    from .config import RIGID_LEGS_MAX_ITER
+
+    max_iter = RIGID_LEGS_MAX_ITER if max_iter is None else int(max_iter)
+    if max_iter < 0:
+        raise ValueError("max_iter must be >= 0")
+    if isinstance(lengths, str) and lengths != "recording":
+        raise ValueError('lengths must be "recording" or a [6, 4] array')
+    if isinstance(anchor, str) and anchor not in ("per_frame", "recording"):
+        raise ValueError('anchor must be "per_frame", "recording" or a [6, 3] array')
+    table = None if isinstance(lengths, str) else _leg_table(lengths, (6, 4), "lengths")
+    origin = None if isinstance(anchor, str) else _leg_table(anchor, (6, 3), "anchor")
+    lib = _native.load()
+    _need_pose(points3d)
+    T, dev = points3d.shape[0], points3d.device
+    if table is None:
+        table = np.ascontiguousarray(segment_length_medians(points3d).cpu().numpy())
+    if isinstance(anchor, str) and anchor == "recording":
+        if T == 0:
+            raise ValueError('anchor="recording" needs at least one frame to take the medians of')
+        origin = np.ascontiguousarray(_coxa_medians(points3d)[1].cpu().numpy())
+    out = points3d.clone()
+    cost = torch.empty((T, 6), dtype=torch.float64, device=dev)
+    info = torch.empty((T, 6, 2), dtype=torch.int32, device=dev)
+    as_ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    _native.check(lib.df3d_leg_fit(points3d.data_ptr(), T, as_ptr(table), None if origin is None else as_ptr(origin), max_iter,
+                                   out.data_ptr(), cost.data_ptr(), info.data_ptr(), _stream(points3d)), "df3d_leg_fit")
+    return LegFitResult(out, cost, info[..., 0], info[..., 1], table)
 
 
 def gaussian_window_taps(window_size, sigma, truncate=4.0):

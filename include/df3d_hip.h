@@ -280,6 +280,30 @@ int df3d_joint_angles(const double* pts_dev, long long T, const double* frame_de
                       double* lengths_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a11 constant-length legs fitted to the 3-D pose (the model is this project's own specification, defined
+ *     in float64 by tests/leg_fit_oracle.py).  The reference stops at the pose.
+ * pts_dev [T, 38, 3] float64 as in a10, with a10's legs and "missing joint" rule.  lengths_host [6, 4]: the fixed lengths
+ *     (coxa, femur, tibia, tarsus) of every leg, finite and > 0.  anchor_host [6, 3] or NULL: where every leg starts; NULL
+ *     anchors each leg at its own measured body-coxa joint.  Both are HOST arrays, read before the call returns.
+ * Per (frame, leg): p0 = the anchor or the measured P0, targets t_k = P_k - p0 (k = 1..4), unknowns four unit directions d_i,
+ *     chain c_k = sum_{i <= k} l_i d_i, cost E = sum_k |c_k - t_k|^2, minimised from the measured directions by a damped Newton
+ *     method on the four spheres (tangent steps, an 8 x 8 Cholesky solve per trial, lambda from 0 in decades between 1e-3 and
+ *     1e12, a step of at most 1e-9 in every tangent coordinate ends it; section 15 has every constant).
+ * out_pts_dev [T, 38, 3]: the 30 leg joints, P0' = p0 and Pk' = p0 + c_k; the other eight joints are NOT written (the caller
+ *     fills them).  May be pts_dev itself (in place); otherwise it must not overlap pts_dev.
+ * cost_dev [T, 6]: the final E.  info_dev [T, 6, 2] int32, 8-byte aligned: (status, accepted iterations); status 0 = converged,
+ *     1 = max_iter reached (max_iter = 0: the measured directions replayed with the fixed lengths), 2 = lambda passed 1e12.
+ * A leg is not fitted -- its five joints are the input's bits, cost NaN, status -1, iterations -1 -- when one of P1..P4 is
+ *     missing, when P0 is missing and no anchor is given, or when a measured segment's squared length is at most 1e-18 of the
+ *     largest squared target.
+ * DF3D_EINVAL before the device is touched: T < 0, max_iter < 0, a null pointer (only the anchor may be), a length that is not
+ *     finite or not > 0, a non-finite anchor entry, out overlapping pts without being pts, cost or info overlapping anything,
+ *     a misaligned info.  T = 0 launches nothing.  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------------------------------- */
+int df3d_leg_fit(const double* pts_dev, long long T, const double* lengths_host, const double* anchor_host, int max_iter,
+                 double* out_pts_dev, double* cost_dev, int* info_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
