@@ -742,13 +742,15 @@ int run_persistent(const LsmrArgs& a, const Work& w, const df3d_lsmr::FusedArgs&
 // kernels need lives in the device-resident state, so the recording is valid for every chunk of every LSMR run on the same problem and
 // buffers (the three or four runs of one trust-region solve); otherwise the kernels are enqueued directly.
 // The recorded kernels take *p BY VALUE, so the key is every field of the problem (all index tables and the ncam / nobs / npts split, not
-// only their sum) plus every buffer the chunk touches: a recording is replayed only against exactly the arguments it was made with.
+// only their sum) plus every buffer the chunk touches, plus WHICH kernels were recorded (the eleven-kernel form and the two-kernel form run
+// on the same problem and buffers: LAUNCHES behind ELEVEN replayed the eleven kernels against its own, untouched state -- found by
+// tests/test_gpu_ba_sweep.py): a recording is replayed only against exactly the arguments it was made with.
 constexpr int CHUNK = 16;
 struct ChunkGraph {
-    static constexpr int NKEY = 12, NDIM = 5;
+    static constexpr int NKEY = 12, NDIM = 6;
     hipGraphExec_t exec = nullptr;
     const void* key[NKEY] = {};
-    long long dims[NDIM] = {0, 0, 0, 0, 0};
+    long long dims[NDIM] = {0, 0, 0, 0, 0, 0};
 
     // the recording of CHUNK x enqueue_iteration() for (key, dims): the one at hand, or a new one in its place; nullptr when the stream
     // refuses the capture (the caller then enqueues directly)
@@ -814,7 +816,7 @@ int run_chunked(const LsmrArgs& a, const Work& w, const df3d_lsmr::FusedArgs& fa
     hipGraphExec_t graph = nullptr;
     if (s != nullptr && a.maxiter >= CHUNK) {
         const void* key[ChunkGraph::NKEY] = {p->obs_xy, a.Jc, a.Jp, a.d, a.x, a.work_dev, p->cam_idx, p->pt_idx, p->intr4, p->pt_start, p->cam_perm, p->cam_start};
-        const long long dims[ChunkGraph::NDIM] = {(long long)m, (long long)n, p->ncam, p->nobs, p->npts};
+        const long long dims[ChunkGraph::NDIM] = {(long long)m, (long long)n, p->ncam, p->nobs, p->npts, eleven ? 11 : 2};
         graph = chunk_graph.lookup_or_record(key, dims, s, enqueue_iteration);
     }
     for (int done = 0; done < a.maxiter && now.istop == 0; done += CHUNK) {

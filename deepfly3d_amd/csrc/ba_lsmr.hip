@@ -543,7 +543,7 @@ __global__ __launch_bounds__(256) void fused_persistent(df3d_ba_problem p, Fused
 //     (2) and of the point entries of v, h, hbar, x (12 per point) in REGISTERS, read once; J v and J^T u for the point block touch only
 //     the workgroup's own data (a point's observations are consecutive), through LDS;
 //   * what is global is small: |u|^2 (+ the previous iteration's |x|^2) after the first half, the 6 x ncam camera sums of J^T u and
-//     |v|^2 after the second -- two ALL-REDUCES of 2 and 43 doubles per iteration, done with the guide's tagged granules (cdna_hip_programming.md
+//     |v|^2 after the second -- two ALL-REDUCES of 2 and 1 + 6 ncam (43 with seven cameras) doubles per iteration, done with the guide's tagged granules (cdna_hip_programming.md
 //     Guideline 16 R2: 8-byte {epoch, 32-bit value} agent-scope atomic stores, every workgroup sweeps all G x N x 2 granules until the
 //     tags match, no counter, no fence) and summed by every workgroup in the same fixed order, so all of them hold the same scalars and
 //     run the scalar steps themselves (the step functions are the ones of the other forms);
@@ -558,7 +558,8 @@ constexpr int LT = 512;             // threads per workgroup: 8 waves per CU = 2
 #endif
 constexpr int LK = DF3D_LSMR_LK;    // observations per thread
 constexpr int LOBS = LT * LK;       // observations per workgroup
-constexpr int LNAR = 43;            // doubles of the larger all-reduce: |v_points|^2 + 6 x 7 camera sums (MAX_CAM = 8 -> 49 would be needed: checked by the host)
+constexpr int LNAR = 49;            // doubles of the larger all-reduce at most: |v_points|^2 + 6 x ncam camera sums (43 with seven cameras, 49 with
+                                    // MAX_CAM = 8: the sizes of gathered / own / res / LAR2_STRIDE below; local_fits checks 1 + 6 ncam against it)
 constexpr int LMAXG = 128;          // workgroups (<= 130 000 observations: every window of 1 000 frames)
 constexpr int LRED = 16;            // partial sums per (camera, column) of the camera reduction (8 cameras x 3 columns x 16 <= LT threads)
 constexpr unsigned LSWEEP_LIMIT = 1u << 20;
@@ -1028,7 +1029,7 @@ __global__ __launch_bounds__(LT, 2) void lsmr_local_kernel(df3d_ba_problem p, Lo
 }
 
 // observation ranges of the data-local form: greedy, as many whole points as fit into LOBS observations AND into the LT point-owner threads of a
-// workgroup; one thread (G <= 64 steps of a binary search).  The kernel's layout assumes what bundle_adjust.py guarantees (every point seen by
+// workgroup; one thread (G <= LMAXG steps of a binary search).  The kernel's layout assumes what bundle_adjust.py guarantees (every point seen by
 // >= 2 cameras, <= 8 observations per point) but the C ABI does not: a problem with single-observation points has more than LT points per LOBS
 // observations, and a point of more than 8 observations can make the ranges run out before the observations do.  Either way the partition does
 // not cover [0, nobs) in gmax ranges: wg_obs[gmax] != nobs, which lsmr_local_kernel reports as "does not fit" (istop -2: the caller falls back
@@ -1058,7 +1059,7 @@ int local_max_workgroups() { return LMAXG; }
 int local_workgroups_for(int nobs) { return (nobs + (LOBS - 8) - 1) / (LOBS - 8); }   // a range holds at least LOBS - 7 observations (a point has <= 8)
 size_t local_scratch_bytes() { return (size_t)(LMAXG + 1) * sizeof(int) + 64 + 2 * (LAR1_STRIDE + LAR2_STRIDE) * sizeof(unsigned long long); }
 
-bool local_fits(const df3d_ba_problem& p) { return local_workgroups_for(p.nobs) <= LMAXG && 1 + 6 * p.ncam <= 49; }
+bool local_fits(const df3d_ba_problem& p) { return local_workgroups_for(p.nobs) <= LMAXG && 1 + 6 * p.ncam <= LNAR; }
 
 // development (DF3D_LSMR_DEBUG): every all-reduce's inputs and outputs of every workgroup of the run just launched, checked on the host
 static void check_local_debug_log(const double* dbg, int G, hipStream_t s) {
@@ -1103,7 +1104,7 @@ static void check_local_debug_log(const double* dbg, int G, hipStream_t s) {
 int launch_local(const df3d_ba_problem& p, const double* Jc, const double* Jp, const double* d, const double* b, double* x, double damp, double atol,
                  double btol, double ctol, int maxiter, void* scratch, double* state_out, hipStream_t s, const double* damp_dev) {
     const int G = local_workgroups_for(p.nobs);
-    if (G > LMAXG || 1 + 6 * p.ncam > 49) return -1;
+    if (G > LMAXG || 1 + 6 * p.ncam > LNAR) return -1;
     if (hipMemsetAsync(scratch, 0, local_scratch_bytes(), s) != hipSuccess) return -2;
     int* const wg_obs = reinterpret_cast<int*>(scratch);
     unsigned long long* const gr1 = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(scratch) + (((size_t)(LMAXG + 1) * sizeof(int) + 63) & ~size_t(63)));

@@ -155,8 +155,9 @@ def matrix_from_rotvec(rvec):
     return out[0] if single else out
 
 
-def build_observations(points2d_px):
-    """Observation table in (frame, joint, camera) order; points with >= 2 views only.
+def build_observations(points2d_px, min_views=2):
+    """Observation table in (frame, joint, camera) order; points with >= min_views views only (2: what an
+    adjustment needs; 1 only in tests of problems the device library accepts but no adjustment builds).
 
     Returns cam_idx (n,), pt_idx (n,), obs_xy (n, 2) as (x = col_px, y = row_px), and the
     (t, j) -> point slot map (T, J) with -1 for untriangulated joints."""
@@ -165,7 +166,7 @@ def build_observations(points2d_px):
     vis = visibility(p)
     nviews = vis.sum(axis=0)
     slot = np.full((T, J), -1, dtype=np.int64)
-    ok = nviews >= 2
+    ok = nviews >= min_views
     slot[ok] = np.arange(int(ok.sum()))
     cam_idx, pt_idx, obs = [], [], []
     for t in range(T):
