@@ -95,6 +95,11 @@ PROTOTYPES = {
     "df3d_body_frame": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p]),
     "df3d_joint_angles": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p]),
     "df3d_leg_fit": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_spectrogram_tile": (c_int, []),
+    "df3d_spectrogram_work_bytes": (c_longlong, [c_void_p, c_int, c_double, c_double, c_double]),
+    "df3d_spectrogram_bank": (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_longlong, c_void_p]),
+    "df3d_spectrogram": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_longlong, c_void_p, c_int,
+                         c_void_p]),
     "df3d_ba_eval": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_colsq": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_matvec": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

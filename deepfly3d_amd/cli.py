@@ -69,6 +69,12 @@ def parse_cli_args(argv=None):
                         "the keys points3d_rigid [T, 38, 3], rigid_segment_lengths [6, 4] and rigid_fit_cost [T, 6] to the result; together "
                         "with --joint-angles also joint_angles_rigid [T, 6, 8], the angles of the fitted pose.  Works with "
                         "--skip-pose-estimation on an earlier result")
+    p.add_argument("--angle-spectrogram", dest="angle_spectrogram", action="store_true",
+                   help="Append the Morlet wavelet amplitudes of the 48 joint-angle series to the result, as the keys angle_spectrogram "
+                        "[T, 6, 8, F] (float32, radians), spectrogram_freqs [F] (Hz) and spectrogram_fps: 25 frequencies from 1 Hz to a quarter "
+                        "of the frame rate (100 fps where the recording has no videos to read it from); together with --rigid-legs also "
+                        "angle_spectrogram_rigid, the same of the fitted pose.  The angles themselves are stored only with --joint-angles.  "
+                        "Works with --skip-pose-estimation on an earlier result")
     args = p.parse_args(argv)
     if args.auto_correct and args.skip_estimation:
         p.error("--auto-correct needs the heat-map peaks of this run's pose estimation: it cannot be combined with --skip-pose-estimation")
@@ -111,7 +117,9 @@ def run(args):
     video_heatmap = getattr(args, "video_heatmap", False)
     joint_angles = getattr(args, "joint_angles", False)
     rigid_legs = getattr(args, "rigid_legs", False)
-    if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not joint_angles and not rigid_legs:
+    angle_spectrogram = getattr(args, "angle_spectrogram", False)
+    if (args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not joint_angles and not rigid_legs
+            and not angle_spectrogram):
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0
     logger.info(f"\nWorking in {args.input_folder}")
@@ -120,8 +128,8 @@ def run(args):
     core = Core(args.input_folder, args.output_folder, args.num_images_max, args.order, dtype=args.dtype, device=getattr(args, "device", None))
     if video_heatmap and not core.has_heatmap:
         raise FileNotFoundError(_NO_IMAGES.format(folder=args.input_folder))
-    if (joint_angles or rigid_legs) and args.skip_estimation and core.points2d is None:
-        flag = "--joint-angles" if joint_angles else "--rigid-legs"
+    if (joint_angles or rigid_legs or angle_spectrogram) and args.skip_estimation and core.points2d is None:
+        flag = "--joint-angles" if joint_angles else "--rigid-legs" if rigid_legs else "--angle-spectrogram"
         raise RuntimeError(f"{flag} needs calibrated cameras to triangulate with, and with --skip-pose-estimation {args.output_folder} "
                            "holds no earlier result to reopen: run the pose estimation first")
     auto = getattr(args, "auto_correct", False)
@@ -139,7 +147,7 @@ def run(args):
             core.auto_correct(flagged_only=True)
         elif auto:
             core.auto_correct()
-        core.save(joint_angles=joint_angles, rigid_legs=rigid_legs)
+        core.save(joint_angles=joint_angles, rigid_legs=rigid_legs, angle_spectrogram=angle_spectrogram)
     if args.video_2d or args.video_3d or video_heatmap:
         # f4 (reference cli.py:305-321): frames drawn on the GPU (csrc/render.hip), encoded by ffmpeg when present.  Rank 0 draws and
         # encodes; the peers wait for its outcome with a heartbeat (distributed.primary_section), so that an encoder failure moves

@@ -69,6 +69,23 @@ def leg_joints(leg):
 RIGID_LEGS_MAX_ITER = 30
 
 
+# ---- Morlet wavelet spectrograms of the joint angles.  The default bank: SPECTROGRAM_NUM_FREQS frequencies
+# spaced geometrically from SPECTROGRAM_F_MIN Hz to fps * SPECTROGRAM_F_MAX_OVER_FPS (a quarter of the sampling rate: above it the
+# negative-frequency image of a real series folds into the row), a wavelet of SPECTROGRAM_OMEGA0 radians per deviation cut at
+# SPECTROGRAM_RADIUS deviations.  SPECTROGRAM_FPS stands in where the recording's frame rate is unknown (Core.get_fps() is None).
+# SPECTROGRAM_TILE is the number of consecutive times one block of the kernel owns, SPECTROGRAM_MAX_SUPPORT the cap on K_i.
+SPECTROGRAM_F_MIN = 1.0
+SPECTROGRAM_F_MAX_OVER_FPS = 0.25
+SPECTROGRAM_NUM_FREQS = 25
+SPECTROGRAM_OMEGA0 = 5.0
+SPECTROGRAM_RADIUS = 6.0
+SPECTROGRAM_FPS = 100.0
+SPECTROGRAM_TILE = 320
+SPECTROGRAM_MAX_SUPPORT = 2048
+# the angles of LEG_ANGLE_NAMES that live on the full circle and are unwrapped along time before the transform
+SPECTROGRAM_UNWRAPPED_ANGLES = ("thc_pitch", "thc_roll", "ctr_roll", "fti_roll")
+
+
 # ---- which camera sees which joint (reference df3d/skeleton_fly.py:202-250), by camera id: cameras 0-2 look at the side whose
 # joints are 0..18, cameras 4-6 at the side of joints 19..37, camera 3 faces the fly.  Pinned by tests/golden/skeleton_tables.npz.
 # Where df3d::relayout_source (csrc/geometry_dev.h) fills a joint of a side camera under the identity ordering, this table sees it;

@@ -367,13 +367,16 @@ class Core:
         the constant-length pose rigid_legs() fits, whose lengths are the fixed ones; "recording" is then still
         the recording frame of the MEASURED pose, so that both sets of angles share one frame.  A rank-0 method, like the
         reprojection-error queries."""
-        X = self._measured_pose("joint_angles")
+        angles, lengths = self._joint_angles_on_device("joint_angles", body_frame, rigid)
+        return angles.cpu().numpy(), lengths.cpu().numpy()
+
+    def _joint_angles_on_device(self, what, body_frame, rigid):
+        X = self._measured_pose(what)
         if rigid:
             if isinstance(body_frame, str) and body_frame == "recording" and X.shape[0]:
                 body_frame = ops._recording_frame(X)
             X = ops.fit_legs(X).points
-        angles, lengths = ops.joint_angles(X, body_frame)
-        return angles.cpu().numpy(), lengths.cpu().numpy()
+        return ops.joint_angles(X, body_frame)
 
     # -- constant-length legs (DESIGN.md section 15) ------------------------------------------------------------------------------------
     def rigid_legs(self, lengths="recording", anchor="per_frame"):
@@ -384,6 +387,47 @@ class Core:
         array.  Triangulates first when there is no points3d yet.  A rank-0 method with joint_angles' refusals."""
         fit = ops.fit_legs(self._measured_pose("rigid_legs"), lengths, anchor)
         return fit.points.cpu().numpy(), np.array(fit.lengths), fit.cost.cpu().numpy()
+
+    # -- wavelet spectrograms of the joint angles (DESIGN.md section 16) ----------------------------------------------------------------
+    def angle_spectrogram(self, rigid=False, body_frame="recording", fps=None, unwrap=True, **bank):
+        """(S [T, 6, 8, F], freqs [F]) as numpy arrays: the Morlet wavelet amplitudes (ops.wavelet_spectrogram, radians) of the
+        48 joint-angle series joint_angles(body_frame, rigid) returns, and the rows' frequencies in Hz.  `fps`: the sampling rate;
+        None means get_fps(), and where that is None config.SPECTROGRAM_FPS.  `unwrap=True` first applies numpy.unwrap's rule
+        along time to the angles that live on the full circle (config.SPECTROGRAM_UNWRAPPED_ANGLES): a wrap at +-pi is otherwise
+        a step of 2 pi that lights up every row.  A series that holds a non-finite sample is left wrapped and named in one logged
+        warning.  `bank`: f_min, f_max, num (ops.wavelet_frequencies) or freqs, and omega0, radius.  A rank-0 method with
+        joint_angles' refusals."""
+        S, freqs, _ = self._angle_spectrogram(rigid, body_frame, fps, unwrap, torch.float64, bank)
+        return S, freqs
+
+    def _angle_spectrogram(self, rigid, body_frame, fps, unwrap, dtype, bank):
+        from . import config
+
+        bank = dict(bank)
+        unknown = set(bank) - {"f_min", "f_max", "num", "freqs", "omega0", "radius"}
+        if unknown:
+            raise TypeError(f"angle_spectrogram got unexpected bank arguments {sorted(unknown)}")
+        if "freqs" in bank and {"f_min", "f_max", "num"} & set(bank):
+            raise TypeError("give either freqs or f_min / f_max / num, not both")
+        if fps is None:
+            fps = self.get_fps()
+        if fps is None:
+            fps = config.SPECTROGRAM_FPS
+        fps = float(fps)
+        freqs = bank["freqs"] if "freqs" in bank else ops.wavelet_frequencies(fps, bank.get("f_min"), bank.get("f_max"), bank.get("num"))
+        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
+        angles = self._joint_angles_on_device("angle_spectrogram", body_frame, rigid)[0]
+        T = angles.shape[0]
+        series = angles.reshape(T, 48)
+        if unwrap:
+            names = config.LEG_ANGLE_NAMES
+            cols = [8 * leg + names.index(a) for leg in range(6) for a in config.SPECTROGRAM_UNWRAPPED_ANGLES]
+            series, left = ops.unwrap_phase(series, cols)
+            if left:
+                logger.warning("angle_spectrogram: not unwrapped, because they hold a non-finite sample: "
+                               + ", ".join(f"{config.LEG_NAMES[c // 8]} {names[c % 8]}" for c in left))
+        S = ops.wavelet_spectrogram(series.reshape(T, 6, 8), fps, freqs, bank.get("omega0"), bank.get("radius"), dtype=dtype)
+        return S.cpu().numpy(), freqs, fps
 
     # -- manual corrections (DESIGN.md section 11; reference df3d/core.py:253-296, 477-479, 509-544) ---------------------------------
     _MOVE_THRESHOLD = 30   # pixels, per coordinate: a pose that differs less from the estimate on every checked joint is not stored
@@ -543,11 +587,13 @@ class Core:
         dd.agree(bad, "the sharded triangulation")
         return None if full is None else full.cpu().numpy()
 
-    def save(self, joint_angles=False, rigid_legs=False):
+    def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False):
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
         keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras).
         `rigid_legs=True` appends, after those, "points3d_rigid", "rigid_segment_lengths" and "rigid_fit_cost" (Core.rigid_legs()) and,
-        together with joint_angles, "joint_angles_rigid" (Core.joint_angles(rigid=True)[0])."""
+        together with joint_angles, "joint_angles_rigid" (Core.joint_angles(rigid=True)[0]).  `angle_spectrogram=True` appends,
+        after all of those, "angle_spectrogram" [T, 6, 8, F] float32 (Core.angle_spectrogram() with its defaults),
+        "spectrogram_freqs" [F], "spectrogram_fps" and, together with rigid_legs, "angle_spectrogram_rigid"."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
@@ -556,12 +602,12 @@ class Core:
         error = None
         if self.is_primary:
             try:
-                self._write_result(pts3d_sharded, joint_angles, rigid_legs)
+                self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
-    def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False):
+    def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False):
         result = {"points2d": np.copy(self.points2d)}
         if self.camNet is not None and self.camNet.has_calibration():
             if pts3d_sharded is not None:
@@ -586,6 +632,11 @@ class Core:
             result["points3d_rigid"], result["rigid_segment_lengths"], result["rigid_fit_cost"] = self.rigid_legs()
             if joint_angles:
                 result["joint_angles_rigid"] = self.joint_angles(rigid=True)[0]
+        if angle_spectrogram:
+            result["angle_spectrogram"], result["spectrogram_freqs"], result["spectrogram_fps"] = self._angle_spectrogram(
+                False, "recording", None, True, torch.float32, {})
+            if rigid_legs:
+                result["angle_spectrogram_rigid"] = self._angle_spectrogram(True, "recording", None, True, torch.float32, {})[0]
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")

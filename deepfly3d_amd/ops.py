@@ -498,6 +498,118 @@ def fit_legs(points3d, lengths="recording", anchor="per_frame", max_iter=None):
     return LegFitResult(out, cost, info[..., 0], info[..., 1], table)
 
 
+def wavelet_frequencies(fps, f_min=None, f_max=None, num=None):
+    """[num] float64 (numpy): the bank's frequencies f_i = f_min (f_max / f_min)^(i / (num - 1)) in Hz, geometric from f_min to
+    f_max; num = 1 gives f_min.  Defaults (config): f_min = SPECTROGRAM_F_MIN, f_max = fps * SPECTROGRAM_F_MAX_OVER_FPS,
+    num = SPECTROGRAM_NUM_FREQS.  f_max may be raised to fps / 2, where the negative-frequency image of a real series folds into
+    the row."""
+    from . import config
+
+    fps = float(fps)
+    f_min = config.SPECTROGRAM_F_MIN if f_min is None else float(f_min)
+    f_max = fps * config.SPECTROGRAM_F_MAX_OVER_FPS if f_max is None else float(f_max)
+    num = config.SPECTROGRAM_NUM_FREQS if num is None else int(num)
+    if not (np.isfinite(fps) and fps > 0):
+        raise ValueError("fps must be finite and > 0")
+    if not (np.isfinite(f_min) and f_min > 0):
+        raise ValueError("f_min must be finite and > 0")
+    if not 1 <= num <= 64:
+        raise ValueError("num must be in [1, 64]")
+    if not f_max >= f_min:
+        raise ValueError(f"f_max ({f_max:g}) must not be below f_min ({f_min:g})")
+    if not f_max <= fps / 2:
+        raise ValueError(f"f_max ({f_max:g}) must be at most fps / 2 ({fps / 2:g})")
+    if num == 1:
+        return np.array([f_min], dtype=np.float64)
+    freqs = f_min * (f_max / f_min) ** (np.arange(num, dtype=np.float64) / (num - 1))
+    freqs[-1] = f_max   # the power rounds: the last row is f_max itself, so that f_max = fps / 2 stays admissible
+    return freqs
+
+
+def _wavelet_bank(fps, freqs, omega0, radius):
+    """(fps, freqs [F] contiguous float64 numpy, omega0, radius, the workspace's bytes) with the defaults filled in, refused by the
+    library's own rules (ValueError with its message) before a device is touched."""
+    from . import config
+
+    fps = float(fps)
+    omega0 = config.SPECTROGRAM_OMEGA0 if omega0 is None else float(omega0)
+    radius = config.SPECTROGRAM_RADIUS if radius is None else float(radius)
+    if freqs is None:
+        freqs = wavelet_frequencies(fps)
+    freqs = freqs.detach().cpu().numpy() if isinstance(freqs, torch.Tensor) else np.asarray(freqs)
+    if freqs.ndim != 1 or freqs.dtype.kind not in "fiu":
+        raise ValueError("freqs must be a numeric [F] array")
+    freqs = np.ascontiguousarray(freqs, dtype=np.float64)
+    lib = _native.load()
+    need = lib.df3d_spectrogram_work_bytes(freqs.ctypes.data_as(ctypes.c_void_p), freqs.shape[0], fps, omega0, radius)
+    if need <= 0:
+        raise ValueError(lib.df3d_last_error().decode())
+    return fps, freqs, omega0, radius, need
+
+
+def wavelet_support(fps, freqs=None, omega0=None, radius=None):
+    """[F] int64 (numpy): K_i = ceil(radius omega0 fps / (2 pi f_i)), the half support of every row in samples.  Row i of
+    wavelet_spectrogram at time t reads the samples t - K_i .. t + K_i: within K_i of either end it leans on the edge extension."""
+    fps, freqs, omega0, radius, _ = _wavelet_bank(fps, freqs, omega0, radius)
+    return np.ceil(radius * (omega0 * fps / (2.0 * np.pi * freqs))).astype(np.int64)
+
+
+@_on_tensor_device
+def wavelet_spectrogram(series, fps, freqs=None, omega0=None, radius=None, dtype=torch.float64):
+    """Morlet wavelet amplitudes of every channel of a bundle of time series, df3d_spectrogram.  series
+    [T], [T, C] or [T, ...] float64 cuda, time first; the trailing axes are flattened and restored, so [T, 6, 8] gives
+    [T, 6, 8, F].  `fps` the sampling rate in Hz; `freqs` the rows' frequencies (default wavelet_frequencies(fps)); `omega0`,
+    `radius` default to config's.  Returns [T, ..., F] of `dtype` (torch.float64, or torch.float32: accumulated in float64 and
+    rounded once) on the series' device and stream: an amplitude in the units of the series, the ends extended by their edge
+    value, NaN exactly where a sample within K_i (wavelet_support) of the time is not finite."""
+    if dtype not in (torch.float64, torch.float32):
+        raise ValueError("dtype must be torch.float64 or torch.float32")
+    fps, freqs, omega0, radius, need = _wavelet_bank(fps, freqs, omega0, radius)
+    if not (isinstance(series, torch.Tensor) and series.is_cuda and series.dtype == torch.float64 and series.dim() >= 1):
+        raise ValueError("series must be a torch.float64 CUDA tensor of shape [T, ...]")
+    lib = _native.load()
+    T, shape, F, dev = series.shape[0], tuple(series.shape), freqs.shape[0], series.device
+    C = int(np.prod(shape[1:], dtype=np.int64))
+    if C < 1:
+        raise ValueError("series must hold at least one channel")
+    x = series.reshape(T, C).t().contiguous()   # [C, T]: a block reads one channel's run of times
+    work = torch.empty((need,), dtype=torch.uint8, device=dev)
+    out = torch.empty((T, C, F), dtype=dtype, device=dev)
+    fp, stream = freqs.ctypes.data_as(ctypes.c_void_p), _stream(series)
+    _native.check(lib.df3d_spectrogram_bank(fp, F, fps, omega0, radius, work.data_ptr(), need, stream), "df3d_spectrogram_bank")
+    _native.check(lib.df3d_spectrogram(x.data_ptr(), T, C, fp, F, fps, omega0, radius, work.data_ptr(), need, out.data_ptr(),
+                                       int(dtype == torch.float32), stream), "df3d_spectrogram")
+    return out.reshape(*shape, F)
+
+
+def unwrap_phase(series, channels=None):
+    """numpy.unwrap's rule along time on the device: series [T, C] float64 (any device), `channels` the columns to unwrap (a
+    list of indices; default all).  Every step between consecutive samples is brought into [-pi, pi] by a multiple of 2 pi (a
+    step of exactly -pi that came from a positive difference becomes +pi; a step whose size is below pi is left alone) and the
+    corrections are summed up.  A requested column that holds a non-finite sample is left as it is.  Returns (the unwrapped
+    copy, the list of the columns left for that reason)."""
+    if not (isinstance(series, torch.Tensor) and series.dtype == torch.float64 and series.dim() == 2):
+        raise ValueError("series must be a torch.float64 tensor of shape [T, C]")
+    T, C = series.shape
+    cols = list(range(C)) if channels is None else [int(c) for c in channels]
+    if any(not 0 <= c < C for c in cols):
+        raise ValueError(f"channels must lie in [0, {C})")
+    out = series.clone()
+    if T < 2 or not cols:
+        return out, []
+    idx = torch.tensor(cols, device=series.device)
+    p = series.index_select(1, idx)
+    finite = torch.isfinite(p).all(dim=0)
+    d = p[1:] - p[:-1]
+    m = torch.remainder(d + np.pi, 2.0 * np.pi) - np.pi
+    m = torch.where((m == -np.pi) & (d > 0), torch.full_like(m, np.pi), m)
+    corr = torch.where(d.abs() < np.pi, torch.zeros_like(d), m - d)
+    up = p.clone()
+    up[1:] += torch.cumsum(corr, dim=0)
+    out[:, idx] = torch.where(finite.unsqueeze(0), up, p)
+    return out, [c for c, ok in zip(cols, finite.cpu().tolist()) if not ok]
+
+
 def gaussian_window_taps(window_size, sigma, truncate=4.0):
     """[window_size] float64: what a Gaussian filter of deviation `sigma`, cut at int(truncate * sigma + 0.5) samples and applied
     to a line of `window_size` samples under nearest extension, multiplies each sample by to form output sample window_size // 2.

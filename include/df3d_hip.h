@@ -304,6 +304,33 @@ int df3d_leg_fit(const double* pts_dev, long long T, const double* lengths_host,
                  double* out_pts_dev, double* cost_dev, int* info_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a12 Morlet wavelet spectrogram of a bundle of time series (the model is this project's own
+ *     specification, defined in float64 by tests/spectrogram_oracle.py).  The reference stops at the pose.
+ * The bank: F frequencies freqs_host [F] (Hz, a HOST array read before the call returns, ascending), the sampling rate fps, the
+ *     wavelet's centre omega0 and the cut radius.  Row i: sigma_i = omega0 fps / (2 pi f_i) samples, K_i = ceil(radius sigma_i),
+ *     and for k = -K_i..K_i: g = exp(-k^2 / (2 sigma_i^2)), phi = 2 pi f_i k / fps, kappa_i = sum g cos phi / sum g,
+ *     n_i = 2 / sum g, a_i[k] = n_i g (cos phi - kappa_i), b_i[k] = -n_i g sin phi.
+ * df3d_spectrogram_work_bytes: the bytes of the caller-owned DEVICE workspace that holds the bank's tap pairs (0 where the bank is
+ *     refused).  df3d_spectrogram_bank fills it (one small kernel); df3d_spectrogram reads it and must be given the same bank.
+ * x_dev [C, T] float64, channel-major.  out_dev [T, C, F], float64 (out_f32 = 0) or float32 (out_f32 = 1; accumulated in float64
+ *     and rounded once): S[t, c, i] = sqrt(A^2 + B^2), A = sum_k a_i[k] x[c, clamp(t + k, 0, T - 1)], B likewise with b_i; NaN
+ *     where A or B is not finite, that is where a sample in the support of (t, i) is not finite.
+ * df3d_spectrogram_tile: the number of consecutive times one block owns (a test sweeps T around it).
+ * DF3D_EINVAL before the device is touched, with a message that names the argument: T < 0, C < 1, F outside [1, 64]; fps,
+ *     freqs[0] (f_min), omega0 or radius not finite and > 0; descending frequencies (f_max < f_min); f_max > fps / 2; a K_i above
+ *     the cap of 2048 samples (the message gives the smallest f_min that fits); out_f32 other than 0 or 1; a null pointer; x not
+ *     8-byte aligned, out not aligned to its element, work not 16-byte aligned; out overlapping x, work overlapping either; a
+ *     workspace below df3d_spectrogram_work_bytes; more than 2^31 - 1 blocks.  T = 0 launches nothing (its pointers may be NULL).
+ *     Both launching entries are asynchronous on `stream`; neither allocates nor keeps a host pointer.
+ * ---------------------------------------------------------------------------------------------- */
+int df3d_spectrogram_tile(void);
+long long df3d_spectrogram_work_bytes(const double* freqs_host, int F, double fps, double omega0, double radius);
+int df3d_spectrogram_bank(const double* freqs_host, int F, double fps, double omega0, double radius, void* work_dev,
+                          long long work_len_bytes, void* stream);
+int df3d_spectrogram(const double* x_dev, long long T, int C, const double* freqs_host, int F, double fps, double omega0,
+                     double radius, const void* work_dev, long long work_len_bytes, void* out_dev, int out_f32, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
