@@ -339,19 +339,44 @@ __global__ void rigid_fit_kernel(Template tm, const double* __restrict__ med_fit
         sv[j] = sqrt(G[0][j] * G[0][j] + G[1][j] * G[1][j] + G[2][j] * G[2][j]);
         smax = fmax(smax, sv[j]);
     }
-    int weak = -1;
+    int weak = -1, strong = -1, nweak = 0;
     for (int j = 0; j < 3; ++j) {
         if (sv[j] > 1e-13 * smax) {
             for (int k = 0; k < 3; ++k) U[k][j] = G[k][j] / sv[j];
+            strong = j;
         } else {
             weak = j;
+            ++nweak;
         }
     }
-    if (weak >= 0) {  // coplanar fit joints: complete the frame (the reference's SVD is arbitrary here as well)
+    if (nweak == 1) {  // coplanar fit joints: complete the frame (the reference's SVD is arbitrary here as well)
         const int a = (weak + 1) % 3, b = (weak + 2) % 3;
         U[0][weak] = U[1][a] * U[2][b] - U[2][a] * U[1][b];
         U[1][weak] = U[2][a] * U[0][b] - U[0][a] * U[2][b];
         U[2][weak] = U[0][a] * U[1][b] - U[1][a] * U[0][b];
+    } else if (nweak == 2) {  // collinear fit joints: any unit vector orthogonal to the one strong column, then their cross product
+        const int a = (strong + 1) % 3, b = (strong + 2) % 3;
+        const double u0 = U[0][strong], u1 = U[1][strong], u2 = U[2][strong];
+        // u x e_k for the axis k that u is least aligned with: |u_k| <= 1/sqrt(3), so the product is at least sqrt(2/3) long
+        int k = 0;
+        if (fabs(u1) < fabs(u0)) k = 1;
+        if (fabs(u2) < fabs(k == 0 ? u0 : u1)) k = 2;
+        double w0 = k == 0 ? 0.0 : (k == 1 ? -u2 : u1);
+        double w1 = k == 0 ? u2 : (k == 1 ? 0.0 : -u0);
+        double w2 = k == 0 ? -u1 : (k == 1 ? u0 : 0.0);
+        const double wn = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+        w0 /= wn;
+        w1 /= wn;
+        w2 /= wn;
+        U[0][a] = w0;
+        U[1][a] = w1;
+        U[2][a] = w2;
+        U[0][b] = u1 * w2 - u2 * w1;
+        U[1][b] = u2 * w0 - u0 * w2;
+        U[2][b] = u0 * w1 - u1 * w0;
+    } else if (nweak == 3) {  // no direction at all (coincident or non-finite fit joints): rot = V
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) U[i][j] = i == j ? 1.0 : 0.0;
     }
     // rot = V U^T ; off = mu_t - mu_s @ rot
     double* o = xf + side * 12;
