@@ -100,6 +100,15 @@ PROTOTYPES = {
     "df3d_spectrogram_bank": (c_int, [c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_longlong, c_void_p]),
     "df3d_spectrogram": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_longlong, c_void_p, c_int,
                          c_void_p]),
+    "df3d_bmap_work_bytes": (c_longlong, [c_int]),
+    "df3d_bmap_prepare": (c_int, [c_void_p, c_longlong, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_bmap_logs": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
+    "df3d_bmap_divergence": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_void_p, c_void_p]),
+    "df3d_bmap_calibrate": (c_int, [c_void_p, c_longlong, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_bmap_joint": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "df3d_bmap_place": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
+    "df3d_bmap_cost": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_tsne_run": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_longlong, c_void_p]),
     "df3d_ba_eval": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_colsq": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_matvec": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

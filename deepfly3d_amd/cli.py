@@ -3,6 +3,7 @@ Video rendering flags are accepted and reported as unsupported (visualisation is
 import argparse
 import glob
 import logging
+import math
 import os
 import sys
 from collections import deque
@@ -75,7 +76,20 @@ def parse_cli_args(argv=None):
                         "of the frame rate (100 fps where the recording has no videos to read it from); together with --rigid-legs also "
                         "angle_spectrogram_rigid, the same of the fitted pose.  The angles themselves are stored only with --joint-angles.  "
                         "Works with --skip-pose-estimation on an earlier result")
+    p.add_argument("--behaviour-map", dest="behaviour_map", action="store_true",
+                   help="Embed every frame's joint-angle spectrogram (the one --angle-spectrogram computes, normalised per frame) in the plane "
+                        "by t-SNE under the Kullback-Leibler divergence and append the keys behaviour_map [T, 2] (float64; NaN for a frame "
+                        "without a spectrum), behaviour_map_train_index, behaviour_map_kl and behaviour_map_perplexity to the result; together "
+                        "with --rigid-legs also behaviour_map_rigid and behaviour_map_rigid_kl.  The spectrogram itself is stored only with "
+                        "--angle-spectrogram.  Works with --skip-pose-estimation on an earlier result")
+    p.add_argument("--behaviour-perplexity", dest="behaviour_perplexity", type=float, default=None, metavar="U",
+                   help="With --behaviour-map: the effective number of neighbours of a frame (default 32).  The recording needs at least "
+                        "3 U + 1 frames")
     args = p.parse_args(argv)
+    if args.behaviour_perplexity is not None and not args.behaviour_map:
+        p.error("--behaviour-perplexity sets the perplexity of --behaviour-map: it needs --behaviour-map")
+    if args.behaviour_perplexity is not None and not (math.isfinite(args.behaviour_perplexity) and args.behaviour_perplexity > 1.0):
+        p.error("--behaviour-perplexity must be finite and > 1")
     if args.auto_correct and args.skip_estimation:
         p.error("--auto-correct needs the heat-map peaks of this run's pose estimation: it cannot be combined with --skip-pose-estimation")
     if args.subpixel and args.skip_estimation:
@@ -118,8 +132,9 @@ def run(args):
     joint_angles = getattr(args, "joint_angles", False)
     rigid_legs = getattr(args, "rigid_legs", False)
     angle_spectrogram = getattr(args, "angle_spectrogram", False)
+    behaviour_map = getattr(args, "behaviour_map", False)
     if (args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not joint_angles and not rigid_legs
-            and not angle_spectrogram):
+            and not angle_spectrogram and not behaviour_map):
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0
     logger.info(f"\nWorking in {args.input_folder}")
@@ -128,10 +143,14 @@ def run(args):
     core = Core(args.input_folder, args.output_folder, args.num_images_max, args.order, dtype=args.dtype, device=getattr(args, "device", None))
     if video_heatmap and not core.has_heatmap:
         raise FileNotFoundError(_NO_IMAGES.format(folder=args.input_folder))
-    if (joint_angles or rigid_legs or angle_spectrogram) and args.skip_estimation and core.points2d is None:
-        flag = "--joint-angles" if joint_angles else "--rigid-legs" if rigid_legs else "--angle-spectrogram"
+    if (joint_angles or rigid_legs or angle_spectrogram or behaviour_map) and args.skip_estimation and core.points2d is None:
+        flag = "--joint-angles" if joint_angles else "--rigid-legs" if rigid_legs else "--angle-spectrogram" if angle_spectrogram else "--behaviour-map"
         raise RuntimeError(f"{flag} needs calibrated cameras to triangulate with, and with --skip-pose-estimation {args.output_folder} "
                            "holds no earlier result to reopen: run the pose estimation first")
+    if behaviour_map:   # a recording too short for the perplexity: refused before any work
+        from . import ops
+
+        ops.behaviour_map_points(core.num_images, getattr(args, "behaviour_perplexity", None))
     auto = getattr(args, "auto_correct", False)
     if not args.skip_estimation:
         from .config import PICTORIAL_DEFAULTS
@@ -147,7 +166,8 @@ def run(args):
             core.auto_correct(flagged_only=True)
         elif auto:
             core.auto_correct()
-        core.save(joint_angles=joint_angles, rigid_legs=rigid_legs, angle_spectrogram=angle_spectrogram)
+        core.save(joint_angles=joint_angles, rigid_legs=rigid_legs, angle_spectrogram=angle_spectrogram, behaviour_map=behaviour_map,
+                  behaviour_perplexity=getattr(args, "behaviour_perplexity", None))
     if args.video_2d or args.video_3d or video_heatmap:
         # f4 (reference cli.py:305-321): frames drawn on the GPU (csrc/render.hip), encoded by ffmpeg when present.  Rank 0 draws and
         # encodes; the peers wait for its outcome with a heartbeat (distributed.primary_section), so that an encoder failure moves

@@ -86,6 +86,21 @@ SPECTROGRAM_MAX_SUPPORT = 2048
 SPECTROGRAM_UNWRAPPED_ANGLES = ("thc_pitch", "thc_roll", "ctr_roll", "fti_roll")
 
 
+# ---- t-SNE behaviour maps of the angle spectrograms.  Every frame's spectrum is normalised to a distribution
+# with BEHAVIOUR_FLOOR added to every channel (a silent channel must not make a divergence infinite); at most BEHAVIOUR_MAX_POINTS
+# frames, spread evenly over the valid ones, are embedded by BEHAVIOUR_ITERATIONS steps of descent (the first
+# BEHAVIOUR_EXAGGERATION_ITERATIONS of them with P multiplied by 12) and the others are placed among them.  BEHAVIOUR_POINTS_CAP
+# is the most max_points may ask for: the dense N x N float64 tables are 2 GB each there.  BEHAVIOUR_PERPLEXITY is the effective
+# number of neighbours of a frame; its entropy is met to BEHAVIOUR_ENTROPY_TOL nats by a beta in (0, BEHAVIOUR_BETA_MAX].
+BEHAVIOUR_FLOOR = 1e-9
+BEHAVIOUR_MAX_POINTS = 8192
+BEHAVIOUR_POINTS_CAP = 16384
+BEHAVIOUR_PERPLEXITY = 32.0
+BEHAVIOUR_ENTROPY_TOL = 1e-10
+BEHAVIOUR_BETA_MAX = 1e12
+BEHAVIOUR_ITERATIONS = 1000
+BEHAVIOUR_EXAGGERATION_ITERATIONS = 250
+
 # ---- which camera sees which joint (reference df3d/skeleton_fly.py:202-250), by camera id: cameras 0-2 look at the side whose
 # joints are 0..18, cameras 4-6 at the side of joints 19..37, camera 3 faces the fly.  Pinned by tests/golden/skeleton_tables.npz.
 # Where df3d::relayout_source (csrc/geometry_dev.h) fills a joint of a side camera under the identity ordering, this table sees it;

@@ -400,13 +400,13 @@ class Core:
         S, freqs, _ = self._angle_spectrogram(rigid, body_frame, fps, unwrap, torch.float64, bank)
         return S, freqs
 
-    def _angle_spectrogram(self, rigid, body_frame, fps, unwrap, dtype, bank):
+    def _angle_spectrogram(self, rigid, body_frame, fps, unwrap, dtype, bank, on_device=False, what="angle_spectrogram"):
         from . import config
 
         bank = dict(bank)
         unknown = set(bank) - {"f_min", "f_max", "num", "freqs", "omega0", "radius"}
         if unknown:
-            raise TypeError(f"angle_spectrogram got unexpected bank arguments {sorted(unknown)}")
+            raise TypeError(f"{what} got unexpected bank arguments {sorted(unknown)}")
         if "freqs" in bank and {"f_min", "f_max", "num"} & set(bank):
             raise TypeError("give either freqs or f_min / f_max / num, not both")
         if fps is None:
@@ -416,7 +416,7 @@ class Core:
         fps = float(fps)
         freqs = bank["freqs"] if "freqs" in bank else ops.wavelet_frequencies(fps, bank.get("f_min"), bank.get("f_max"), bank.get("num"))
         freqs = np.ascontiguousarray(freqs, dtype=np.float64)
-        angles = self._joint_angles_on_device("angle_spectrogram", body_frame, rigid)[0]
+        angles = self._joint_angles_on_device(what, body_frame, rigid)[0]
         T = angles.shape[0]
         series = angles.reshape(T, 48)
         if unwrap:
@@ -427,7 +427,27 @@ class Core:
                 logger.warning("angle_spectrogram: not unwrapped, because they hold a non-finite sample: "
                                + ", ".join(f"{config.LEG_NAMES[c // 8]} {names[c % 8]}" for c in left))
         S = ops.wavelet_spectrogram(series.reshape(T, 6, 8), fps, freqs, bank.get("omega0"), bank.get("radius"), dtype=dtype)
-        return S.cpu().numpy(), freqs, fps
+        return S if on_device else S.cpu().numpy(), freqs, fps
+
+    # -- t-SNE behaviour map of the angle spectrograms ---------------------------------------------------------
+    def behaviour_map(self, rigid=False, perplexity=None, n_iter=None, max_points=None, seed=0, **spectrogram_kwargs):
+        """The behaviour map (ops.behaviour_map) of the float64 spectrogram angle_spectrogram(rigid, **spectrogram_kwargs) computes,
+        every frame's [6, 8, F] amplitudes flattened to one spectrum: an ops.BehaviourMapResult of numpy arrays -- embedding [T, 2]
+        (NaN for a frame whose spectrum holds a NaN), train_index [N], beta [T], info [T], kl and perplexity.  A recording too
+        short for the perplexity (3 perplexity <= frames - 1) is refused before anything is computed.  A rank-0 method with
+        angle_spectrogram's refusals."""
+        r = self._behaviour_map(rigid, perplexity, n_iter, max_points, seed, spectrogram_kwargs)
+        return ops.BehaviourMapResult(r.embedding.cpu().numpy(), r.train_index.cpu().numpy(), r.beta.cpu().numpy(), r.info.cpu().numpy(), r.kl,
+                                      r.perplexity)
+
+    def _behaviour_map(self, rigid, perplexity, n_iter, max_points, seed, kwargs):
+        kwargs = dict(kwargs)
+        body_frame, fps, unwrap = kwargs.pop("body_frame", "recording"), kwargs.pop("fps", None), kwargs.pop("unwrap", True)
+        frames = getattr(self, "num_images", None)
+        if frames is not None and self.camNet is not None and self.camNet.has_calibration():
+            ops.behaviour_map_points(frames, perplexity, max_points)   # before any work
+        S = self._angle_spectrogram(rigid, body_frame, fps, unwrap, torch.float64, kwargs, on_device=True, what="behaviour_map")[0]
+        return ops.behaviour_map(S, perplexity, n_iter, max_points, seed)
 
     # -- manual corrections (DESIGN.md section 11; reference df3d/core.py:253-296, 477-479, 509-544) ---------------------------------
     _MOVE_THRESHOLD = 30   # pixels, per coordinate: a pose that differs less from the estimate on every checked joint is not stored
@@ -587,13 +607,16 @@ class Core:
         dd.agree(bad, "the sharded triangulation")
         return None if full is None else full.cpu().numpy()
 
-    def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False):
+    def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False, behaviour_perplexity=None):
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
         keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras).
         `rigid_legs=True` appends, after those, "points3d_rigid", "rigid_segment_lengths" and "rigid_fit_cost" (Core.rigid_legs()) and,
         together with joint_angles, "joint_angles_rigid" (Core.joint_angles(rigid=True)[0]).  `angle_spectrogram=True` appends,
         after all of those, "angle_spectrogram" [T, 6, 8, F] float32 (Core.angle_spectrogram() with its defaults),
-        "spectrogram_freqs" [F], "spectrogram_fps" and, together with rigid_legs, "angle_spectrogram_rigid"."""
+        "spectrogram_freqs" [F], "spectrogram_fps" and, together with rigid_legs, "angle_spectrogram_rigid".  `behaviour_map=True`
+        appends, after all of those, "behaviour_map" [T, 2] float64 (Core.behaviour_map() with its defaults and
+        `behaviour_perplexity`), "behaviour_map_train_index", "behaviour_map_kl", "behaviour_map_perplexity" and, together with
+        rigid_legs, "behaviour_map_rigid" and "behaviour_map_rigid_kl"; the spectrogram itself is stored only with angle_spectrogram."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
@@ -602,12 +625,15 @@ class Core:
         error = None
         if self.is_primary:
             try:
-                self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram)
+                self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
-    def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False):
+    def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False,
+                      behaviour_perplexity=None):
+        if behaviour_map and getattr(self, "num_images", None) is not None:   # too short for the perplexity: refused before any work
+            ops.behaviour_map_points(self.num_images, behaviour_perplexity)
         result = {"points2d": np.copy(self.points2d)}
         if self.camNet is not None and self.camNet.has_calibration():
             if pts3d_sharded is not None:
@@ -637,6 +663,13 @@ class Core:
                 False, "recording", None, True, torch.float32, {})
             if rigid_legs:
                 result["angle_spectrogram_rigid"] = self._angle_spectrogram(True, "recording", None, True, torch.float32, {})[0]
+        if behaviour_map:
+            m = self.behaviour_map(perplexity=behaviour_perplexity)
+            result["behaviour_map"], result["behaviour_map_train_index"] = m.embedding, m.train_index
+            result["behaviour_map_kl"], result["behaviour_map_perplexity"] = m.kl, m.perplexity
+            if rigid_legs:
+                m = self.behaviour_map(rigid=True, perplexity=behaviour_perplexity)
+                result["behaviour_map_rigid"], result["behaviour_map_rigid_kl"] = m.embedding, m.kl
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")

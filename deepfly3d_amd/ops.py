@@ -3,6 +3,7 @@
 Inputs/outputs are torch CUDA tensors (device memory + stream plumbing only); every computation is a
 libdf3d_hip.so kernel.  No CPU fallback: a missing library or GPU raises `_native.NativeLibraryError`.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -608,6 +609,248 @@ def unwrap_phase(series, channels=None):
     up[1:] += torch.cumsum(corr, dim=0)
     out[:, idx] = torch.where(finite.unsqueeze(0), up, p)
     return out, [c for c, ok in zip(cols, finite.cpu().tolist()) if not ok]
+
+
+# ---- t-SNE behaviour maps of per-frame spectra ---------------------------------------------------------------
+BehaviourMapResult = collections.namedtuple("BehaviourMapResult", "embedding train_index beta info kl perplexity")
+
+
+def _bmap_call(name, *args):
+    """One a13 entry; its DF3D_EINVAL is the caller's mistake and becomes a ValueError with the library's message."""
+    lib = _native.load()
+    rc = getattr(lib, name)(*args)
+    if rc == _native.DF3D_EINVAL:
+        raise ValueError(lib.df3d_last_error().decode())
+    _native.check(rc, name)
+
+
+def _need_f64(t, dims, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() in dims):
+        raise ValueError(f"{name} must be a torch.float64 CUDA tensor of {' or '.join(str(d) for d in dims)} dimensions")
+    return t.contiguous()
+
+
+def behaviour_map_points(frames, perplexity=None, max_points=None):
+    """(N, perplexity): how many of `frames` valid frames a behaviour map embeds, N = min(frames, max_points), after the model's
+    refusals (ValueError): max_points outside [1, config.BEHAVIOUR_POINTS_CAP]; a perplexity that is not finite or <= 1; fewer
+    frames than 3 perplexity + 1 -- every training frame calibrates against the N - 1 others, and the rule is 3 perplexity <= N - 1."""
+    from . import config
+
+    u = float(config.BEHAVIOUR_PERPLEXITY if perplexity is None else perplexity)
+    cap = config.BEHAVIOUR_POINTS_CAP
+    max_points = int(config.BEHAVIOUR_MAX_POINTS if max_points is None else max_points)
+    if not 1 <= max_points <= cap:
+        raise ValueError(f"max_points must be in [1, {cap}] (it is {max_points}): the dense N x N float64 tables are 2 GB each at {cap}")
+    if not (np.isfinite(u) and u > 1.0):
+        raise ValueError(f"perplexity must be finite and > 1 (it is {u:g})")
+    N = min(int(frames), max_points)
+    need = int(np.ceil(3.0 * u)) + 1
+    if N < need:
+        what = f"this recording has {int(frames)} valid frames" if int(frames) <= max_points else f"max_points is {max_points}"
+        raise ValueError(f"perplexity {u:g} needs at least {need} frames to embed (3 perplexity <= frames - 1) and {what}: "
+                         f"the largest perplexity accepted for {N} frames is {max((N - 1) / 3.0, 0.0):.4g}")
+    return N, u
+
+
+def behaviour_train_rows(valid_count, N):
+    """[N] int64 (numpy): the positions floor(i valid_count / N), i = 0..N - 1, of the training frames in the list of valid frames."""
+    return (np.arange(N, dtype=np.int64) * int(valid_count)) // max(int(N), 1)
+
+
+def _distributions(S):
+    """(p [T, D], log p [T, D], e [T], valid [T] int32) of S [T, ...]: df3d_bmap_prepare."""
+    from . import config
+
+    if not (isinstance(S, torch.Tensor) and S.is_cuda and S.dtype == torch.float64 and S.dim() >= 1):
+        raise ValueError("S must be a torch.float64 CUDA tensor of shape [T, ...]")
+    T = S.shape[0]
+    D = int(np.prod(tuple(S.shape[1:]), dtype=np.int64))
+    if D < 1:
+        raise ValueError("S must hold at least one channel")
+    S2 = S.reshape(T, D).contiguous()
+    p, logp = torch.empty_like(S2), torch.empty_like(S2)
+    e = torch.empty((T,), dtype=torch.float64, device=S.device)
+    valid = torch.empty((T,), dtype=torch.int32, device=S.device)
+    _bmap_call("df3d_bmap_prepare", S2.data_ptr(), T, D, config.BEHAVIOUR_FLOOR, p.data_ptr(), logp.data_ptr(), e.data_ptr(), valid.data_ptr(),
+               _stream(S))
+    return p, logp, e, valid
+
+
+@_on_tensor_device
+def spectrogram_distributions(S):
+    """(p [T, D] float64, valid [T] bool): every frame's spectrum S[t] (non-negative amplitudes; [T, ...], the trailing axes
+    flattened to D) as a distribution over its channels, p = (S / sum S + floor) / (1 + D floor) with floor =
+    config.BEHAVIOUR_FLOOR.  A row with a negative or non-finite entry or a zero sum is not valid; its p is NaN."""
+    p, _, _, valid = _distributions(S)
+    return p, valid != 0
+
+
+def _divergence(pa, ea, lb):
+    M, D = pa.shape
+    N = lb.shape[0]
+    K = torch.empty((M, N), dtype=torch.float64, device=pa.device)
+    step = 65535 * 128   # the most rows one call takes
+    for m0 in range(0, M, step):
+        m1 = min(M, m0 + step)
+        _bmap_call("df3d_bmap_divergence", pa[m0:m1].data_ptr(), ea[m0:m1].data_ptr(), m1 - m0, lb.data_ptr(), N, D, K[m0:m1].data_ptr(), _stream(pa))
+    return K
+
+
+def _logs(p):
+    logp = torch.empty_like(p)
+    e = torch.empty((p.shape[0],), dtype=torch.float64, device=p.device)
+    _bmap_call("df3d_bmap_logs", p.data_ptr(), p.shape[0], p.shape[1], logp.data_ptr(), e.data_ptr(), _stream(p))
+    return logp, e
+
+
+@_on_tensor_device
+def kl_divergence(pa, pb):
+    """K [M, N] float64: K[i, j] = max(0, sum_d pa[i, d] (log pa[i, d] - log pb[j, d])), the Kullback-Leibler divergence of row i
+    of pa [M, D] from row j of pb [N, D] (distributions with positive entries, as spectrogram_distributions gives them).  The
+    matrix is not symmetric."""
+    pa, pb = _need_f64(pa, (2,), "pa"), _need_f64(pb, (2,), "pb")
+    if pa.shape[1] != pb.shape[1] or pa.shape[1] < 1 or pa.device != pb.device:
+        raise ValueError("pa [M, D] and pb [N, D] must share D >= 1 and the device")
+    return _divergence(pa, _logs(pa)[1], _logs(pb)[0])
+
+
+@_on_tensor_device
+def perplexity_calibrate(K, perplexity=None, exclude=None):
+    """(cond [M, N], beta [M], info [M] int32) of a divergence table K [M, N]: cond[i] = softmax_j(-beta_i K[i, j]) with beta_i chosen
+    so that the row's entropy is log(perplexity) to config.BEHAVIOUR_ENTROPY_TOL nats.  `exclude`: None (every column takes
+    part), "self" (column i of row i is left out and gets 0; K must be square) or an int32 tensor [M] of the column each row
+    leaves out (-1: none).  A row in which at least `perplexity` entries tie at the minimum cannot reach the target: it gets
+    beta = config.BEHAVIOUR_BETA_MAX and bit 0 of its info.  ValueError: a perplexity that is not finite, <= 1 or above a third
+    of the admitted columns."""
+    from . import config
+
+    K = _need_f64(K, (2,), "K")
+    M, N = K.shape
+    u = float(config.BEHAVIOUR_PERPLEXITY if perplexity is None else perplexity)
+    if isinstance(exclude, str):
+        if exclude != "self" or M != N:
+            raise ValueError('exclude must be None, "self" (K square) or an int32 tensor [M]')
+        exclude = torch.arange(M, dtype=torch.int32, device=K.device)
+    elif exclude is not None:
+        if not (isinstance(exclude, torch.Tensor) and exclude.dtype == torch.int32 and exclude.shape == (M,) and exclude.device == K.device):
+            raise ValueError('exclude must be None, "self" (K square) or an int32 tensor [M] on the device of K')
+        exclude = exclude.contiguous()
+    cond = torch.empty_like(K)
+    beta = torch.empty((M,), dtype=torch.float64, device=K.device)
+    info = torch.empty((M,), dtype=torch.int32, device=K.device)
+    _bmap_call("df3d_bmap_calibrate", K.data_ptr(), M, N, u, config.BEHAVIOUR_ENTROPY_TOL, config.BEHAVIOUR_BETA_MAX,
+               None if exclude is None else exclude.data_ptr(), cond.data_ptr(), beta.data_ptr(), info.data_ptr(), _stream(K))
+    return cond, beta, info
+
+
+@_on_tensor_device
+def joint_probabilities(cond):
+    """P [N, N] = (cond + cond^T) / (2N) with a zero diagonal: the joint table of the training set."""
+    cond = _need_f64(cond, (2,), "cond")
+    if cond.shape[0] != cond.shape[1]:
+        raise ValueError("cond must be square")
+    P = torch.empty_like(cond)
+    _bmap_call("df3d_bmap_joint", cond.data_ptr(), cond.shape[0], P.data_ptr(), _stream(cond))
+    return P
+
+
+def _tsne_work(N, device):
+    need = _native.load().df3d_bmap_work_bytes(N)
+    if need <= 0:
+        from . import config
+
+        raise ValueError(f"N must be in [1, {config.BEHAVIOUR_POINTS_CAP}] (it is {N})")
+    return torch.empty((need,), dtype=torch.uint8, device=device), need
+
+
+@_on_tensor_device
+def tsne(P, init, n_iter=None, first_iter=0, state=None):
+    """(Y, V, G), each [N, 2]: iterations first_iter .. first_iter + n_iter - 1 (default config.BEHAVIOUR_ITERATIONS) of the
+    model's descent on the joint table P [N, N] from the positions `init` [N, 2] and `state` = (V, G) (default: V = 0, G = 1, the
+    start).  The step size is max(N / 48, 50); the exaggeration and the momentum follow the absolute iteration index, so a run may
+    be split anywhere and resumed from what it returned.  Nothing is read back."""
+    from . import config
+
+    P, Y = _need_f64(P, (2,), "P"), _need_f64(init, (2,), "init").clone()
+    N = P.shape[0]
+    if P.shape != (N, N) or Y.shape != (N, 2) or Y.device != P.device:
+        raise ValueError("P must be [N, N] and init [N, 2] on its device")
+    n_iter = config.BEHAVIOUR_ITERATIONS if n_iter is None else int(n_iter)
+    if state is None:
+        V, G = torch.zeros_like(Y), torch.ones_like(Y)
+    else:
+        V, G = (_need_f64(t, (2,), "state").clone() for t in state)
+        if V.shape != Y.shape or G.shape != Y.shape:
+            raise ValueError("state must be (V [N, 2], G [N, 2])")
+    if N == 0:
+        return Y, V, G
+    work, need = _tsne_work(N, P.device)
+    _bmap_call("df3d_tsne_run", P.data_ptr(), N, Y.data_ptr(), V.data_ptr(), G.data_ptr(), int(first_iter), n_iter, max(N / 48.0, 50.0),
+               work.data_ptr(), need, _stream(P))
+    return Y, V, G
+
+
+@_on_tensor_device
+def tsne_cost(P, Y):
+    """The Kullback-Leibler cost sum_{P_ij > 0} P_ij log(P_ij Z / w_ij) of the positions Y [N, 2] under the joint table P [N, N]:
+    a float64 tensor of one element on the device (nothing is read back)."""
+    P, Y = _need_f64(P, (2,), "P"), _need_f64(Y, (2,), "Y")
+    N = P.shape[0]
+    if P.shape != (N, N) or Y.shape != (N, 2) or Y.device != P.device:
+        raise ValueError("P must be [N, N] and Y [N, 2] on its device")
+    work, need = _tsne_work(N, P.device)
+    cost = torch.empty((1,), dtype=torch.float64, device=P.device)
+    _bmap_call("df3d_bmap_cost", P.data_ptr(), N, Y.data_ptr(), cost.data_ptr(), work.data_ptr(), need, _stream(P))
+    return cost[0]
+
+
+_PLACE_CHUNK_BYTES = 1 << 28   # the most bytes of one row chunk's divergence table during placement
+
+
+@_on_tensor_device
+def behaviour_map(S, perplexity=None, n_iter=None, max_points=None, seed=0):
+    """The t-SNE behaviour map of per-frame spectra S [T, ...] (float64 cuda, non-negative), a
+    BehaviourMapResult: `embedding` [T, 2] (NaN for a frame that is not valid), `train_index` [N] int64 (the frames that were
+    embedded by descent, N = min(valid frames, max_points), spread evenly over the valid ones; every other valid frame is placed
+    at the mean of the training positions under its own calibrated conditional), `beta` [T] and `info` [T] int32 (the
+    calibration's, NaN / 0 for an invalid frame; bit 0: the perplexity could not be met, the frame's neighbours tie), `kl` (the
+    final cost, a float, the one value read back) and `perplexity`.  Defaults: config.BEHAVIOUR_PERPLEXITY, _ITERATIONS,
+    _MAX_POINTS; the start is 1e-4 times standard normals of a CPU torch.Generator seeded with `seed`."""
+    if not (isinstance(S, torch.Tensor) and S.dim() >= 1):
+        raise ValueError("S must be a torch.float64 CUDA tensor of shape [T, ...]")
+    T, dev = S.shape[0], S.device
+    behaviour_map_points(T, perplexity, max_points)   # too few frames whatever their validity: refused before any work
+    p, logp, e, valid = _distributions(S)
+    vidx = torch.nonzero(valid).flatten()
+    Tv = int(vidx.numel())
+    N, u = behaviour_map_points(Tv, perplexity, max_points)
+    rows = torch.from_numpy(behaviour_train_rows(Tv, N)).to(dev)
+    train = vidx[rows]
+    pt, lt, et = p[train], logp[train], e[train]
+    cond, beta_t, info_t = perplexity_calibrate(_divergence(pt, et, lt), u, "self")
+    P = joint_probabilities(cond)
+    del cond
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(int(seed))
+    Y0 = (1e-4 * torch.randn((N, 2), generator=gen, dtype=torch.float64)).to(dev)
+    Y = tsne(P, Y0, n_iter)[0]
+    kl = tsne_cost(P, Y)
+    del P
+    embedding = torch.full((T, 2), float("nan"), dtype=torch.float64, device=dev)
+    beta = torch.full((T,), float("nan"), dtype=torch.float64, device=dev)
+    info = torch.zeros((T,), dtype=torch.int32, device=dev)
+    embedding[train], beta[train], info[train] = Y, beta_t, info_t
+    placed = torch.ones((Tv,), dtype=torch.bool, device=dev)
+    placed[rows] = False
+    rest = vidx[placed]
+    chunk = max(1, _PLACE_CHUNK_BYTES // (8 * N))
+    for r0 in range(0, int(rest.numel()), chunk):   # row chunks: no [T, N] table ever exists
+        sel = rest[r0 : r0 + chunk]
+        c, b, i = perplexity_calibrate(_divergence(p[sel], e[sel], lt), u)
+        out = torch.empty((sel.numel(), 2), dtype=torch.float64, device=dev)
+        _bmap_call("df3d_bmap_place", c.data_ptr(), sel.numel(), N, Y.data_ptr(), out.data_ptr(), _stream(S))
+        embedding[sel], beta[sel], info[sel] = out, b, i
+    return BehaviourMapResult(embedding, train, beta, info, float(kl.item()), u)
 
 
 def gaussian_window_taps(window_size, sigma, truncate=4.0):

@@ -331,6 +331,49 @@ int df3d_spectrogram(const double* x_dev, long long T, int C, const double* freq
                      double radius, const void* work_dev, long long work_len_bytes, void* out_dev, int out_f32, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a13 t-SNE behaviour map of per-frame spectra (the model is this project's own specification, defined
+ *     in float64 by tests/behaviour_map_oracle.py).  All arrays are DEVICE float64 / int32, row-major; every stage is its own
+ *     entry.  No floating-point atomics and fixed-order sums: two calls on the same input give the same bits.
+ * df3d_bmap_prepare: S [T, D] -> p, logp [T, D], e [T], valid [T].  A row is valid when every entry is finite and >= 0 and its sum
+ *     a is finite and > 0; then p = (S / a + floor) / (1 + D floor), logp = log p, e = sum_d p logp, valid = 1.  Otherwise p, logp
+ *     and e are NaN and valid = 0.  df3d_bmap_logs: logp and e of distributions that exist already (positive entries).
+ * df3d_bmap_divergence: K [M, N] = max(0, ea_i - sum_d pa[i, d] lb[j, d]), the Kullback-Leibler divergence of row i of one set
+ *     (pa [M, D], ea [M]) from row j of another (lb [N, D], its LOGARITHMS).  At most 65 535 * 128 rows per call.
+ * df3d_bmap_calibrate: per row of K [M, N], the conditional c[i, j] = exp(-beta_i (K[i, j] - m_i)) / sum_{j' != x_i} exp(...) with
+ *     m_i the smallest admitted entry, c[i, x_i] = 0, x_i = exclude[i] (exclude NULL, or an entry of -1: no column excluded), and
+ *     beta_i the root of H_i(beta) = -sum c log c = log(perplexity), accepted when |H_i - log perplexity| <= tol.  Where no beta in
+ *     (0, beta_max] reaches the target (at least `perplexity` admitted entries tie at the minimum) beta_i = beta_max and bit 0 of
+ *     info[i] is set; bit 1 reports a search that ran out of steps.  N <= 16 384 (the row stays in LDS).
+ * df3d_bmap_joint: P [N, N] = (c + c^T) / (2N), zero diagonal.  df3d_bmap_place: out [M, 2] = c [M, N] Y [N, 2].
+ * df3d_tsne_run: iterations first_iter .. first_iter + num_iters - 1 of the descent on Y, V, G [N, 2] (in place): alpha = 12,
+ *     mu = 0.5 for an iteration index below 250, alpha = 1, mu = 0.8 from there; w_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} w_ij,
+ *     g_i = 4 sum_j (alpha P_ij - w_ij / Z) w_ij (y_i - y_j); per component G += 0.2 where g V < 0, else G *= 0.8, G = max(G, 0.01);
+ *     V = mu V - lr G g; Y += V.  Two launches per iteration, no read-back: [0, k) followed by [k, n) gives the bits of [0, n).
+ * df3d_bmap_cost: cost[0] = sum_{P_ij > 0} P_ij log(P_ij Z / w_ij).  df3d_bmap_work_bytes(N): the bytes of the caller-owned
+ *     workspace of df3d_tsne_run and df3d_bmap_cost (0 where N is outside [1, 16 384]).
+ * DF3D_EINVAL before the device is touched, with a message that names the argument: a negative count, D < 1, N outside its
+ *     range, a null, misaligned (8 bytes; 16 for Y, out and work; 4 for int32) or overlapping buffer, a floor, tol, beta_max or lr
+ *     that is not finite and positive (floor may be 0), a perplexity that is not finite or <= 1 or above n / 3 with n the number
+ *     of admitted entries (the message gives the smallest frame count and the largest perplexity accepted), a workspace below
+ *     the query, a block count that overflows.  An empty problem (T = 0, M = 0, num_iters = 0) launches nothing and returns
+ *     DF3D_OK.  Every launching entry is asynchronous on `stream`, allocates nothing and keeps no host pointer.
+ * ---------------------------------------------------------------------------------------------- */
+long long df3d_bmap_work_bytes(int N);
+int df3d_bmap_prepare(const double* S_dev, long long T, int D, double floor_, double* p_dev, double* logp_dev, double* e_dev,
+                      int* valid_dev, void* stream);
+int df3d_bmap_logs(const double* p_dev, long long T, int D, double* logp_dev, double* e_dev, void* stream);
+int df3d_bmap_divergence(const double* pa_dev, const double* ea_dev, long long M, const double* lb_dev, long long N, int D,
+                         double* K_dev, void* stream);
+int df3d_bmap_calibrate(const double* K_dev, long long M, int N, double perplexity, double tol, double beta_max, const int* exclude_dev,
+                        double* cond_dev, double* beta_dev, int* info_dev, void* stream);
+int df3d_bmap_joint(const double* cond_dev, int N, double* P_dev, void* stream);
+int df3d_bmap_place(const double* cond_dev, long long M, int N, const double* Y_dev, double* out_dev, void* stream);
+int df3d_bmap_cost(const double* P_dev, int N, const double* Y_dev, double* cost_dev, void* work_dev, long long work_len_bytes,
+                   void* stream);
+int df3d_tsne_run(const double* P_dev, int N, double* Y_dev, double* V_dev, double* G_dev, int first_iter, int num_iters, double lr,
+                  void* work_dev, long long work_len_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
