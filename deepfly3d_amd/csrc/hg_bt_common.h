@@ -94,19 +94,27 @@ __device__ __forceinline__ void bt_t1_issue_persistent(const void* t1in, const v
     const unsigned char* const tin = reinterpret_cast<const unsigned char*>(t1in) + (size_t)view * H * W * ROWB;
     const unsigned char* const zer = reinterpret_cast<const unsigned char*>(zeros);
     const int q = lane_ >> 4, slot = lane_ & 15;
+    // the lane's halo pixel (hy, hx): divided by HW once, for the wave's first piece; from piece to piece it advances by 16 halo pixels, which
+    // wraps at most once (HW >= 16).  Both halves of a piece share address and bounds test: the second is 256 bytes on (inside the image)
+    static_assert(HW >= 16, "one wrap per step of 16 halo pixels");
+    const int hp0 = 4 * wave_ + q;
+    int hy = hp0 / HW, hx = hp0 - hy * HW;
 #pragma unroll
     for (int k = 0; k < (HALO / 4 + 3) / 4; ++k) {
         const int pc = wave_ + 4 * k;
         if (pc < HALO / 4) {
-            const int hp = 4 * pc + q;
-            const int hy = hp / HW, hx = hp - hy * HW;
             const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
             const bool ok = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
             const unsigned c16 = (unsigned)((slot ^ (hx & 15)) << 4);
             const unsigned in_view = (unsigned)((y * W + x) * ROWB) + c16;
-            const unsigned char* const base = ok ? tin : zer;
-            br_glds_piece64(base + (ok ? in_view : c16), t1_addr + (unsigned)(pc * 1024));
-            if constexpr (NH == 2) br_glds_piece64(base + (ok ? in_view + 256u : c16), t1_addr + (unsigned)(HALO * 256 + pc * 1024));
+            const unsigned char* const src = (ok ? tin : zer) + (ok ? in_view : c16);
+            br_glds_piece64(src, t1_addr + (unsigned)(pc * 1024));
+            if constexpr (NH == 2) br_glds_piece64(src + (ok ? 256u : 0u), t1_addr + (unsigned)(HALO * 256 + pc * 1024));
+        }
+        hx += 16;
+        if (hx >= HW) {
+            hx -= HW;
+            ++hy;
         }
     }
 }

@@ -22,7 +22,12 @@
 //     requested WN_UBUF - 1 passes = 1 024 MFMA cycles ahead);  ONE barrier per chunk (3 072 MFMA cycles);
 //   * t2 = relu(Y + b2) (b2 is the start value of position (1,1), whose column of both A^T is all ones) crosses to the pixel-major mapping
 //     of phase 3 through LDS (64 KB in the dead t1 region), and phase 3 is hg_bt_ring_f32.h's, unchanged: W3 through the 4-slot LDS-DMA ring
-//     (which takes the dead V buffers' place), residual add, ADD2 / UP / pooled outputs.
+//     (which takes the dead V buffers' place), residual add, ADD2 / UP / pooled outputs;
+//   * in phase 2 every address a chunk needs is complete in ONE register when the chunk's clump ends (round 8, profiles/r08_tail_gaps.txt;
+//     scripts/mfma_gaps.py counts what stands between the MFMAs of the built code): the patch columns, with their rows as immediate offsets of
+//     the reads, and the store and read bases of V buffer 2, which lies past the 16-bit offset of an LDS access (wn_far_off).  Phase 3's
+//     fragment reads are left to hipcc: read one quad ahead through two explicit register sets they measured 0.4-0.8 % SLOWER per launch
+//     (the read's latency already hides under the MFMAs in flight; see the record).
 //
 // U stream: 96 passes x 16 KB.  Passes 0 .. 63 (1 MiB) sit in the block's Winograd slot (p.w2d, in front of W3), passes 64 .. 95 (512 KiB) in the
 // block's direct-form stage images (p.wstream, BRF_NSTAGE / L2F_NSTAGE x 8 KB = 832 KB): no launch of an engine with `wino` reads those images
@@ -149,6 +154,13 @@ template <int N>
 __device__ __forceinline__ void wn_uwait(f32x4 (&u)[4]) {
     asm volatile("s_waitcnt vmcnt(%4)" : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]) : "n"(N) : "memory");
 }
+// An LDS region past the 16-bit immediate offset of an access (V buffer 2): address = lane constant + region offset, the offset as a
+// wave-uniform value the compiler cannot fold -- ONE v_add per base, where the source forms it (an s_mov is free beside the MFMAs); folded,
+// hipcc forms the address with a literal v_add where it wants it, between two MFMAs
+__device__ __forceinline__ unsigned wn_far_off(unsigned off) {
+    asm volatile("" : "+s"(off));
+    return off;
+}
 // one 16-byte load, scalar base + lane offset, issued where it stands (the residual tiles: hipcc sinks compiler-visible loads to their first use --
 // the epilogue -- and the wave then sits out an HBM round trip with nothing else to do; measured 4.7 % of the kernel)
 __device__ __forceinline__ void wn_xload1(f32x4& d, const void* sbase, unsigned voff) {
@@ -240,6 +252,10 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
     // three V buffers (chunk c is read from buffer c % 3 while chunk c + 2 is built into (c + 2) % 3: a chunk's first fragments can then be
     // requested before the barrier that ends the chunk in front of it): 0, 1 where the W3 ring's slots 0 .. 3 will be, 2 where its slots 4 .. 7 will be
     auto vbuf_off = [](int b) { return b == 0 ? 0 : b == 1 ? BR_RING_BYTES / 2 : WN_RING2_OFF; };
+    // Buffer 2 sits past the 16-bit offset of an LDS access from the lane constants (wn_far_off): its store base (vwr2) and fragment read base
+    // (vrd2) are formed in the clump of the chunk that needs them first -- not by a v_add where hipcc wants the address, between two MFMAs
+    unsigned vrd2 = 0, vwr2 = 0;
+    auto vrd_of = [&](int b) { return b == 2 ? smem + vrd2 : smem + vbuf_off(b) + vrd; };
     // the F(2, 3) step of the two rows a lane builds, per column: (t0 - t2, t1 + t2) for h = 0 (rows 0, 1 of B2^T d), (t0 - t2, t1 - t0) for
     // h = 1 (rows 3, 2) -- one form, two packed FMAs with wave-uniform coefficients.  The zero coefficients add 0 * t exactly for every finite
     // t; only a non-finite t1 value would become NaN here instead of staying infinite, and no Winograd form carries an infinity through anyway:
@@ -248,9 +264,14 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
     const f32x2 cw2 = {-1.0f, wh ? 0.0f : 1.0f}, cw0 = {0.0f, wh ? -1.0f : 0.0f};
     float tR[6][3];   // the patch values of the lane's (patch, channel, row half): [column][row]
     unsigned ta[6];   // LDS addresses of the next patch reads (computed in the VALU clump of the chunk before)
+    // (the empty asm: the address is complete in ONE register where it is formed -- in the clump -- and rows t = 1, 2 are immediate offsets of
+    // the reads; left open, hipcc folds the row offset into the scalar term and forms every row's address with a v_add between two MFMAs)
     auto t_addr = [&](int c) {   // chunk c's patch columns
 #pragma unroll
-        for (int col = 0; col < 6; ++col) ta[col] = (rd[col] ^ (unsigned)((c & 7) << 5)) + (t1_addr + (unsigned)((c >> 3) * BR_T1_BYTES));
+        for (int col = 0; col < 6; ++col) {
+            ta[col] = (rd[col] ^ (unsigned)((c & 7) << 5)) + (t1_addr + (unsigned)((c >> 3) * BR_T1_BYTES));
+            asm volatile("" : "+v"(ta[col]));
+        }
     };
     auto t_read = [&](int col) {   // column col of the lane's three rows
         typedef const __attribute__((address_space(3))) float* lds_f;
@@ -297,7 +318,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
             asm volatile("" ::"v"(vo[jp]));
             return;
         }
-        *reinterpret_cast<f32x4*>(smem + vbuf_off(buf) + vwr + jp * 1024) = vo[jp];
+        *reinterpret_cast<f32x4*>((buf == 2 ? smem + vwr2 : smem + vbuf_off(buf) + vwr) + jp * 1024) = vo[jp];
     };
     auto t_transform_write = [&](int buf, int c_next_addr) {   // (tile entry: clump, then the stores)
         t_transform(c_next_addr);
@@ -375,8 +396,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
             constexpr bool FIRST = decltype(first_tag)::value;
             const int cn = c + 1 < WN_CHUNKS ? c + 1 : c;   // (the last chunks re-request fragments / rebuild buffers nobody reads any more: one code path)
             const int c3 = c + 3 < WN_CHUNKS ? c + 3 : WN_CHUNKS - 1;
-            const unsigned char* const vb_ = smem + vbuf_off(BR) + vrd;
-            const unsigned char* const vn_ = smem + vbuf_off((BR + 1) % 3) + vrd;
+            const unsigned char* const vb_ = vrd_of(BR);   // (BR == 2: vrd2, formed in the clump of the chunk before)
             if (FIRST) {
 #pragma unroll
                 for (int g = 0; g < 2; ++g) vf[0][g] = *reinterpret_cast<const f32x4*>(vb_ + g * 1024);
@@ -392,9 +412,19 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
                     else uload(cn, eu - WN_PASSES, ufr[eu % WN_UBUF]);
                     __builtin_amdgcn_sched_barrier(0);   // (... issued HERE: the scheduler would sink the statement behind the pass's MFMAs)
                 }
-                if (e == 3 && !(WN_ABL & 2)) {
-                    if (WN_ABL & 4096) t_transform_write((BR + 2) % 3, c3);   // (development: the stores right behind the clump)
-                    else t_transform(c3);   // V(c + 2) from the patch read in passes 0, 1; addresses for the reads of chunk c + 1's passes 0, 1
+                if (e == 3) {   // the chunk's one clump
+                    if (BR == 0) {   // this chunk's stores go to buffer 2
+                        vwr2 = vwr + wn_far_off(WN_RING2_OFF);
+                        asm volatile("" : "+v"(vwr2));
+                    }
+                    if (BR == 1) {   // the next chunk reads buffer 2 (its first fragments in this chunk's last pass)
+                        vrd2 = vrd + wn_far_off(WN_RING2_OFF);
+                        asm volatile("" : "+v"(vrd2));
+                    }
+                    if (!(WN_ABL & 2)) {
+                        if (WN_ABL & 4096) t_transform_write((BR + 2) % 3, c3);   // (development: the stores right behind the clump)
+                        else t_transform(c3);   // V(c + 2) from the patch read in passes 0, 1; addresses for the reads of chunk c + 1's passes 0, 1
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll
@@ -404,7 +434,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
                     if (g < 2) {
                         const int en = e + 1, sn = en / 3, ppn = en % 3;
                         if (e < WN_PASSES - 1) vf[en & 1][g] = *reinterpret_cast<const f32x4*>(vb_ + (sn * 6 + 2 * ppn + g) * 1024);
-                        else vf[0][g] = *reinterpret_cast<const f32x4*>(vn_ + g * 1024);
+                        else vf[0][g] = *reinterpret_cast<const f32x4*>(vrd_of((BR + 1) % 3) + g * 1024);
                     }
                     if (e < 2 && g < 3 && !(WN_ABL & 2)) t_read(3 * e + g);
                     if (e == 3 && g < 3 && !(WN_ABL & (2 | 4096))) v_store((BR + 2) % 3, g);
