@@ -9,8 +9,8 @@ from ctypes import POINTER, Structure, c_char, c_char_p, c_double, c_float, c_in
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DF3D_LIB") or os.path.join(_HERE, "libdf3d_hip.so")  # DF3D_LIB: developer override (kernel A/B builds)
 
-ABI_VERSION = 610
-LSMR_AUTO, LSMR_BARRIERS, LSMR_LAUNCHES, LSMR_LOCAL, LSMR_ELEVEN = 0, 1, 2, 3, 11   # DF3D_LSMR_* of include/df3d_hip.h  # DF3D_ABI_VERSION of include/df3d_hip.h: the revision these prototypes were written against
+ABI_VERSION = 610  # DF3D_ABI_VERSION of include/df3d_hip.h: the revision these prototypes were written against
+LSMR_AUTO, LSMR_BARRIERS, LSMR_LAUNCHES, LSMR_LOCAL, LSMR_ELEVEN = 0, 1, 2, 3, 11   # DF3D_LSMR_* of include/df3d_hip.h
 DF3D_EINVAL = -1  # include/df3d_hip.h
 DF3D_ENOSPC = -5
 DF3D_EIO = -6

@@ -129,12 +129,11 @@ _NO_IMAGES = ("--video-heatmap draws the heat-maps the network computes from the
 
 def run(args):
     video_heatmap = getattr(args, "video_heatmap", False)
-    joint_angles = getattr(args, "joint_angles", False)
-    rigid_legs = getattr(args, "rigid_legs", False)
-    angle_spectrogram = getattr(args, "angle_spectrogram", False)
-    behaviour_map = getattr(args, "behaviour_map", False)
-    if (args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not joint_angles and not rigid_legs
-            and not angle_spectrogram and not behaviour_map):
+    # what the second save appends to the result: the four kinematics flags, in the order of their keys, and the map's perplexity
+    extras = {name: getattr(args, name, False) for name in ("joint_angles", "rigid_legs", "angle_spectrogram", "behaviour_map")}
+    flagged = [name for name, on in extras.items() if on]
+    extras["behaviour_perplexity"] = getattr(args, "behaviour_perplexity", None)
+    if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not flagged:
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0
     logger.info(f"\nWorking in {args.input_folder}")
@@ -143,14 +142,13 @@ def run(args):
     core = Core(args.input_folder, args.output_folder, args.num_images_max, args.order, dtype=args.dtype, device=getattr(args, "device", None))
     if video_heatmap and not core.has_heatmap:
         raise FileNotFoundError(_NO_IMAGES.format(folder=args.input_folder))
-    if (joint_angles or rigid_legs or angle_spectrogram or behaviour_map) and args.skip_estimation and core.points2d is None:
-        flag = "--joint-angles" if joint_angles else "--rigid-legs" if rigid_legs else "--angle-spectrogram" if angle_spectrogram else "--behaviour-map"
-        raise RuntimeError(f"{flag} needs calibrated cameras to triangulate with, and with --skip-pose-estimation {args.output_folder} "
-                           "holds no earlier result to reopen: run the pose estimation first")
-    if behaviour_map:   # a recording too short for the perplexity: refused before any work
+    if flagged and args.skip_estimation and core.points2d is None:
+        raise RuntimeError(f"--{flagged[0].replace('_', '-')} needs calibrated cameras to triangulate with, and with --skip-pose-estimation "
+                           f"{args.output_folder} holds no earlier result to reopen: run the pose estimation first")
+    if extras["behaviour_map"]:   # a recording too short for the perplexity: refused before any work
         from . import ops
 
-        ops.behaviour_map_points(core.num_images, getattr(args, "behaviour_perplexity", None))
+        ops.behaviour_map_points(core.num_images, extras["behaviour_perplexity"])
     auto = getattr(args, "auto_correct", False)
     if not args.skip_estimation:
         from .config import PICTORIAL_DEFAULTS
@@ -166,8 +164,7 @@ def run(args):
             core.auto_correct(flagged_only=True)
         elif auto:
             core.auto_correct()
-        core.save(joint_angles=joint_angles, rigid_legs=rigid_legs, angle_spectrogram=angle_spectrogram, behaviour_map=behaviour_map,
-                  behaviour_perplexity=getattr(args, "behaviour_perplexity", None))
+        core.save(**extras)
     if args.video_2d or args.video_3d or video_heatmap:
         # f4 (reference cli.py:305-321): frames drawn on the GPU (csrc/render.hip), encoded by ffmpeg when present.  Rank 0 draws and
         # encodes; the peers wait for its outcome with a heartbeat (distributed.primary_section), so that an encoder failure moves

@@ -23,9 +23,10 @@ import torch
 
 from . import _native, logger, ops
 from .camera_network import CameraNetwork
-from .config import IGNORE_JOINT_ID, camera_is_flipped, camera_see_joint, config, heatmap_planes, load_calibration, plane_color
+from .config import IGNORE_JOINT_ID, SPECTROGRAM_FPS, camera_is_flipped, camera_see_joint, config, heatmap_planes, load_calibration, plane_color
 from .db import PoseDB
 from .inference import inference_folder
+from .kinematics import PoseChain
 from .os_util import camera_videos, extract_frames, get_max_img_id, image_path_for, parse_frame_rate, parse_vid_name, probe_frame_rate
 from .procrustes import procrustes_separate, video_pose
 
@@ -343,9 +344,10 @@ class Core:
         """The previous image before `img_id` with a flagged joint, or None (reference df3d/core.py:217-227)."""
         return self.next_error_in_range(range(img_id - 1, -1, -1))
 
-    # -- leg joint angles (DESIGN.md section 14) --------------------------------------------------------------------------------------
-    def _measured_pose(self, what):
-        """camNet.points3d on the device (triangulating first when there is none), with the refusals of the rank-0 pose queries."""
+    # -- the kinematic chain (DESIGN.md sections 14-17): one kinematics.PoseChain per call, never kept ----------------------------------
+    def _measured_pose(self, what, fps=None):
+        """The PoseChain of camNet.points3d on the device (triangulating first when there is none), with the refusals of the rank-0
+        pose queries."""
         from . import distributed as dd
 
         if dd.current()[0] != 0:
@@ -356,7 +358,7 @@ class Core:
             self.camNet.triangulate()
         _native.require_gpu()
         dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
-        return torch.from_numpy(np.ascontiguousarray(self.camNet.points3d, dtype=np.float64)).to(dev)
+        return PoseChain(torch.from_numpy(np.ascontiguousarray(self.camNet.points3d, dtype=np.float64)).to(dev), fps)
 
     def joint_angles(self, body_frame="recording", rigid=False):
         """(angles [T, 6, 8] radians, lengths [T, 6, 4]) as numpy arrays: the eight joint angles (config.LEG_ANGLE_NAMES) and four
@@ -367,43 +369,21 @@ class Core:
         the constant-length pose rigid_legs() fits, whose lengths are the fixed ones; "recording" is then still
         the recording frame of the MEASURED pose, so that both sets of angles share one frame.  A rank-0 method, like the
         reprojection-error queries."""
-        angles, lengths = self._joint_angles_on_device("joint_angles", body_frame, rigid)
+        chain = self._measured_pose("joint_angles")
+        angles, lengths = (chain.rigid() if rigid else chain).joint_angles(body_frame)
         return angles.cpu().numpy(), lengths.cpu().numpy()
 
-    def _joint_angles_on_device(self, what, body_frame, rigid):
-        X = self._measured_pose(what)
-        if rigid:
-            if isinstance(body_frame, str) and body_frame == "recording" and X.shape[0]:
-                body_frame = ops._recording_frame(X)
-            X = ops.fit_legs(X).points
-        return ops.joint_angles(X, body_frame)
-
-    # -- constant-length legs (DESIGN.md section 15) ------------------------------------------------------------------------------------
     def rigid_legs(self, lengths="recording", anchor="per_frame"):
         """(points [T, 38, 3], lengths [6, 4], cost [T, 6]) as numpy arrays: the triangulation `camNet.points3d` with every leg replaced
         by the chain of constant segment lengths that lies closest to its measured joints (ops.fit_legs), the lengths used, and each
         leg's summed squared distance from the measured joints (NaN where a leg misses a joint and is left as measured).  `lengths`:
         "recording" (every segment's median over the recording) or a [6, 4] array; `anchor`: "per_frame", "recording" or a [6, 3]
         array.  Triangulates first when there is no points3d yet.  A rank-0 method with joint_angles' refusals."""
-        fit = ops.fit_legs(self._measured_pose("rigid_legs"), lengths, anchor)
+        fit = ops.fit_legs(self._measured_pose("rigid_legs").points3d, lengths, anchor)
         return fit.points.cpu().numpy(), np.array(fit.lengths), fit.cost.cpu().numpy()
 
-    # -- wavelet spectrograms of the joint angles (DESIGN.md section 16) ----------------------------------------------------------------
-    def angle_spectrogram(self, rigid=False, body_frame="recording", fps=None, unwrap=True, **bank):
-        """(S [T, 6, 8, F], freqs [F]) as numpy arrays: the Morlet wavelet amplitudes (ops.wavelet_spectrogram, radians) of the
-        48 joint-angle series joint_angles(body_frame, rigid) returns, and the rows' frequencies in Hz.  `fps`: the sampling rate;
-        None means get_fps(), and where that is None config.SPECTROGRAM_FPS.  `unwrap=True` first applies numpy.unwrap's rule
-        along time to the angles that live on the full circle (config.SPECTROGRAM_UNWRAPPED_ANGLES): a wrap at +-pi is otherwise
-        a step of 2 pi that lights up every row.  A series that holds a non-finite sample is left wrapped and named in one logged
-        warning.  `bank`: f_min, f_max, num (ops.wavelet_frequencies) or freqs, and omega0, radius.  A rank-0 method with
-        joint_angles' refusals."""
-        S, freqs, _ = self._angle_spectrogram(rigid, body_frame, fps, unwrap, torch.float64, bank)
-        return S, freqs
-
-    def _angle_spectrogram(self, rigid, body_frame, fps, unwrap, dtype, bank, on_device=False, what="angle_spectrogram"):
-        from . import config
-
-        bank = dict(bank)
+    def _wavelet_bank(self, what, fps, bank):
+        """(fps, {freqs, omega0, radius}) of angle_spectrogram's `fps` and `bank`, refused before any device work."""
         unknown = set(bank) - {"f_min", "f_max", "num", "freqs", "omega0", "radius"}
         if unknown:
             raise TypeError(f"{what} got unexpected bank arguments {sorted(unknown)}")
@@ -412,42 +392,39 @@ class Core:
         if fps is None:
             fps = self.get_fps()
         if fps is None:
-            fps = config.SPECTROGRAM_FPS
+            fps = SPECTROGRAM_FPS
         fps = float(fps)
         freqs = bank["freqs"] if "freqs" in bank else ops.wavelet_frequencies(fps, bank.get("f_min"), bank.get("f_max"), bank.get("num"))
-        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
-        angles = self._joint_angles_on_device(what, body_frame, rigid)[0]
-        T = angles.shape[0]
-        series = angles.reshape(T, 48)
-        if unwrap:
-            names = config.LEG_ANGLE_NAMES
-            cols = [8 * leg + names.index(a) for leg in range(6) for a in config.SPECTROGRAM_UNWRAPPED_ANGLES]
-            series, left = ops.unwrap_phase(series, cols)
-            if left:
-                logger.warning("angle_spectrogram: not unwrapped, because they hold a non-finite sample: "
-                               + ", ".join(f"{config.LEG_NAMES[c // 8]} {names[c % 8]}" for c in left))
-        S = ops.wavelet_spectrogram(series.reshape(T, 6, 8), fps, freqs, bank.get("omega0"), bank.get("radius"), dtype=dtype)
-        return S if on_device else S.cpu().numpy(), freqs, fps
+        return fps, dict(freqs=np.ascontiguousarray(freqs, dtype=np.float64), omega0=bank.get("omega0"), radius=bank.get("radius"))
 
-    # -- t-SNE behaviour map of the angle spectrograms ---------------------------------------------------------
+    def angle_spectrogram(self, rigid=False, body_frame="recording", fps=None, unwrap=True, **bank):
+        """(S [T, 6, 8, F], freqs [F]) as numpy arrays: the Morlet wavelet amplitudes (ops.wavelet_spectrogram, radians) of the
+        48 joint-angle series joint_angles(body_frame, rigid) returns, and the rows' frequencies in Hz.  `fps`: the sampling rate;
+        None means get_fps(), and where that is None config.SPECTROGRAM_FPS.  `unwrap=True` first applies numpy.unwrap's rule
+        along time to the angles that live on the full circle (config.SPECTROGRAM_UNWRAPPED_ANGLES): a wrap at +-pi is otherwise
+        a step of 2 pi that lights up every row.  A series that holds a non-finite sample is left wrapped and named in one logged
+        warning.  `bank`: f_min, f_max, num (ops.wavelet_frequencies) or freqs, and omega0, radius.  A rank-0 method with
+        joint_angles' refusals."""
+        fps, bank = self._wavelet_bank("angle_spectrogram", fps, bank)
+        chain = self._measured_pose("angle_spectrogram", fps)
+        return (chain.rigid() if rigid else chain).spectrogram(body_frame, unwrap, **bank).cpu().numpy(), bank["freqs"]
+
     def behaviour_map(self, rigid=False, perplexity=None, n_iter=None, max_points=None, seed=0, **spectrogram_kwargs):
         """The behaviour map (ops.behaviour_map) of the float64 spectrogram angle_spectrogram(rigid, **spectrogram_kwargs) computes,
         every frame's [6, 8, F] amplitudes flattened to one spectrum: an ops.BehaviourMapResult of numpy arrays -- embedding [T, 2]
         (NaN for a frame whose spectrum holds a NaN), train_index [N], beta [T], info [T], kl and perplexity.  A recording too
         short for the perplexity (3 perplexity <= frames - 1) is refused before anything is computed.  A rank-0 method with
         angle_spectrogram's refusals."""
-        r = self._behaviour_map(rigid, perplexity, n_iter, max_points, seed, spectrogram_kwargs)
-        return ops.BehaviourMapResult(r.embedding.cpu().numpy(), r.train_index.cpu().numpy(), r.beta.cpu().numpy(), r.info.cpu().numpy(), r.kl,
-                                      r.perplexity)
-
-    def _behaviour_map(self, rigid, perplexity, n_iter, max_points, seed, kwargs):
-        kwargs = dict(kwargs)
-        body_frame, fps, unwrap = kwargs.pop("body_frame", "recording"), kwargs.pop("fps", None), kwargs.pop("unwrap", True)
+        bank = dict(spectrogram_kwargs)
+        body_frame, fps, unwrap = bank.pop("body_frame", "recording"), bank.pop("fps", None), bank.pop("unwrap", True)
         frames = getattr(self, "num_images", None)
         if frames is not None and self.camNet is not None and self.camNet.has_calibration():
             ops.behaviour_map_points(frames, perplexity, max_points)   # before any work
-        S = self._angle_spectrogram(rigid, body_frame, fps, unwrap, torch.float64, kwargs, on_device=True, what="behaviour_map")[0]
-        return ops.behaviour_map(S, perplexity, n_iter, max_points, seed)
+        fps, bank = self._wavelet_bank("behaviour_map", fps, bank)
+        chain = self._measured_pose("behaviour_map", fps)
+        r = (chain.rigid() if rigid else chain).behaviour_map(perplexity, n_iter, max_points, seed, body_frame=body_frame, unwrap=unwrap, **bank)
+        return ops.BehaviourMapResult(r.embedding.cpu().numpy(), r.train_index.cpu().numpy(), r.beta.cpu().numpy(), r.info.cpu().numpy(), r.kl,
+                                      r.perplexity)
 
     # -- manual corrections (DESIGN.md section 11; reference df3d/core.py:253-296, 477-479, 509-544) ---------------------------------
     _MOVE_THRESHOLD = 30   # pixels, per coordinate: a pose that differs less from the estimate on every checked joint is not stored
@@ -652,27 +629,49 @@ class Core:
             result["points2d_argmax"] = np.copy(self.points2d_argmax)
         if getattr(self, "_subpixel", False):   # only when this run refined its detections: without it the schema is the reference's
             result["subpixel"] = True
-        if joint_angles:   # opt-in, like the two keys above: without it the schema is the reference's
-            result["joint_angles"], result["segment_lengths"] = self.joint_angles()
-        if rigid_legs:
-            result["points3d_rigid"], result["rigid_segment_lengths"], result["rigid_fit_cost"] = self.rigid_legs()
-            if joint_angles:
-                result["joint_angles_rigid"] = self.joint_angles(rigid=True)[0]
-        if angle_spectrogram:
-            result["angle_spectrogram"], result["spectrogram_freqs"], result["spectrogram_fps"] = self._angle_spectrogram(
-                False, "recording", None, True, torch.float32, {})
-            if rigid_legs:
-                result["angle_spectrogram_rigid"] = self._angle_spectrogram(True, "recording", None, True, torch.float32, {})[0]
-        if behaviour_map:
-            m = self.behaviour_map(perplexity=behaviour_perplexity)
-            result["behaviour_map"], result["behaviour_map_train_index"] = m.embedding, m.train_index
-            result["behaviour_map_kl"], result["behaviour_map_perplexity"] = m.kl, m.perplexity
-            if rigid_legs:
-                m = self.behaviour_map(rigid=True, perplexity=behaviour_perplexity)
-                result["behaviour_map_rigid"], result["behaviour_map_rigid_kl"] = m.embedding, m.kl
+        if joint_angles or rigid_legs or angle_spectrogram or behaviour_map:   # opt-in, like the two keys above: else the reference's schema
+            result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity))
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")
+
+    _KINEMATIC_KEYS = ("joint_angles", "segment_lengths", "points3d_rigid", "rigid_segment_lengths", "rigid_fit_cost", "joint_angles_rigid",
+                       "angle_spectrogram", "spectrogram_freqs", "spectrogram_fps", "angle_spectrogram_rigid", "behaviour_map",
+                       "behaviour_map_train_index", "behaviour_map_kl", "behaviour_map_perplexity", "behaviour_map_rigid", "behaviour_map_rigid_kl")
+
+    def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity):
+        """The keys save()'s flags append, in the result's order, all read from one PoseChain of this save's triangulation."""
+        what = "joint_angles" if joint_angles else "rigid_legs" if rigid_legs else "angle_spectrogram" if angle_spectrogram else "behaviour_map"
+        spectra = angle_spectrogram or behaviour_map
+        fps, bank = self._wavelet_bank(what, None, {}) if spectra else (None, {})   # save()'s fps and frequencies are the method's defaults
+        chains = [self._measured_pose(what, fps)]
+        keys, host = {}, lambda t: t.cpu().numpy()
+        if joint_angles:
+            keys["joint_angles"], keys["segment_lengths"] = map(host, chains[0].angles)
+        if rigid_legs:
+            chains.append(chains[0].rigid())
+            keys["points3d_rigid"], keys["rigid_fit_cost"] = host(chains[0].fit.points), host(chains[0].fit.cost)
+            keys["rigid_segment_lengths"] = np.array(chains[0].fit.lengths)
+            if joint_angles:
+                keys["joint_angles_rigid"] = host(chains[1].angles[0])
+        # The spectra read the [T, 48] series alone, and those wait on the host too (384 bytes per frame).  Everything the chains hold
+        # is dropped with them, so that a map runs beside its own spectrogram and nothing else, as it did when every key started anew.
+        dev = chains[0].points3d.device
+        series = [c.series.unflatten(1, (6, 8)).cpu() for c in chains] if spectra else []
+        del chains
+        for tag in ("", "_rigid")[:len(series)]:
+            S = ops.wavelet_spectrogram(series.pop(0).to(dev), fps, dtype=torch.float64 if behaviour_map else torch.float32, **bank)
+            if angle_spectrogram:   # the float64 amplitude rounded once: by this cast where the map needs float64, else by the kernel
+                keys["angle_spectrogram" + tag] = host(S.to(torch.float32))
+            if behaviour_map:
+                m = ops.behaviour_map(S, perplexity)
+                keys["behaviour_map" + tag], keys[f"behaviour_map{tag}_kl"] = host(m.embedding), m.kl
+                if not tag:
+                    keys["behaviour_map_train_index"], keys["behaviour_map_perplexity"] = host(m.train_index), m.perplexity
+            S = m = None   # released before the other variant's is computed: one float64 spectrogram at a time
+        if angle_spectrogram:
+            keys["spectrogram_freqs"], keys["spectrogram_fps"] = bank["freqs"], fps
+        return {k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}
 
     # -- helpers --------------------------------------------------------------------------------------
     def _correction_for(self, corrections, cam_id, img_id):

@@ -1,4 +1,6 @@
-"""Thin host wrappers over the C ABI for the non-network kernels (a3 arg-max, a4 re-layout, a6 triangulation).
+"""Thin host wrappers over the C ABI for the non-network kernels: arg-max and peaks, re-layout, triangulation, Procrustes and the
+video pose, and what DESIGN.md sections 9-17 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
+overlay, joint angles, the leg fit, wavelet spectrograms and behaviour maps.
 
 Inputs/outputs are torch CUDA tensors (device memory + stream plumbing only); every computation is a
 libdf3d_hip.so kernel.  No CPU fallback: a missing library or GPU raises `_native.NativeLibraryError`.
@@ -378,7 +380,7 @@ def _coxa_medians(points3d):
     return coxae, column_median(cols).reshape(6, 3)
 
 
-def _recording_frame(points3d):
+def recording_frame(points3d):
     """[1, 3, 3]: the body frame of the pose whose 18 body-coxa coordinates are the temporal medians of those of points3d
     [T >= 1, 38, 3]: one frame for a tethered fly's recording."""
     coxae, medians = _coxa_medians(points3d)
@@ -411,7 +413,7 @@ def joint_angles(points3d, body_frame="recording"):
     if T == 0:   # no medians to take, nothing to launch
         return angles, lengths
     if frames is None:
-        frames = _recording_frame(points3d) if body_frame == "recording" else _pose_frames(points3d)
+        frames = recording_frame(points3d) if body_frame == "recording" else _pose_frames(points3d)
     _native.check(lib.df3d_joint_angles(points3d.data_ptr(), T, frames.data_ptr(), frames.shape[0], angles.data_ptr(), lengths.data_ptr(),
                                         _stream(points3d)), "df3d_joint_angles")
     return angles, lengths

@@ -343,7 +343,7 @@ def test_cli_skip_pose_estimation_angle_spectrogram_rigid_legs(native_lib, cuda,
     for key, pose in (("angle_spectrogram", run["points3d_wo_procrustes"]), ("angle_spectrogram_rigid", run["points3d_rigid"])):
         assert run[key].shape == (15, 6, 8, 25) and run[key].dtype == np.float32
         X = torch.from_numpy(np.ascontiguousarray(run["points3d_wo_procrustes"])).to(cuda)
-        frame = ops._recording_frame(X)
+        frame = ops.recording_frame(X)
         angles = ops.joint_angles(torch.from_numpy(np.ascontiguousarray(pose)).to(cuda), frame)[0].cpu().numpy()
         series, _ = _unwrapped(angles)
         want = so.spectrogram(series.reshape(15, 6, 8), 100.0, run["spectrogram_freqs"])
