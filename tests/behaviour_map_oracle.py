@@ -132,6 +132,15 @@ def row_entropy(K_row, beta, exclude=-1):
     return H, beta * var, k - q, keep
 
 
+def conditional_tolerance(c, dk, slope, n):
+    """The bar per admitted entry of a calibrated row c (the oracle's) against one calibrated on its own: both betas sit within
+    bar_H = ENTROPY_TOL + entropy_rounding(n) of the target in H, so within 2 bar_H / |dH/dbeta| of each other (1 % for the
+    curvature); dc_j / dbeta = c_j (k_mean - k_j); the weights' own rounding is a relative (n + 8) 2^-52.  `dk` and `slope` are
+    row_entropy's."""
+    bar_H = ENTROPY_TOL + entropy_rounding(n)
+    return 1.01 * c * np.abs(dk) * 2.0 * bar_H / slope + 8.0 * (n + 8) * EPS * c
+
+
 def entropy_rounding(n):
     """What rounding may add to an n-term evaluation of H = log S + beta Q / S: every weight carries the exponential's own error and
     the rounding of its argument (a relative beta k 2^-53, which sums to 2^-53 beta Q / S <= 2^-53 log n over the row), S and Q
@@ -207,6 +216,14 @@ def cost(P, Y):
     _, w, Z = pair_terms(Y)
     m = P > 0
     return float((P[m] * np.log(P[m] * Z / w[m])).sum())
+
+
+def cost_tolerance(P, Y):
+    """The bar of the cost, an N^2-term sum of P (log P + log Z - log w): the worst case of the sum with the constant 4, as for the
+    gradient."""
+    _, w, Z = pair_terms(Y)
+    m = P > 0
+    return 4.0 * (Y.shape[0] + 64) * EPS * float((P[m] * (np.abs(np.log(P[m])) + abs(np.log(Z)) + np.abs(np.log(w[m])))).sum())
 
 
 def initial(N, seed=0):
@@ -299,15 +316,77 @@ def step_comparison(P, state, k, got):
     return max(fy, fv, fg), excused.mean()
 
 
+LARGE_SIZES = (1024, 1025, 1283)   # one full trip of the gradient kernel's 1024-column loop; a second trip of one column; one of 259
+LARGE_SYNTHETIC = {120: (5, 3.0), 399: (6, 20.0)}   # stage: (seed, scale) of the synthetic states
+GAINS = (0.01, 0.64, 0.8, 1.0, 1.2, 2.4)
+
+
+@functools.lru_cache(maxsize=None)
+def large_cond(N):
+    """cond [N, N] of N spectra of 25 channels at perplexity 10, the row itself excluded."""
+    p = distributions(spectra(N, 25, seed=170 + N)[0])[0]
+    return calibrate(divergence(p, p), 10.0, "self")[0]
+
+
+def synthetic_state(N, seed, scale):
+    """(Y, V, G) that no run has to reach: three clusters of spread 0.2 scale round centres drawn N(0, scale^2), frame t in
+    cluster t mod 3, velocities N(0, (0.01 scale)^2) and gains from GAINS (the floor, both branches' products, the start)."""
+    rng = np.random.default_rng(seed)
+    centres = scale * rng.standard_normal((3, 2))
+    Y = centres[np.arange(N) % 3] + 0.2 * scale * rng.standard_normal((N, 2))
+    V = 0.01 * scale * rng.standard_normal((N, 2))
+    G = rng.choice(np.array(GAINS), size=(N, 2))
+    return Y, V, G
+
+
+@functools.lru_cache(maxsize=None)
+def large_case(N):
+    """(P, {k: (Y, V, G) before iteration k}) for one teacher-forced step at the sizes of LARGE_SIZES.  The oracle is NOT run
+    for 400 iterations here (minutes): stage 0 is the real start, stages 120 and 399 are synthetic_state's -- a state does not
+    have to be reachable for one step from it to be checked."""
+    P = joint(large_cond(N))
+    Y0 = initial(N, seed=N)
+    states = {0: (Y0, np.zeros_like(Y0), np.ones_like(Y0))}
+    for k, (seed, scale) in LARGE_SYNTHETIC.items():
+        states[k] = synthetic_state(N, seed, scale)
+    assert sorted(states) == list(TEACHER_STAGES)
+    return P, states
+
+
+# the calibration keeps its row in 8 N bytes of dynamic LDS: the last size below 48 KiB and the first above it (there the launch
+# raises the kernel's limit), both sides of 64 KiB (8192 is the default training size) and the cap
+WIDE_SIZES = (6144, 6145, 8192, 8193, 16384)
+WIDE_TIES = 40
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case(N):
+    """(pa [4, 25], pb [N, 25], K [5, N], exclude [5] int32): four ordinary rows of divergences against N columns and a fifth in
+    which WIDE_TIES entries tie exactly at the row's minimum -- spread over the whole row, column N - 2 among them -- and every
+    other entry lies at least 0.75 above: at the default perplexity of 32 that row cannot be calibrated.  `exclude` is the
+    explicit list: the last column, none, the first, one in the 17th stride of a 256-thread loop, and for the tied row the
+    column next to its last tie."""
+    pa = distributions(spectra(4, 25, seed=N)[0])[0]
+    pb = distributions(spectra(N, 25, seed=N + 1)[0])[0]
+    K = np.empty((5, N))
+    K[:4] = divergence(pa, pb)
+    K[4] = np.abs(np.random.default_rng(N + 2).standard_normal(N)) + 1.0
+    K[4, wide_ties(N)] = 0.25
+    return pa, pb, K, np.array([N - 1, -1, 0, 4097, N - 1], dtype=np.int32)
+
+
+def wide_ties(N):
+    ties = np.unique(np.linspace(2, N - 2, WIDE_TIES).astype(np.int64))
+    assert len(ties) == WIDE_TIES and ties[-1] == N - 2
+    return ties
+
+
 PLANTED = dict(D=40, spread=0.12, seed=1717, perplexity=10.0, n_iter=500, max_points=120, invalid=(6, 51, 112, 179))
 
 
 @functools.lru_cache(maxsize=None)
-def planted_case():
-    """(S [184, D], labels [184] (-1: invalid), the oracle's result, the final KL of eight perturbed starts): three planted
-    behaviours interleaved in time (frame t shows behaviour t mod 3), four invalid rows that leave 60 valid frames each.  120 of
-    the 180 valid frames are embedded and 60 placed; the invalid rows shift the phase of the training rule floor(1.5 i) against
-    the labels, so every behaviour has training frames and placed ones."""
+def planted_spectra():
+    """(S [184, D], labels [184] (-1: invalid)) of planted_case, without the oracle's runs."""
     c = PLANTED
     T = 180 + len(c["invalid"])
     full, lab = spectra(T, c["D"], c["seed"], spread=c["spread"])
@@ -319,6 +398,17 @@ def planted_case():
     lab = lab.copy()
     lab[list(c["invalid"])] = -1
     assert [int((lab == k).sum()) for k in range(3)] == [60, 60, 60]
+    return full, lab
+
+
+@functools.lru_cache(maxsize=None)
+def planted_case():
+    """(S [184, D], labels [184] (-1: invalid), the oracle's result, the final KL of eight perturbed starts): three planted
+    behaviours interleaved in time (frame t shows behaviour t mod 3), four invalid rows that leave 60 valid frames each.  120 of
+    the 180 valid frames are embedded and 60 placed; the invalid rows shift the phase of the training rule floor(1.5 i) against
+    the labels, so every behaviour has training frames and placed ones."""
+    c = PLANTED
+    full, lab = planted_spectra()
     res = behaviour_map(full, c["perplexity"], c["n_iter"], c["max_points"], seed=0)
     Y0 = initial(c["max_points"], 0)
     kls = [cost(res["P"], run(res["P"], y, c["n_iter"])[0]) for y in perturbed(Y0)]

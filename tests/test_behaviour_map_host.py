@@ -145,6 +145,52 @@ def test_teacher_seeds_keep_the_excused_components_under_one_percent():
             assert frac == 0.0 and excused <= 0.01, (N, k, excused)
 
 
+@pytest.mark.parametrize("N", bo.LARGE_SIZES)
+def test_large_cases_stay_inside_their_bars_in_another_summation_order(N):
+    """What the GPU step tests at LARGE_SIZES rest on.  The oracle's step with every point renumbered back to front sums each
+    row's columns, and Z, in the opposite order: a stand-in for the device's order.  It stays inside step_comparison's bars with
+    at most 1 % of the components excused (the existing cap, not a measurement), at the real start and at both synthetic
+    states, and the synthetic gains take both branches and the floor."""
+    P, states = bo.large_case(N)
+    assert sorted(states) == list(bo.TEACHER_STAGES) and P.shape == (N, N)
+    assert np.array_equal(P, P.T) and np.all(np.diag(P) == 0) and abs(P.sum() - 1.0) <= 64 * bo.EPS
+    assert np.abs(states[0][0]).max() < 1e-3 and not states[0][1].any() and np.all(states[0][2] == 1.0)
+    Pr = np.ascontiguousarray(P[::-1, ::-1])
+    for k, state in states.items():
+        got = [a[::-1] for a in bo.step(Pr, *(a[::-1] for a in state), k)[:3]]
+        frac, excused = bo.step_comparison(P, state, k, got)
+        print(f"N = {N}, stage {k}: the reversed order is {frac:.3g} of the bars from the oracle, {100 * excused:.2g} % excused")
+        assert frac <= 1.0 and excused <= 0.01, (N, k, frac, excused)
+        if k:
+            Y, V, G = state
+            g = bo.gradient(P, Y, bo.schedule(k)[0])
+            up = g * V < 0.0
+            assert set(np.unique(G)) == set(bo.GAINS)
+            assert up.any() and (~up).any()                                      # G + 0.2 and 0.8 G
+            assert (~up & (G == 0.01)).any() and (up & (G == 0.01)).any()         # 0.008 is lifted to the floor, 0.21 is not
+            assert np.abs(Y).max() > 1.0 and V.all()
+
+
+@pytest.mark.parametrize("N", bo.WIDE_SIZES)
+def test_wide_cases_calibrate_and_their_tied_row_is_refused(N):
+    """What the GPU calibration tests at WIDE_SIZES rest on: the oracle's own beta meets the entropy bar on the four ordinary
+    rows with and without an exclusion, and the tied row gets beta_max, bit 0 and 1 / 40 on its ties.  Nothing O(N^2) is built."""
+    pa, pb, K, exclude = bo.wide_case(N)
+    ties = bo.wide_ties(N)
+    assert K.shape == (5, N) and pa.shape == (4, 25) and pb.shape == (N, 25) and list(exclude[:4]) == [N - 1, -1, 0, 4097]
+    assert N - 2 in ties and exclude[4] not in ties and np.all(K[4, ties] == K[4].min()) and np.delete(K[4], ties).min() >= K[4].min() + 0.75
+    for ex in (None, exclude):
+        cond, beta, info = bo.calibrate(K, bo.PERPLEXITY, ex)
+        assert list(info) == [0, 0, 0, 0, 1] and beta[4] == bo.BETA_MAX and np.all((beta[:4] > 1.0) & (beta[:4] < 1e3))
+        for i in range(4):
+            x = -1 if ex is None else int(ex[i])
+            n = N - (x >= 0)
+            H, slope, _, keep = bo.row_entropy(K[i], beta[i], x)
+            assert abs(H - np.log(bo.PERPLEXITY)) <= bo.ENTROPY_TOL + bo.entropy_rounding(n) and slope > 0
+            assert keep.sum() == n and (x < 0 or cond[i, x] == 0.0) and abs(cond[i].sum() - 1.0) <= (n + 8) * bo.EPS
+        assert np.array_equal(cond[4, ties], np.full(bo.WIDE_TIES, 1.0 / bo.WIDE_TIES)) and not np.delete(cond[4], ties).any()
+
+
 def test_resumed_runs_are_the_whole_run():
     P, _ = bo.teacher_case(13)
     Y0 = bo.initial(13, 5)

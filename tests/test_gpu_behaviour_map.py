@@ -95,10 +95,8 @@ def test_calibration(native_lib, cuda, N, exclude):
     for i in range(N):
         H, slope, dk, keep = bo.row_entropy(K[i], beta[i], i if exclude else -1)
         worst_H = max(worst_H, abs(H - np.log(u)) / bar_H)
-        # both betas sit within bar_H of the target in H, so within 2 bar_H / |dH/dbeta| of each other (1 % for the curvature);
-        # dc_j / dbeta = c_j (k_mean - k_j); the weights' own rounding is a relative (n + 8) 2^-52
         c = want[i, keep]
-        bar_c = 1.01 * c * np.abs(dk) * 2.0 * bar_H / slope + 8.0 * (n + 8) * bo.EPS * c
+        bar_c = bo.conditional_tolerance(c, dk, slope, n)
         worst_c = max(worst_c, _fraction(np.abs(cond[i, keep] - c), bar_c))
         if exclude:
             assert cond[i, i] == 0.0
@@ -152,10 +150,7 @@ def test_teacher_forced_step_and_cost(native_lib, cuda, N):
         Y, V, G = kept[k]
         got = [t.cpu().numpy() for t in ops.tsne(Pd, _dev(Y, cuda), 1, first_iter=k, state=(_dev(V, cuda), _dev(G, cuda)))]
         frac, excused = bo.step_comparison(P, (Y, V, G), k, got)
-        # the cost at the same state: an N^2-term sum of P (log P + log Z - log w)
-        _, w, Z = bo.pair_terms(Y)
-        m = P > 0
-        bar = 4.0 * (N + 64) * bo.EPS * (P[m] * (np.abs(np.log(P[m])) + abs(np.log(Z)) + np.abs(np.log(w[m])))).sum()
+        bar = bo.cost_tolerance(P, Y)   # the cost at the same state
         cerr = abs(float(ops.tsne_cost(Pd, _dev(Y, cuda))) - bo.cost(P, Y))
         print(f"N = {N}, iteration {k}: Y, V, G up to {frac:.3g} of their bars, {100 * excused:.2g} % excused; the cost {cerr / bar:.3g} of its bar")
         assert frac <= 1.0 and excused <= 0.01 and cerr <= bar
