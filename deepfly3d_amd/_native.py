@@ -109,6 +109,12 @@ PROTOTYPES = {
     "df3d_bmap_place": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
     "df3d_bmap_cost": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "df3d_tsne_run": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_longlong, c_void_p]),
+    "df3d_bseg_work_bytes": (c_longlong, [c_longlong, c_int]),
+    "df3d_bseg_bounds": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p]),
+    "df3d_bseg_density": (c_int, [c_void_p, c_longlong, c_double, c_double, c_double, c_int, c_double, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_bseg_watershed": (c_int, [c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_bseg_labels": (c_int, [c_void_p, c_longlong, c_double, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "df3d_bseg_bouts": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "df3d_ba_eval": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_colsq": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_matvec": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

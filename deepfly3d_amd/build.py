@@ -25,8 +25,10 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # smooth.hip keeps the default -ffp-contract=fast on purpose: its test bound is 1e-10 px, not bit parity, fused multiply-adds only
 # tighten the sums, and the pass is bound by float64 vector instructions, which contraction cuts by a quarter
 # subpixel.hip: the float64 sub-pixel rule, compared bit for bit with tests/subpixel_oracle.py
+# behaviour_segment.hip: the grid coordinates, the cell of a frame and the peak threshold are the operations of
+# tests/behaviour_segment_oracle.py one by one: the integer outputs are compared exactly, and the density's bar assumes the oracle's coordinates
 FILE_FLAGS = {"pose3d.hip": ["-ffp-contract=off"], "ba_lsmr.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"],
-              "subpixel.hip": ["-ffp-contract=off"]}
+              "subpixel.hip": ["-ffp-contract=off"], "behaviour_segment.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -85,7 +85,28 @@ def parse_cli_args(argv=None):
     p.add_argument("--behaviour-perplexity", dest="behaviour_perplexity", type=float, default=None, metavar="U",
                    help="With --behaviour-map: the effective number of neighbours of a frame (default 32).  The recording needs at least "
                         "3 U + 1 frames")
+    p.add_argument("--behaviour-segments", dest="behaviour_segments", action="store_true",
+                   help="With --behaviour-map: segment the map and append the keys behaviour_density [G, G] (the Gaussian density of the frames on "
+                        "a square grid), behaviour_density_origin (x0, y0 and the cell size h), behaviour_density_sigma, behaviour_regions [G, G] (the "
+                        "watershed region of every cell round the density's peaks, 0: none), behaviour_region_peaks [R, 2], behaviour_labels [T] "
+                        "(int32: every frame's region, 0: none, -1: a frame without a place on the map), behaviour_bouts [B, 3] (label, start, "
+                        "length), behaviour_occupancy and behaviour_transitions to the result; together with --rigid-legs also the same nine "
+                        "with _rigid appended.  Works with --skip-pose-estimation on an earlier result")
+    p.add_argument("--behaviour-sigma", dest="behaviour_sigma", type=float, default=None, metavar="S",
+                   help="With --behaviour-segments: the deviation of the density's Gaussians in the map's units (default 1/32 of the map's extent)")
+    p.add_argument("--behaviour-grid", dest="behaviour_grid", type=int, default=None, metavar="G",
+                   help="With --behaviour-segments: the cells per side of the density's grid, 2 to 1024 (default 256)")
     args = p.parse_args(argv)
+    if args.behaviour_segments and not args.behaviour_map:
+        p.error("--behaviour-segments segments the map of --behaviour-map: it needs --behaviour-map")
+    if args.behaviour_sigma is not None and not args.behaviour_segments:
+        p.error("--behaviour-sigma sets the density of --behaviour-segments: it needs --behaviour-segments")
+    if args.behaviour_grid is not None and not args.behaviour_segments:
+        p.error("--behaviour-grid sets the grid of --behaviour-segments: it needs --behaviour-segments")
+    if args.behaviour_sigma is not None and not (math.isfinite(args.behaviour_sigma) and args.behaviour_sigma > 0.0):
+        p.error("--behaviour-sigma must be finite and > 0")
+    if args.behaviour_grid is not None and not 2 <= args.behaviour_grid <= 1024:
+        p.error("--behaviour-grid must be in [2, 1024]")
     if args.behaviour_perplexity is not None and not args.behaviour_map:
         p.error("--behaviour-perplexity sets the perplexity of --behaviour-map: it needs --behaviour-map")
     if args.behaviour_perplexity is not None and not (math.isfinite(args.behaviour_perplexity) and args.behaviour_perplexity > 1.0):
@@ -133,6 +154,8 @@ def run(args):
     extras = {name: getattr(args, name, False) for name in ("joint_angles", "rigid_legs", "angle_spectrogram", "behaviour_map")}
     flagged = [name for name, on in extras.items() if on]
     extras["behaviour_perplexity"] = getattr(args, "behaviour_perplexity", None)
+    if getattr(args, "behaviour_segments", False):   # the map's segmentation: no keys of its own flag without --behaviour-map
+        extras.update(behaviour_segments=True, behaviour_sigma=getattr(args, "behaviour_sigma", None), behaviour_grid=getattr(args, "behaviour_grid", None))
     if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not flagged:
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0

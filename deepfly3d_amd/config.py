@@ -101,6 +101,15 @@ BEHAVIOUR_BETA_MAX = 1e12
 BEHAVIOUR_ITERATIONS = 1000
 BEHAVIOUR_EXAGGERATION_ITERATIONS = 250
 
+# ---- segmentation of the behaviour map.  The density of the map is a sum of Gaussians of deviation
+# BEHAVIOUR_DENSITY_SIGMA_FRACTION times the map's larger extent, on a square grid of BEHAVIOUR_GRID x BEHAVIOUR_GRID cells that
+# reaches three deviations past the outermost frames; a peak of the density founds a region when it reaches BEHAVIOUR_MIN_PEAK of
+# the highest.
+BEHAVIOUR_GRID = 256
+BEHAVIOUR_GRID_RANGE = (2, 1024)
+BEHAVIOUR_DENSITY_SIGMA_FRACTION = 1.0 / 32.0
+BEHAVIOUR_MIN_PEAK = 0.01
+
 # ---- which camera sees which joint (reference df3d/skeleton_fly.py:202-250), by camera id: cameras 0-2 look at the side whose
 # joints are 0..18, cameras 4-6 at the side of joints 19..37, camera 3 faces the fly.  Pinned by tests/golden/skeleton_tables.npz.
 # Where df3d::relayout_source (csrc/geometry_dev.h) fills a joint of a side camera under the identity ordering, this table sees it;

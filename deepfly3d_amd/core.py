@@ -426,6 +426,26 @@ class Core:
         return ops.BehaviourMapResult(r.embedding.cpu().numpy(), r.train_index.cpu().numpy(), r.beta.cpu().numpy(), r.info.cpu().numpy(), r.kl,
                                       r.perplexity)
 
+    def behaviour_segments(self, rigid=False, grid=None, sigma=None, min_peak=None, **behaviour_map_kwargs):
+        """The segmentation (ops.segment_map) of the map behaviour_map(rigid, **behaviour_map_kwargs) computes, the map itself
+        computed once: an ops.BehaviourSegmentsResult of numpy arrays -- density [G, G], origin (x0, y0, h), sigma, regions [G, G]
+        int32, region_peaks [R, 2], labels [T] int32 (-1 for a frame without a place on the map, 0 for one outside every region),
+        bouts [B, 3] int64 (label, start, length), occupancy [R + 1] and transitions [R + 1, R + 1] int64.  `grid`, `sigma`,
+        `min_peak`: config.BEHAVIOUR_GRID, config.BEHAVIOUR_DENSITY_SIGMA_FRACTION of the map's extent and
+        config.BEHAVIOUR_MIN_PEAK by default.  A rank-0 method with behaviour_map's refusals."""
+        kw = dict(behaviour_map_kwargs)
+        perplexity, max_points = kw.pop("perplexity", None), kw.pop("max_points", None)
+        n_iter, seed = kw.pop("n_iter", None), kw.pop("seed", 0)
+        body_frame, fps, unwrap = kw.pop("body_frame", "recording"), kw.pop("fps", None), kw.pop("unwrap", True)
+        frames = getattr(self, "num_images", None)
+        if frames is not None and self.camNet is not None and self.camNet.has_calibration():
+            ops.behaviour_map_points(frames, perplexity, max_points)   # before any work
+        fps, bank = self._wavelet_bank("behaviour_segments", fps, kw)
+        chain = self._measured_pose("behaviour_segments", fps)
+        _, s = (chain.rigid() if rigid else chain).behaviour_segments(grid, sigma, min_peak, perplexity=perplexity, n_iter=n_iter,
+                                                                      max_points=max_points, seed=seed, body_frame=body_frame, unwrap=unwrap, **bank)
+        return ops.BehaviourSegmentsResult(*(t.cpu().numpy() if isinstance(t, torch.Tensor) else t for t in s))
+
     # -- manual corrections (DESIGN.md section 11; reference df3d/core.py:253-296, 477-479, 509-544) ---------------------------------
     _MOVE_THRESHOLD = 30   # pixels, per coordinate: a pose that differs less from the estimate on every checked joint is not stored
 
@@ -584,7 +604,8 @@ class Core:
         dd.agree(bad, "the sharded triangulation")
         return None if full is None else full.cpu().numpy()
 
-    def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False, behaviour_perplexity=None):
+    def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False, behaviour_perplexity=None,
+             behaviour_segments=False, behaviour_sigma=None, behaviour_grid=None):
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
         keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras).
         `rigid_legs=True` appends, after those, "points3d_rigid", "rigid_segment_lengths" and "rigid_fit_cost" (Core.rigid_legs()) and,
@@ -593,22 +614,37 @@ class Core:
         "spectrogram_freqs" [F], "spectrogram_fps" and, together with rigid_legs, "angle_spectrogram_rigid".  `behaviour_map=True`
         appends, after all of those, "behaviour_map" [T, 2] float64 (Core.behaviour_map() with its defaults and
         `behaviour_perplexity`), "behaviour_map_train_index", "behaviour_map_kl", "behaviour_map_perplexity" and, together with
-        rigid_legs, "behaviour_map_rigid" and "behaviour_map_rigid_kl"; the spectrogram itself is stored only with angle_spectrogram."""
+        rigid_legs, "behaviour_map_rigid" and "behaviour_map_rigid_kl"; the spectrogram itself is stored only with angle_spectrogram.
+        `behaviour_segments=True` (it needs behaviour_map) appends, after all of those, the segmentation of that same map
+        (ops.segment_map with `behaviour_sigma` and `behaviour_grid`): "behaviour_density" [G, G], "behaviour_density_origin" (x0, y0, h),
+        "behaviour_density_sigma", "behaviour_regions" [G, G] int32, "behaviour_region_peaks" [R, 2], "behaviour_labels" [T] int32,
+        "behaviour_bouts" [B, 3], "behaviour_occupancy" and "behaviour_transitions" and, together with rigid_legs, the same nine with
+        "_rigid" appended."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
         # triangulates every frame itself -- every rank knows that it ran (the flag is set on all of them) and takes this branch
         pts3d_sharded = self._triangulate_sharded() if dd.current()[1] > 1 and not getattr(self, "_corrected", False) else None
         error = None
+        if behaviour_segments and not behaviour_map:
+            raise ValueError("behaviour_segments segments the map behaviour_map computes: it needs behaviour_map=True")
+        if (behaviour_sigma is not None or behaviour_grid is not None) and not behaviour_segments:
+            raise ValueError("behaviour_sigma and behaviour_grid belong to behaviour_segments: they need behaviour_segments=True")
+        segments = (behaviour_sigma, behaviour_grid) if behaviour_segments else None
+        if segments is not None:   # refused before any work
+            if behaviour_grid is not None:
+                ops._need_grid(behaviour_grid)
+            if behaviour_sigma is not None and not (np.isfinite(behaviour_sigma) and behaviour_sigma > 0):
+                raise ValueError(f"behaviour_sigma must be finite and > 0 (it is {behaviour_sigma:g})")
         if self.is_primary:
             try:
-                self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity)
+                self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
     def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False,
-                      behaviour_perplexity=None):
+                      behaviour_perplexity=None, segments=None):
         if behaviour_map and getattr(self, "num_images", None) is not None:   # too short for the perplexity: refused before any work
             ops.behaviour_map_points(self.num_images, behaviour_perplexity)
         result = {"points2d": np.copy(self.points2d)}
@@ -630,7 +666,7 @@ class Core:
         if getattr(self, "_subpixel", False):   # only when this run refined its detections: without it the schema is the reference's
             result["subpixel"] = True
         if joint_angles or rigid_legs or angle_spectrogram or behaviour_map:   # opt-in, like the two keys above: else the reference's schema
-            result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity))
+            result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments))
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")
@@ -638,9 +674,13 @@ class Core:
     _KINEMATIC_KEYS = ("joint_angles", "segment_lengths", "points3d_rigid", "rigid_segment_lengths", "rigid_fit_cost", "joint_angles_rigid",
                        "angle_spectrogram", "spectrogram_freqs", "spectrogram_fps", "angle_spectrogram_rigid", "behaviour_map",
                        "behaviour_map_train_index", "behaviour_map_kl", "behaviour_map_perplexity", "behaviour_map_rigid", "behaviour_map_rigid_kl")
+    _SEGMENT_KEYS = ("behaviour_density", "behaviour_density_origin", "behaviour_density_sigma", "behaviour_regions", "behaviour_region_peaks",
+                     "behaviour_labels", "behaviour_bouts", "behaviour_occupancy", "behaviour_transitions")
+    _KINEMATIC_KEYS += _SEGMENT_KEYS + tuple(k + "_rigid" for k in _SEGMENT_KEYS)
 
-    def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity):
-        """The keys save()'s flags append, in the result's order, all read from one PoseChain of this save's triangulation."""
+    def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity, segments=None):
+        """The keys save()'s flags append, in the result's order, all read from one PoseChain of this save's triangulation.
+        `segments`: None, or (sigma, grid) of the segmentation of every map."""
         what = "joint_angles" if joint_angles else "rigid_legs" if rigid_legs else "angle_spectrogram" if angle_spectrogram else "behaviour_map"
         spectra = angle_spectrogram or behaviour_map
         fps, bank = self._wavelet_bank(what, None, {}) if spectra else (None, {})   # save()'s fps and frequencies are the method's defaults
@@ -668,6 +708,12 @@ class Core:
                 keys["behaviour_map" + tag], keys[f"behaviour_map{tag}_kl"] = host(m.embedding), m.kl
                 if not tag:
                     keys["behaviour_map_train_index"], keys["behaviour_map_perplexity"] = host(m.train_index), m.perplexity
+                if segments is not None:   # of the map just computed: the t-SNE never runs twice
+                    s = ops.segment_map(m.embedding, segments[1], segments[0])
+                    values = (host(s.density), np.array(s.origin), s.sigma, host(s.regions), host(s.region_peaks), host(s.labels), host(s.bouts),
+                              host(s.occupancy), host(s.transitions))
+                    keys.update({k + tag: v for k, v in zip(self._SEGMENT_KEYS, values)})
+                    s = None
             S = m = None   # released before the other variant's is computed: one float64 spectrogram at a time
         if angle_spectrogram:
             keys["spectrogram_freqs"], keys["spectrogram_fps"] = bank["freqs"], fps

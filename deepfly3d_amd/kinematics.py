@@ -1,5 +1,5 @@
-"""`PoseChain`: the kinematic chain of one triangulated pose (DESIGN.md sections 14-17) -- body frame, joint angles, leg fit,
-unwrapping, wavelet spectrogram, behaviour map -- with every stage that the default arguments reach computed once.
+"""`PoseChain`: the kinematic chain of one triangulated pose (DESIGN.md sections 14-18) -- body frame, joint angles, leg fit,
+unwrapping, wavelet spectrogram, behaviour map and its segmentation -- with every stage that the default arguments reach computed once.
 
 A chain lives for one call of `Core`: each stage once per save, nothing kept between calls, because `camNet.points3d` changes under
 corrections and re-triangulation.  It keeps the small products (frame, fit, angles, the 48 series: a few KB per frame).  The
@@ -82,3 +82,8 @@ class PoseChain:
     def behaviour_map(self, perplexity=None, n_iter=None, max_points=None, seed=0, **spectrogram_kwargs):
         """ops.behaviour_map of the float64 spectrogram(**spectrogram_kwargs)."""
         return ops.behaviour_map(self.spectrogram(**spectrogram_kwargs), perplexity, n_iter, max_points, seed)
+
+    def behaviour_segments(self, grid=None, sigma=None, min_peak=None, **behaviour_map_kwargs):
+        """(the BehaviourMapResult, ops.segment_map of its embedding): one map, computed once, and its segmentation."""
+        m = self.behaviour_map(**behaviour_map_kwargs)
+        return m, ops.segment_map(m.embedding, grid, sigma, min_peak)

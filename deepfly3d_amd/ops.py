@@ -1,6 +1,6 @@
 """Thin host wrappers over the C ABI for the non-network kernels: arg-max and peaks, re-layout, triangulation, Procrustes and the
-video pose, and what DESIGN.md sections 9-17 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
-overlay, joint angles, the leg fit, wavelet spectrograms and behaviour maps.
+video pose, and what DESIGN.md sections 9-18 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
+overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps and their segmentation.
 
 Inputs/outputs are torch CUDA tensors (device memory + stream plumbing only); every computation is a
 libdf3d_hip.so kernel.  No CPU fallback: a missing library or GPU raises `_native.NativeLibraryError`.
@@ -853,6 +853,164 @@ def behaviour_map(S, perplexity=None, n_iter=None, max_points=None, seed=0):
         _bmap_call("df3d_bmap_place", c.data_ptr(), sel.numel(), N, Y.data_ptr(), out.data_ptr(), _stream(S))
         embedding[sel], beta[sel], info[sel] = out, b, i
     return BehaviourMapResult(embedding, train, beta, info, float(kl.item()), u)
+
+
+# ---- segmentation of the behaviour map -------------------------------------------------------------------------
+BehaviourSegmentsResult = collections.namedtuple("BehaviourSegmentsResult",
+                                                 "density origin sigma regions region_peaks labels bouts occupancy transitions")
+
+
+def _bseg_work(T, G, device):
+    need = _native.load().df3d_bseg_work_bytes(int(T), int(G))
+    if need <= 0:
+        raise ValueError(f"no workspace for T = {T} frames on a grid of {G}: grid must be in [2, 1024] and T at most 65 535 * 2 048")
+    return torch.empty((need,), dtype=torch.uint8, device=device), need
+
+
+def _need_map(Y):
+    if not (isinstance(Y, torch.Tensor) and Y.is_cuda and Y.dtype == torch.float64 and Y.dim() == 2 and Y.shape[1] == 2):
+        raise ValueError("Y must be a torch.float64 CUDA tensor of shape [T, 2]")
+    return Y.contiguous()
+
+
+def _need_grid(grid):
+    from . import config
+
+    lo, hi = config.BEHAVIOUR_GRID_RANGE
+    G = config.BEHAVIOUR_GRID if grid is None else grid
+    if isinstance(G, bool) or not isinstance(G, (int, np.integer)) or not lo <= G <= hi:
+        raise ValueError(f"grid must be an integer in [{lo}, {hi}] (it is {G!r})")
+    return int(G)
+
+
+def density_grid(lo, hi, grid=None, sigma=None):
+    """((x0, y0, h), sigma): the square grid of the model over a map whose valid rows span lo = (min x, min y) .. hi = (max x,
+    max y).  ext = max(hi - lo), c = (lo + hi) / 2, sigma = `sigma` or config.BEHAVIOUR_DENSITY_SIGMA_FRACTION ext, L = ext / 2 +
+    3 sigma, x0 = c_x - L, y0 = c_y - L, h = 2 L / grid.  ValueError: a sigma that is not finite and > 0 -- among them the default of
+    a map without extent."""
+    from . import config
+
+    G = _need_grid(grid)
+    lo, hi = (float(lo[0]), float(lo[1])), (float(hi[0]), float(hi[1]))
+    ext = max(hi[0] - lo[0], hi[1] - lo[1])
+    if sigma is None:
+        if not ext > 0.0:
+            raise ValueError("every valid frame of the map lies on one point, so the default sigma (a fraction of the map's extent) is 0: "
+                             "give sigma")
+        sigma = config.BEHAVIOUR_DENSITY_SIGMA_FRACTION * ext
+    sigma = float(sigma)
+    if not (np.isfinite(sigma) and sigma > 0.0):
+        raise ValueError(f"sigma must be finite and > 0 (it is {sigma:g})")
+    L = ext / 2.0 + 3.0 * sigma
+    x0, y0 = (lo[0] + hi[0]) / 2.0 - L, (lo[1] + hi[1]) / 2.0 - L
+    h = 2.0 * L / G
+    if not (np.isfinite(h) and h > 0.0 and np.isfinite(x0) and np.isfinite(y0)):
+        raise ValueError(f"the map's extent {ext:g} and sigma {sigma:g} leave no finite grid")
+    return (x0, y0, h), sigma
+
+
+@_on_tensor_device
+def map_density(Y, grid=None, sigma=None):
+    """(rho [G, G] float64, (x0, y0, h), sigma): the Gaussian density of the map Y [T, 2] (float64 cuda; a row with a non-finite
+    entry is not valid and contributes nothing) on the grid density_grid() lays over its valid rows: rho[r, q] = (M 2 pi sigma^2)^-1
+    sum_t exp(-|g_rq - Y[t]|^2 / (2 sigma^2)) with g_rq = (x0 + (q + 0.5) h, y0 + (r + 0.5) h), the exact sum over all M valid frames.
+    `grid`: G, default config.BEHAVIOUR_GRID.  The five bounds are read back.  ValueError: no valid row, and density_grid's."""
+    Y = _need_map(Y)
+    G = _need_grid(grid)
+    T = Y.shape[0]
+    bounds = torch.zeros((5,), dtype=torch.float64, device=Y.device)
+    _bmap_call("df3d_bseg_bounds", Y.data_ptr(), T, bounds.data_ptr(), _stream(Y))
+    b = bounds.cpu().tolist()
+    if T == 0 or b[4] < 1.0:
+        raise ValueError(f"the map holds no valid frame ({T} rows, each with a non-finite entry): there is nothing to take a density of")
+    origin, sigma = density_grid((b[0], b[2]), (b[1], b[3]), G, sigma)
+    rho = torch.empty((G, G), dtype=torch.float64, device=Y.device)
+    work, need = _bseg_work(T, G, Y.device)
+    _bmap_call("df3d_bseg_density", Y.data_ptr(), T, origin[0], origin[1], origin[2], G, sigma, rho.data_ptr(), work.data_ptr(), need, _stream(Y))
+    return rho, origin, sigma
+
+
+@_on_tensor_device
+def watershed(rho, min_peak=None):
+    """(regions [G, G] int32, root_cells [R] int32) of a density rho [G, G] (float64 cuda, finite, >= 0): every cell climbs to the
+    8-neighbour with the largest key (rho, -index) until none is larger (index = r G + q: among equal densities the smaller index
+    is the higher, so plateaux and an all-equal field are decided); the peaks with rho > 0 and rho >= min_peak max rho (default
+    config.BEHAVIOUR_MIN_PEAK, in [0, 1]) found the regions 1 .. R, numbered by rising index; a cell whose peak was dropped is 0.
+    `root_cells`: the peaks' indices.  R is read back."""
+    from . import config
+
+    rho = _need_f64(rho, (2,), "rho")
+    G = rho.shape[0]
+    if rho.shape != (G, G):
+        raise ValueError("rho must be square, [G, G]")
+    _need_grid(G)
+    min_peak = float(config.BEHAVIOUR_MIN_PEAK if min_peak is None else min_peak)
+    if not 0.0 <= min_peak <= 1.0:
+        raise ValueError(f"min_peak must be in [0, 1] (it is {min_peak:g})")
+    regions = torch.empty((G, G), dtype=torch.int32, device=rho.device)
+    roots = torch.empty((G * G,), dtype=torch.int32, device=rho.device)
+    count = torch.empty((1,), dtype=torch.int32, device=rho.device)
+    work, need = _bseg_work(0, G, rho.device)
+    _bmap_call("df3d_bseg_watershed", rho.data_ptr(), G, min_peak, regions.data_ptr(), count.data_ptr(), roots.data_ptr(), work.data_ptr(), need,
+               _stream(rho))
+    return regions, roots[: int(count.item())].clone()
+
+
+@_on_tensor_device
+def map_labels(Y, regions, origin):
+    """labels [T] int32: -1 for a row of Y [T, 2] with a non-finite entry, else regions[r, q] of the cell the frame lies in,
+    q = clamp(floor((Y[t, 0] - x0) / h), 0, G - 1) and r likewise from Y[t, 1] and y0; origin = (x0, y0, h)."""
+    Y = _need_map(Y)
+    if not (isinstance(regions, torch.Tensor) and regions.is_cuda and regions.dtype == torch.int32 and regions.dim() == 2
+            and regions.shape[0] == regions.shape[1] and regions.device == Y.device):
+        raise ValueError("regions must be a torch.int32 CUDA tensor of shape [G, G] on the device of Y")
+    G = _need_grid(regions.shape[0])
+    x0, y0, h = (float(v) for v in origin)
+    regions = regions.contiguous()
+    labels = torch.empty((Y.shape[0],), dtype=torch.int32, device=Y.device)
+    _bmap_call("df3d_bseg_labels", Y.data_ptr(), Y.shape[0], x0, y0, h, G, regions.data_ptr(), labels.data_ptr(), _stream(Y))
+    return labels
+
+
+@_on_tensor_device
+def ethogram(labels, num_regions):
+    """(bouts [B, 3] int64, occupancy [R + 1] int64, transitions [R + 1, R + 1] int64) of labels [T] (int32 cuda, -1 .. R =
+    num_regions): the maximal runs of equal labels as rows (label, start, length) -- runs of -1 and of 0 among them, their lengths
+    sum to T --, the frames of each label 0 .. R, and the counts of pairs (t, t + 1) whose labels are both >= 0 and differ.  B is
+    read back."""
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32 and labels.dim() == 1):
+        raise ValueError("labels must be a torch.int32 CUDA tensor of shape [T]")
+    R = int(num_regions)
+    if not 0 <= R <= 32767:
+        raise ValueError(f"num_regions must be in [0, 32767] (it is {R})")
+    labels = labels.contiguous()
+    T, dev = labels.shape[0], labels.device
+    occupancy = torch.zeros((R + 1,), dtype=torch.int64, device=dev)
+    transitions = torch.zeros((R + 1, R + 1), dtype=torch.int64, device=dev)
+    if T == 0:
+        return torch.zeros((0, 3), dtype=torch.int64, device=dev), occupancy, transitions
+    bouts = torch.empty((T, 3), dtype=torch.int64, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    work, need = _bseg_work(T, 2, dev)
+    _bmap_call("df3d_bseg_bouts", labels.data_ptr(), T, R, bouts.data_ptr(), count.data_ptr(), occupancy.data_ptr(), transitions.data_ptr(),
+               work.data_ptr(), need, _stream(labels))
+    return bouts[: int(count.item())].clone(), occupancy, transitions
+
+
+@_on_tensor_device
+def segment_map(Y, grid=None, sigma=None, min_peak=None):
+    """The segmentation of a behaviour map Y [T, 2] (float64 cuda), a BehaviourSegmentsResult: `density`
+    [G, G], `origin` (x0, y0, h) and `sigma` (map_density), `regions` [G, G] int32 (watershed), `region_peaks` [R, 2] float64 (the
+    map coordinates of the centres of the peaks' cells), `labels` [T] int32 (map_labels), and `bouts`, `occupancy`, `transitions`
+    (ethogram)."""
+    rho, origin, sigma = map_density(Y, grid, sigma)
+    regions, roots = watershed(rho, min_peak)
+    G = rho.shape[0]
+    r, q = torch.div(roots, G, rounding_mode="floor"), roots % G
+    peaks = torch.stack((origin[0] + (q.double() + 0.5) * origin[2], origin[1] + (r.double() + 0.5) * origin[2]), dim=1)
+    labels = map_labels(Y, regions, origin)
+    bouts, occupancy, transitions = ethogram(labels, roots.numel())
+    return BehaviourSegmentsResult(rho, origin, sigma, regions, peaks, labels, bouts, occupancy, transitions)
 
 
 def gaussian_window_taps(window_size, sigma, truncate=4.0):

@@ -374,6 +374,45 @@ int df3d_tsne_run(const double* P_dev, int N, double* Y_dev, double* V_dev, doub
                   void* work_dev, long long work_len_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a14 segmentation of the behaviour map (the model is this project's own specification, defined in float64
+ *     by tests/behaviour_segment_oracle.py).  All arrays are DEVICE arrays, row-major: float64, int32, and int64 for the ethogram.
+ *     No floating-point atomics and fixed-order sums: two calls on the same input give the same bits, on any machine.  A row of
+ *     Y [T, 2] is valid when both entries are finite.
+ * df3d_bseg_bounds: bounds[5] = min x, max x, min y, max y over the valid rows and their count M (a double; +-inf and 0 where
+ *     there is none).
+ * df3d_bseg_density: rho [G, G], rho[r, q] = (M 2 pi sigma^2)^-1 sum_valid t exp(-((gx_q - Y[t, 0])^2 + (gy_r - Y[t, 1])^2) / (2 sigma^2))
+ *     with gx_q = x0 + (q + 0.5) h and gy_r = y0 + (r + 0.5) h: the exact sum over every valid frame, computed as the separable
+ *     product on v_mfma_f64_16x16x4_f64 in slices of 2 048 frames that are added in index order.  All zeros where M = 0.
+ * df3d_bseg_watershed: cells are ordered by the key (rho, -index), index = r G + q; a cell points at the 8-neighbour with the
+ *     largest key if that key exceeds its own, else it is a root, and every cell's root is the end of its chain.  A root is kept
+ *     when rho > 0 and rho >= min_peak max rho; kept roots are numbered 1 .. R by rising index.  regions [G, G]: the number of the
+ *     cell's root, 0 where it was dropped.  num_regions[0] = R.  root_cells [G * G]: the kept roots' indices, then -1.  rho is
+ *     finite and >= 0.
+ * df3d_bseg_labels: labels [T] = -1 for an invalid row, else regions[r, q] with q = clamp(floor((Y[t, 0] - x0) / h), 0, G - 1) and r
+ *     likewise from Y[t, 1] and y0.
+ * df3d_bseg_bouts: the maximal runs of equal labels.  bouts [T, 3] int64: row b < B is (label, start, length), the rows from B on
+ *     are zero; num_bouts[0] = B; occupancy [R + 1] int64: the frames of label 0 .. R; transitions [R + 1, R + 1] int64: the pairs
+ *     (t, t + 1) whose labels are both in [0, R] and differ.  A label outside [-1, R] is counted in neither table.
+ * df3d_bseg_work_bytes(T, G): the bytes of the caller-owned workspace that serves every entry above at this T and G (0 where T or
+ *     G is out of range).
+ * DF3D_EINVAL before the device is touched, with a message that names the argument: G outside [2, 1 024]; T negative or above
+ *     65 535 * 2 048 (bounds, density) or 2^31 - 1 (labels, bouts); sigma, h, x0 or y0 not finite, sigma or h <= 0; min_peak outside
+ *     [0, 1]; num_regions outside [0, 32 767]; a null, misaligned (16 bytes for Y and work, 8 for float64 and int64, 4 for int32) or
+ *     overlapping buffer; a workspace below the query.  T = 0 launches nothing and returns DF3D_OK.  Every launching entry is
+ *     asynchronous on `stream`, allocates nothing and keeps no host pointer.
+ * ---------------------------------------------------------------------------------------------- */
+long long df3d_bseg_work_bytes(long long T, int G);
+int df3d_bseg_bounds(const double* Y_dev, long long T, double* bounds_dev, void* stream);
+int df3d_bseg_density(const double* Y_dev, long long T, double x0, double y0, double h, int G, double sigma, double* rho_dev, void* work_dev,
+                      long long work_len_bytes, void* stream);
+int df3d_bseg_watershed(const double* rho_dev, int G, double min_peak, int* regions_dev, int* num_regions_dev, int* root_cells_dev,
+                        void* work_dev, long long work_len_bytes, void* stream);
+int df3d_bseg_labels(const double* Y_dev, long long T, double x0, double y0, double h, int G, const int* regions_dev, int* labels_dev,
+                     void* stream);
+int df3d_bseg_bouts(const int* labels_dev, long long T, int num_regions, long long* bouts_dev, int* num_bouts_dev, long long* occupancy_dev,
+                    long long* transitions_dev, void* work_dev, long long work_len_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
