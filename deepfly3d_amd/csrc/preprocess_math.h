@@ -1,7 +1,8 @@
 // The arithmetic of the input front-end (uint8 camera frame -> one pixel of the network input), shared by
 // preprocess_kernel (csrc/preprocess.hip) and by the stem kernels when they sample the camera frames themselves
 // (df3d_hg_forward_u8): optional left-right flip, down-scale, grey -> 3 channels, (v / 255 - mean) * (1 / std).
-// Multiply-add fusion is off inside, so both users round identically (and like the numpy oracle).
+// Multiply-add fusion is off inside, so both users round identically (and like the numpy oracle).  The pragma below does that only
+// in a file built with -ffp-contract=fast-honor-pragmas (build.py FILE_FLAGS): a plain -ffp-contract=fast disregards it.
 //
 // df2d's resize rule is not in the reference checkout, so it is DATA (Norm::resize, DF3D_RESIZE_* of df3d_hip.h):
 //   0  bilinear, half-pixel centres, no antialias   (cv2.INTER_LINEAR / torch interpolate(align_corners=False))

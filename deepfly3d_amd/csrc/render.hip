@@ -219,6 +219,7 @@ extern "C" {
 int df3d_render_pose2d_grid(const unsigned char* luma_dev, int height, int width, const double* points_px_dev, int num_joints, const int* bones_host,
                             int num_bones, const unsigned char* joint_rgb_host, double radius, double line_width, unsigned char* out_rgb_dev, void* stream) {
     DF3D_CHECK_ARG(luma_dev && points_px_dev && out_rgb_dev && height > 0 && width > 0 && radius >= 0 && line_width >= 0, "null pointer or empty image");
+    DF3D_CHECK_ARG(height <= 65535 && (long long)width * 3 <= 0x7fffffffll, "image too large: at most 65535 rows and 2^31 - 1 columns in the grid");
     Skeleton sk;
     if (int rc = fill_skeleton(sk, num_joints, bones_host, num_bones, joint_rgb_host)) return rc;
     hipLaunchKernelGGL(render_pose2d_kernel, dim3((width + 255) / 256, height, 6), dim3(256), 0, df3d::as_stream(stream), luma_dev, height, width,
@@ -231,6 +232,7 @@ int df3d_render_pose3d_panels(const double* points3d_dev, int num_joints, const 
                               const double* azimuth_deg3, double elevation_deg, double lim, int size, double line_width, unsigned char* out_rgb_dev,
                               void* stream) {
     DF3D_CHECK_ARG(points3d_dev && azimuth_deg3 && out_rgb_dev && lim > 0 && size > 1 && line_width >= 0, "null pointer or bad panel geometry");
+    DF3D_CHECK_ARG(size <= 65535, "panel too large: at most 65535 rows");
     Skeleton sk;
     if (int rc = fill_skeleton(sk, num_joints, bones_host, num_bones, joint_rgb_host)) return rc;
     const double k = 3.14159265358979323846 / 180.0;
@@ -250,6 +252,7 @@ int df3d_render_pose3d_panels(const double* points3d_dev, int num_joints, const 
 int df3d_resize_rgb(const unsigned char* in_dev, int in_h, int in_w, int in_pitch_px, unsigned char* out_dev, int out_h, int out_w, int out_pitch_px,
                     void* stream) {
     DF3D_CHECK_ARG(in_dev && out_dev && in_h > 0 && in_w > 0 && out_h > 0 && out_w > 0 && in_pitch_px >= in_w && out_pitch_px >= out_w, "null pointer or bad size");
+    DF3D_CHECK_ARG(out_h <= 65535, "image too large: at most 65535 output rows");
     hipLaunchKernelGGL(resize_rgb_kernel, dim3((out_w + 255) / 256, out_h), dim3(256), 0, df3d::as_stream(stream), in_dev, in_h, in_w, in_pitch_px, out_dev,
                        out_h, out_w, out_pitch_px);
     DF3D_LAUNCH_CHECK();

@@ -65,6 +65,8 @@ class FrameRenderer:
         _native.require_gpu()
         self.lib = _native.load()
         self.dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        if self.dev.type == "cuda" and self.dev.index is None:   # "cuda": the current device, by its index (tensors carry one)
+            self.dev = torch.device("cuda", torch.cuda.current_device())
         self.h, self.w, self.j = height, width, num_joints
         self.bones, self.rgb = _tables(num_joints)
         self._bones_p = self.bones.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
@@ -73,10 +75,34 @@ class FrameRenderer:
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
 
+    def _need(self, t, dtype, shape, name):
+        """The C ABI reads `t` from its data pointer alone: type, device, shape and layout are settled here."""
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dtype} CUDA tensor")
+        if t.device != self.dev:
+            raise ValueError(f"{name} lives on {t.device}, the renderer on {self.dev}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+
+    def _need_rows(self, t, name):
+        """[h, w, 3] uint8 with packed pixels; rows may lie apart by a whole number of pixels (a view of a wider or taller image)."""
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3):
+            raise ValueError(f"{name} must be a [h, w, 3] {torch.uint8} CUDA tensor")
+        if t.device != self.dev:
+            raise ValueError(f"{name} lives on {t.device}, the renderer on {self.dev}")
+        if t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name} must not be empty, got {list(t.shape)}")
+        if t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) % 3 != 0 or t.stride(0) < 3 * t.shape[1]:
+            raise ValueError(f"{name} must have packed RGB pixels and a row pitch of whole pixels, at least its width; strides {t.stride()}")
+
     def grid2d(self, luma6, points6, out=None):
         """luma6 [6, H, W] uint8 cuda, points6 [6, J, 2] float64 cuda (row_px, col_px) -> [2 H, 3 W, 3] uint8 cuda."""
+        self._need(luma6, torch.uint8, (6, self.h, self.w), "luma6")
+        self._need(points6, torch.float64, (6, self.j, 2), "points6")
         if out is None:
             out = torch.empty((2 * self.h, 3 * self.w, 3), dtype=torch.uint8, device=self.dev)
+        else:
+            self._need(out, torch.uint8, (2 * self.h, 3 * self.w, 3), "out")
         with torch.cuda.device(self.dev):
             _native.check(self.lib.df3d_render_pose2d_grid(luma6.data_ptr(), self.h, self.w, points6.data_ptr(), self.j, self._bones_p, len(self.bones),
                                                            self._rgb_p, JOINT_RADIUS, BONE_WIDTH, out.data_ptr(), self._stream()), "df3d_render_pose2d_grid")
@@ -84,8 +110,11 @@ class FrameRenderer:
 
     def panels3d(self, points3d, out=None, size=PANEL_SIZE):
         """points3d [J, 3] float64 cuda -> [size, 3 size, 3] uint8 cuda."""
+        self._need(points3d, torch.float64, (self.j, 3), "points3d")
         if out is None:
             out = torch.empty((size, 3 * size, 3), dtype=torch.uint8, device=self.dev)
+        else:
+            self._need(out, torch.uint8, (size, 3 * size, 3), "out")
         az = (ctypes.c_double * 3)(*panel_azimuths())
         with torch.cuda.device(self.dev):
             _native.check(self.lib.df3d_render_pose3d_panels(points3d.data_ptr(), self.j, self._bones_p, len(self.bones), self._rgb_p, az, PANEL_ELEV,
@@ -94,7 +123,8 @@ class FrameRenderer:
 
     def resize(self, img, out):
         """img [h, w, 3] uint8 cuda -> out (a [oh, ow, 3] view of a wider image is fine: row pitch taken from its stride)."""
-        assert img.stride(1) == 3 and out.stride(1) == 3 and img.stride(2) == 1 and out.stride(2) == 1
+        self._need_rows(img, "img")
+        self._need_rows(out, "out")
         with torch.cuda.device(self.dev):
             _native.check(self.lib.df3d_resize_rgb(img.data_ptr(), img.shape[0], img.shape[1], img.stride(0) // 3, out.data_ptr(), out.shape[0], out.shape[1],
                                                    out.stride(0) // 3, self._stream()), "df3d_resize_rgb")

@@ -651,6 +651,7 @@ int df3d_hg_forward_upto(df3d_hg* h, const float* images_dev, int n, int upto, f
  *     panels [size, 3 size, 3] uint8, orthographic views from azimuth_deg3[k] / elevation_deg (matplotlib's view_init angles,
  *     reference df3d/plot_util.py:48-51), +-lim mapped onto the panel, black background.
  * df3d_resize_rgb: bilinear, pixel centres at half integers (cv2.INTER_LINEAR's geometry); pitches in pixels.
+ * Rows go on the launch grid's y axis: height, size and out_h are at most 65535 (DF3D_EINVAL beyond, nothing launched).
  * All asynchronous on `stream`. */
 int df3d_render_pose2d_grid(const unsigned char* luma_dev, int height, int width, const double* points_px_dev, int num_joints,
                             const int* bones_host, int num_bones, const unsigned char* joint_rgb_host, double radius, double line_width,

@@ -18,24 +18,37 @@ def _seg_dist2(px, py, ax, ay, bx, by):
     return (px - qx) * (px - qx) + (py - qy) * (py - qy)
 
 
+def pose2d_masks(H, W, pts, bones, radius, line_width):
+    """One camera slot's drawing as masks, in drawing order: ([(bone index, [H, W] bool)], [(joint, [H, W] bool)]) of the bones and joints
+    that are drawn at all (both ends seen / seen).  pts [J, 2] (row, col).  A non-finite coordinate gives an empty mask: every
+    comparison with a NaN is false, as on the device."""
+    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    hw2, rad2 = (0.5 * line_width) ** 2, float(radius) ** 2
+    pts = np.asarray(pts, np.float64)
+    seen = (pts[:, 0] != 0.0) & (pts[:, 1] != 0.0)
+    bone_masks, joint_masks = [], []
+    with np.errstate(invalid="ignore", over="ignore"):   # inf - inf, 1e300 ** 2: the NaN and inf are the rule's, not a fault
+        for k, (a, b) in enumerate(bones):
+            if seen[a] and seen[b]:
+                bone_masks.append((k, _seg_dist2(xx, yy, pts[a, 1], pts[a, 0], pts[b, 1], pts[b, 0]) <= hw2))
+        for j in range(len(pts)):
+            if seen[j]:
+                dx, dy = xx - pts[j, 1], yy - pts[j, 0]
+                joint_masks.append((j, dx * dx + dy * dy <= rad2))
+    return bone_masks, joint_masks
+
+
 def pose2d_grid(luma, points_px, bones, joint_rgb, radius, line_width):
     """luma [6, H, W] uint8, points_px [6, J, 2] (row, col) -> [2 H, 3 W, 3] uint8."""
     _, H, W = luma.shape
     out = np.zeros((2 * H, 3 * W, 3), np.uint8)
-    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
-    hw2, rad2 = (0.5 * line_width) ** 2, float(radius) ** 2
     for slot in range(6):
         img = np.repeat(luma[slot][:, :, None], 3, axis=2).copy()
-        pts = np.asarray(points_px[slot], np.float64)
-        seen = (pts[:, 0] != 0.0) & (pts[:, 1] != 0.0)
-        for a, b in bones:
-            if seen[a] and seen[b]:
-                hit = _seg_dist2(xx, yy, pts[a, 1], pts[a, 0], pts[b, 1], pts[b, 0]) <= hw2
-                img[hit] = joint_rgb[a]
-        for j in range(len(pts)):
-            if seen[j]:
-                dx, dy = xx - pts[j, 1], yy - pts[j, 0]
-                img[dx * dx + dy * dy <= rad2] = joint_rgb[j]
+        bone_masks, joint_masks = pose2d_masks(H, W, points_px[slot], bones, radius, line_width)
+        for k, hit in bone_masks:
+            img[hit] = joint_rgb[bones[k][0]]
+        for j, hit in joint_masks:
+            img[hit] = joint_rgb[j]
         r, c = divmod(slot, 3)
         out[r * H:(r + 1) * H, c * W:(c + 1) * W] = img
     return out
@@ -56,14 +69,16 @@ def pose3d_panels(points3d, bones, joint_rgb, azimuth_deg3, elevation_deg, lim, 
         sx = (u / lim * 0.5 + 0.5) * float(size - 1)
         sy = (0.5 - v / lim * 0.5) * float(size - 1)
         img = np.zeros((size, size, 3), np.uint8)
-        for a, b in bones:
-            img[_seg_dist2(xx, yy, sx[a], sy[a], sx[b], sy[b]) <= hw2] = joint_rgb[a]
+        with np.errstate(invalid="ignore", over="ignore"):   # a NaN joint draws nothing, as on the device
+            for a, b in bones:
+                img[_seg_dist2(xx, yy, sx[a], sy[a], sx[b], sy[b]) <= hw2] = joint_rgb[a]
         out[:, panel * size:(panel + 1) * size] = img
     return out
 
 
-def resize_rgb(img, out_h, out_w):
-    """bilinear, pixel centres at half integers, clamped; round half up."""
+def resize_rgb(img, out_h, out_w, unrounded=False):
+    """bilinear, pixel centres at half integers, clamped; round half up.  `unrounded=True`: the float64 values before the rounding
+    (a test reads from them how many pixels sit exactly on a half)."""
     ih, iw = img.shape[:2]
     fy = (np.arange(out_h, dtype=np.float64) + 0.5) * float(ih) / float(out_h) - 0.5
     fx = (np.arange(out_w, dtype=np.float64) + 0.5) * float(iw) / float(out_w) - 0.5
@@ -75,4 +90,5 @@ def resize_rgb(img, out_h, out_w):
     v00, v01, v10, v11 = f[y0][:, x0], f[y0][:, x1], f[y1][:, x0], f[y1][:, x1]
     top = v00 + wx * (v01 - v00)
     bot = v10 + wx * (v11 - v10)
-    return np.floor(top + wy * (bot - top) + 0.5).astype(np.uint8)
+    v = top + wy * (bot - top)
+    return v if unrounded else np.floor(v + 0.5).astype(np.uint8)

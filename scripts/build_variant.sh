@@ -31,7 +31,7 @@ for f in deepfly3d_amd/csrc/*.hip; do
   [ -f deepfly3d_amd/csrc/_obj/$b.o ] || { echo "run python -m deepfly3d_amd.build first"; exit 1; }
   objs="$objs deepfly3d_amd/csrc/_obj/$b.o"
 done
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -ffp-contract=fast "$@" -Iinclude -c deepfly3d_amd/csrc/hourglass.hip -o scratch/variants/hourglass_$name.o
+/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -ffp-contract=fast-honor-pragmas "$@" -Iinclude -c deepfly3d_amd/csrc/hourglass.hip -o scratch/variants/hourglass_$name.o
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o scratch/variants/libdf3d_hip_$name.so $objs scratch/variants/hourglass_$name.o
 rm -f scratch/variants/hourglass_$name.o
 echo scratch/variants/libdf3d_hip_$name.so

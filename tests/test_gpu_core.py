@@ -212,7 +212,8 @@ def test_inference_folder_plumbing(native_lib, cuda, tmp_path, golden_dir, monke
 
 
 def test_preprocess_kernel_against_torch(native_lib, cuda):
-    """Front-end kernel vs a torch restatement: bilinear (half-pixel centres, no antialias) + flip + normalise."""
+    """Front-end kernel vs a torch restatement: bilinear (half-pixel centres, no antialias) + flip + normalise.
+    (The camera size only; other frame and output shapes, up-scales among them: tests/test_gpu_frontend_sweep.py.)"""
     from deepfly3d_amd import inference
 
     img = torch.randint(0, 256, (3, 480, 960), dtype=torch.uint8, generator=torch.Generator().manual_seed(2))
@@ -231,7 +232,9 @@ def test_every_resize_rule_against_its_restatement(native_lib, cuda, rule):
     """df2d's resize rule is data (inference.PREPROCESS["resize"]): each candidate against oracle/preprocess.py (torch
     interpolate for the two bilinear forms, overlap-weight matrices in float64 for cv2.INTER_AREA's definition), grey and
     colour frames, flipped and not, the camera size and an odd one; and the network fed with the frames themselves
-    (df3d_hg_forward_u8) equals preprocess + forward bit for bit under every rule."""
+    (df3d_hg_forward_u8) equals preprocess + forward bit for bit under every rule.
+    (One network input size, down-scales, the f32 engine: tests/test_gpu_frontend_sweep.py runs every rule over up-scales, 1 x 1 frames
+    and outputs, identity sizes, seven views with a flip table, and on engines of other input sizes in all four dtypes.)"""
     from deepfly3d_amd import inference
     from deepfly3d_amd.hourglass import HourglassEngine
     from deepfly3d_amd.synthetic import synthetic_state_dict
@@ -395,7 +398,9 @@ def test_full_size_workload_properties(native_lib, cuda, golden_dir, dtype):
 @pytest.mark.parametrize("dtype", ["f32", "bf16", "f16", "f32s"])
 def test_forward_from_camera_frames_equals_preprocess_then_forward(native_lib, cuda, dtype):
     """df3d_hg_forward_u8 (the stem samples the uint8 frames itself) is bit for bit df3d_hg_forward(df3d_preprocess_u8(frames)):
-    grey and 3-channel frames, flipped and not, a frame size that is not a multiple of the network input, non-trivial mean / std."""
+    grey and 3-channel frames, flipped and not, a frame size that is not a multiple of the network input, non-trivial mean / std.
+    (The 256 x 512 engine and `bilinear`: tests/test_gpu_frontend_sweep.py runs the three stems under every rule on 64 x 64, 128 x 64 and
+    64 x 192 engines, with one tile per workgroup and with workgroups that prefetch a next tile.)"""
     from deepfly3d_amd import inference
     from deepfly3d_amd.hourglass import HourglassEngine
     from deepfly3d_amd.synthetic import synthetic_state_dict

@@ -2,7 +2,12 @@
 
 The frames are drawn on the device; oracle/render.py restates the drawing rule in numpy and must agree bit for bit.  The encoder side
 (ffmpeg when present, else Motion-JPEG in AVI) is exercised through the real `df3d-cli --video-2d --video-3d` run on the reference's
-sample images."""
+sample images.
+
+This file holds the PRODUCT's case: 480 x 960 frames, 38 joints, the product skeleton and colours, a 200-pixel panel, one resize.  The
+same three kernels over other sizes (around the 256-pixel x tile), the 64-joint and 96-bone table limits, radius and line width 0,
+unseen / coincident / off-image / non-finite joints, pitched views, guard bytes, side streams, the argument checks and FrameRenderer's
+input checks are in tests/test_gpu_render_sweep.py; the oracle itself is checked in tests/test_render_oracle_host.py."""
 import os
 import pickle
 import shutil
