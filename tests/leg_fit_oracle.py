@@ -2,7 +2,7 @@
 method on the product of four unit spheres that fits a chain of fixed segment lengths to the measured joints of a leg.  The model is
 this project's own specification; this module defines it.  `basis_variant=True` builds every tangent basis from the coordinate axis
 AFTER the largest component of the direction instead of the axis of the smallest one: the same model on another arithmetic path,
-which measures how far the converged answer depends on rounding.  `replay` is the closed form of max_iter = 0, `witness_fit` an
+which measures how far the converged answer depends on rounding.  `fit_leg(trace=[])` records every pass.  `replay` is the closed form of max_iter = 0, `witness_fit` an
 independent scipy fit of the same cost in spherical angles."""
 import numpy as np
 
@@ -104,8 +104,10 @@ def cholesky_solve(A, b):
     return x
 
 
-def fit_leg(P, lengths, anchor=None, max_iter=MAX_ITER, basis_variant=False):
-    """(points [5, 3], cost, status, iterations) of one leg: joints P [5, 3], fixed lengths [4], anchor [3] or None."""
+def fit_leg(P, lengths, anchor=None, max_iter=MAX_ITER, basis_variant=False, trace=None):
+    """(points [5, 3], cost, status, iterations) of one leg: joints P [5, 3], fixed lengths [4], anchor [3] or None.  A list given as
+    `trace` receives one record per pass (one trial): (lam, pivot failed, accepted, small, max |delta|); where the pivot failed `small` is
+    False and max |delta| NaN.  The trace only listens: the results are the same bits with and without it."""
     P = np.asarray(P, dtype=np.float64)
     lengths = np.asarray(lengths, dtype=np.float64)
     st = start(P, anchor)
@@ -130,16 +132,22 @@ def fit_leg(P, lengths, anchor=None, max_iter=MAX_ITER, basis_variant=False):
                 D[2 * i:2 * i + 2] = lengths[i] * lengths[i] * (4 - i)
             while True:
                 delta = cholesky_solve(H + lam * np.diag(D), -g)
+                accepted = small = False
+                step = np.nan
                 if delta is not None:
                     trial = np.stack([d[i] + B[i] @ delta[2 * i:2 * i + 2] for i in range(4)])
                     trial = trial / np.sqrt((trial * trial).sum(axis=1))[:, None]
                     small = bool(np.all(np.abs(delta) <= TOL))
+                    step = float(np.abs(delta).max()) if trace is not None else np.nan
                     # the slack: E is a sum of twelve squares, good to ~1e-15 relative.  A plain E' < E fails by rounding on a
                     # last step of ~3e-9, the damping then grows until the step shrinks under TOL, and the leg "converges" 1e-9 mm
                     # short; which legs do depends on the arithmetic path (basis_variant moved the answer by 1.1e-9 mm, with the
                     # slack by 9e-16), and the iteration counts are the same
-                    if small or cost(trial, lengths, t) <= E * (1.0 + SLACK):
-                        break
+                    accepted = small or cost(trial, lengths, t) <= E * (1.0 + SLACK)
+                if trace is not None:
+                    trace.append((lam, delta is None, accepted, small, step))
+                if accepted:
+                    break
                 lam = max(10.0 * lam, LAMBDA_MIN)
                 if lam > LAMBDA_MAX:
                     status = STALLED
