@@ -115,6 +115,13 @@ PROTOTYPES = {
     "df3d_bseg_watershed": (c_int, [c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "df3d_bseg_labels": (c_int, [c_void_p, c_longlong, c_double, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "df3d_bseg_bouts": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_gait_work_bytes": (c_longlong, [c_longlong]),
+    "df3d_gait_velocity": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "df3d_gait_states": (c_int, [c_void_p, c_longlong, c_double, c_double, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_gait_steps": (c_int, [c_void_p, c_void_p, c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_gait_phase": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_gait_coupling": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_gait_patterns": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_eval": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_colsq": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_matvec": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

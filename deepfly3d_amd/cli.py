@@ -96,7 +96,32 @@ def parse_cli_args(argv=None):
                    help="With --behaviour-segments: the deviation of the density's Gaussians in the map's units (default 1/32 of the map's extent)")
     p.add_argument("--behaviour-grid", dest="behaviour_grid", type=int, default=None, metavar="G",
                    help="With --behaviour-segments: the cells per side of the density's grid, 2 to 1024 (default 256)")
+    p.add_argument("--gait", dest="gait", action="store_true",
+                   help="Analyse the gait from the leg tips and append, after every other key, gait_tip_position and gait_tip_velocity [T, 6, 3] "
+                        "(every tip relative to its body-coxa joint and its velocity, in leg coordinates), gait_states [T, 6] (int8: -1 unknown, "
+                        "0 stance, 1 swing, by hysteresis on the tip's anterior velocity), gait_steps [S, 4] (leg, lift-off, touch-down, next "
+                        "lift-off), gait_step_metrics [S, 3] (swing duration, stance duration, stride), gait_phase [T, 6], gait_coupling [6, 6, 2] "
+                        "and gait_coupling_count [6, 6], gait_pattern [T] (the mask of the legs in swing; 21 and 42 are the tripods), "
+                        "gait_pattern_histogram [64], gait_state_counts [6, 3], gait_thresholds and gait_fps to the result; together with "
+                        "--rigid-legs also the same thirteen with _rigid appended.  Works with --skip-pose-estimation on an earlier result")
+    p.add_argument("--gait-on", dest="gait_on", type=float, default=None, metavar="V",
+                   help="With --gait: the anterior tip velocity above which a leg goes into swing, in pose units (mm) per second (default 5, a "
+                        "guess from published tip speeds that nobody has measured on a recording)")
+    p.add_argument("--gait-off", dest="gait_off", type=float, default=None, metavar="V",
+                   help="With --gait: the anterior tip velocity below which a leg goes into stance (default 0, a guess like --gait-on); it must "
+                        "lie below --gait-on")
     args = p.parse_args(argv)
+    if args.gait_on is not None and not args.gait:
+        p.error("--gait-on sets the swing threshold of --gait: it needs --gait")
+    if args.gait_off is not None and not args.gait:
+        p.error("--gait-off sets the stance threshold of --gait: it needs --gait")
+    if args.gait:
+        from . import ops
+
+        try:
+            ops.gait_thresholds(args.gait_on, args.gait_off)
+        except ValueError as e:
+            p.error(f"--gait-on and --gait-off: {e}")
     if args.behaviour_segments and not args.behaviour_map:
         p.error("--behaviour-segments segments the map of --behaviour-map: it needs --behaviour-map")
     if args.behaviour_sigma is not None and not args.behaviour_segments:
@@ -150,12 +175,14 @@ _NO_IMAGES = ("--video-heatmap draws the heat-maps the network computes from the
 
 def run(args):
     video_heatmap = getattr(args, "video_heatmap", False)
-    # what the second save appends to the result: the four kinematics flags, in the order of their keys, and the map's perplexity
-    extras = {name: getattr(args, name, False) for name in ("joint_angles", "rigid_legs", "angle_spectrogram", "behaviour_map")}
+    # what the second save appends to the result: the kinematics flags, in the order of their keys, and the map's perplexity
+    extras = {name: getattr(args, name, False) for name in ("joint_angles", "rigid_legs", "angle_spectrogram", "behaviour_map", "gait")}
     flagged = [name for name, on in extras.items() if on]
     extras["behaviour_perplexity"] = getattr(args, "behaviour_perplexity", None)
     if getattr(args, "behaviour_segments", False):   # the map's segmentation: no keys of its own flag without --behaviour-map
         extras.update(behaviour_segments=True, behaviour_sigma=getattr(args, "behaviour_sigma", None), behaviour_grid=getattr(args, "behaviour_grid", None))
+    if extras["gait"]:
+        extras.update(gait_on=getattr(args, "gait_on", None), gait_off=getattr(args, "gait_off", None))
     if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not flagged:
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0

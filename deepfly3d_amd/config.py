@@ -110,6 +110,17 @@ BEHAVIOUR_GRID_RANGE = (2, 1024)
 BEHAVIOUR_DENSITY_SIGMA_FRACTION = 1.0 / 32.0
 BEHAVIOUR_MIN_PEAK = 0.01
 
+# ---- gait analysis of the leg tips.  A tip's velocity is the central difference over GAIT_DIFF_HALF frames
+# to either side (clipped at the recording's ends; within GAIT_DIFF_HALF_RANGE).  A leg goes into swing when its anterior velocity
+# rises above GAIT_SWING_ON and into stance when it falls below GAIT_SWING_OFF, in pose units (mm) per second; in between it keeps
+# its state.  The two defaults are a guess from published tip speeds of walking flies: nobody has measured them on a real recording.
+# GAIT_TRIPODS: the swing masks (bit L = leg L) of the two tripods, legs 0, 2, 4 and legs 1, 3, 5.
+GAIT_DIFF_HALF = 2
+GAIT_DIFF_HALF_RANGE = (1, 64)
+GAIT_SWING_ON = 5.0
+GAIT_SWING_OFF = 0.0
+GAIT_TRIPODS = (21, 42)
+
 # ---- which camera sees which joint (reference df3d/skeleton_fly.py:202-250), by camera id: cameras 0-2 look at the side whose
 # joints are 0..18, cameras 4-6 at the side of joints 19..37, camera 3 faces the fly.  Pinned by tests/golden/skeleton_tables.npz.
 # Where df3d::relayout_source (csrc/geometry_dev.h) fills a joint of a side camera under the identity ordering, this table sees it;

@@ -12,6 +12,7 @@ The GUI itself is out of scope; the methods it drives a
 (`nearest_joint`, `move_joint`, `write_corrections`, `check_cameras`, `smooth_points2d`).  The error navigation (`next_error`,
 `prev_error`, `next_error_in_range`, `joint_has_error`, `get_joint_reprojection_error`) runs on the device.
 """
+import dataclasses
 import glob
 import os
 import pickle
@@ -446,6 +447,40 @@ class Core:
                                                                       max_points=max_points, seed=seed, body_frame=body_frame, unwrap=unwrap, **bank)
         return ops.BehaviourSegmentsResult(*(t.cpu().numpy() if isinstance(t, torch.Tensor) else t for t in s))
 
+    _GAIT_KEYS = ("gait_tip_position", "gait_tip_velocity", "gait_states", "gait_steps", "gait_step_metrics", "gait_phase", "gait_coupling",
+                  "gait_coupling_count", "gait_pattern", "gait_pattern_histogram", "gait_state_counts", "gait_thresholds", "gait_fps")
+
+    def _gait_fps(self, fps):
+        """angle_spectrogram's rule: `fps`, else get_fps(), else config.SPECTROGRAM_FPS."""
+        if fps is None:
+            fps = self.get_fps()
+        return float(SPECTROGRAM_FPS if fps is None else fps)
+
+    def gait(self, rigid=False, fps=None, on=None, off=None, half_window=None):
+        """The gait analysis (ops.gait) of the triangulation `camNet.points3d` in the recording's body frame, an
+        ops.GaitResult of numpy arrays: tip and vel [T, 6, 3] (every leg's tip relative to its body-coxa joint and its velocity, in
+        leg coordinates), states [T, 6] int32 (-1 unknown, 0 stance, 1 swing), steps [S, 4] int64 (leg, lift-off, touch-down, next
+        lift-off) and step_metrics [S, 3] (swing duration, stance duration, stride), phase [T, 6], coupling [6, 6, 2] and
+        coupling_count [6, 6], pattern [T] int32 (the mask of the legs in swing; config.GAIT_TRIPODS), pattern_histogram [64],
+        state_counts [6, 3], thresholds (on, off, half_window) and fps.  `fps`: None means get_fps(), and where that is None
+        config.SPECTROGRAM_FPS.  `on`, `off`: the swing thresholds on the tip's anterior velocity, config.GAIT_SWING_ON and
+        GAIT_SWING_OFF by default -- a guess nobody has measured on a recording; `half_window`: config.GAIT_DIFF_HALF.  `rigid=True`:
+        of the constant-length pose rigid_legs() fits, in the recording frame of the measured pose.  A rank-0 method with
+        joint_angles' refusals."""
+        thresholds = dict(zip(("on", "off", "half_window"), ops.gait_thresholds(on, off, half_window)))   # refused before any work
+        chain = self._measured_pose("gait", ops._gait_fps(self._gait_fps(fps)))
+        g = (chain.rigid() if rigid else chain).gait(**thresholds)
+        values = (getattr(g, f.name) for f in dataclasses.fields(g))
+        return ops.GaitResult(*(v.cpu().numpy() if isinstance(v, torch.Tensor) else v for v in values))
+
+    @staticmethod
+    def _gait_values(g):
+        """The values of _GAIT_KEYS from a GaitResult of device tensors."""
+        host = lambda t: t.cpu().numpy()   # noqa: E731
+        return (host(g.tip), host(g.vel), host(g.states).astype(np.int8), host(g.steps), host(g.step_metrics), host(g.phase), host(g.coupling),
+                host(g.coupling_count), host(g.pattern), host(g.pattern_histogram), host(g.state_counts), np.array(g.thresholds, dtype=np.float64),
+                g.fps)
+
     # -- manual corrections (DESIGN.md section 11; reference df3d/core.py:253-296, 477-479, 509-544) ---------------------------------
     _MOVE_THRESHOLD = 30   # pixels, per coordinate: a pose that differs less from the estimate on every checked joint is not stored
 
@@ -605,7 +640,7 @@ class Core:
         return None if full is None else full.cpu().numpy()
 
     def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False, behaviour_perplexity=None,
-             behaviour_segments=False, behaviour_sigma=None, behaviour_grid=None):
+             behaviour_segments=False, behaviour_sigma=None, behaviour_grid=None, gait=False, gait_on=None, gait_off=None):
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
         keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras).
         `rigid_legs=True` appends, after those, "points3d_rigid", "rigid_segment_lengths" and "rigid_fit_cost" (Core.rigid_legs()) and,
@@ -619,7 +654,12 @@ class Core:
         (ops.segment_map with `behaviour_sigma` and `behaviour_grid`): "behaviour_density" [G, G], "behaviour_density_origin" (x0, y0, h),
         "behaviour_density_sigma", "behaviour_regions" [G, G] int32, "behaviour_region_peaks" [R, 2], "behaviour_labels" [T] int32,
         "behaviour_bouts" [B, 3], "behaviour_occupancy" and "behaviour_transitions" and, together with rigid_legs, the same nine with
-        "_rigid" appended."""
+        "_rigid" appended.  `gait=True` appends, after every other key, the gait analysis of this save's triangulation (Core.gait() with
+        its defaults and the swing thresholds `gait_on` and `gait_off`): "gait_tip_position" and "gait_tip_velocity" [T, 6, 3],
+        "gait_states" [T, 6] int8, "gait_steps" [S, 4], "gait_step_metrics" [S, 3], "gait_phase" [T, 6], "gait_coupling" [6, 6, 2],
+        "gait_coupling_count" [6, 6], "gait_pattern" [T] int32, "gait_pattern_histogram" [64], "gait_state_counts" [6, 3],
+        "gait_thresholds" (on, off, half_window) and "gait_fps" and, together with rigid_legs, the same thirteen with "_rigid" appended
+        (of the fit this save computed, in the measured pose's recording frame)."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
@@ -630,6 +670,9 @@ class Core:
             raise ValueError("behaviour_segments segments the map behaviour_map computes: it needs behaviour_map=True")
         if (behaviour_sigma is not None or behaviour_grid is not None) and not behaviour_segments:
             raise ValueError("behaviour_sigma and behaviour_grid belong to behaviour_segments: they need behaviour_segments=True")
+        if (gait_on is not None or gait_off is not None) and not gait:
+            raise ValueError("gait_on and gait_off belong to gait: they need gait=True")
+        gait = dict(zip(("on", "off", "half_window"), ops.gait_thresholds(gait_on, gait_off))) if gait else None   # refused before any work
         segments = (behaviour_sigma, behaviour_grid) if behaviour_segments else None
         if segments is not None:   # refused before any work
             if behaviour_grid is not None:
@@ -638,13 +681,13 @@ class Core:
                 raise ValueError(f"behaviour_sigma must be finite and > 0 (it is {behaviour_sigma:g})")
         if self.is_primary:
             try:
-                self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments)
+                self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
     def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False,
-                      behaviour_perplexity=None, segments=None):
+                      behaviour_perplexity=None, segments=None, gait=None):
         if behaviour_map and getattr(self, "num_images", None) is not None:   # too short for the perplexity: refused before any work
             ops.behaviour_map_points(self.num_images, behaviour_perplexity)
         result = {"points2d": np.copy(self.points2d)}
@@ -665,8 +708,8 @@ class Core:
             result["points2d_argmax"] = np.copy(self.points2d_argmax)
         if getattr(self, "_subpixel", False):   # only when this run refined its detections: without it the schema is the reference's
             result["subpixel"] = True
-        if joint_angles or rigid_legs or angle_spectrogram or behaviour_map:   # opt-in, like the two keys above: else the reference's schema
-            result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments))
+        if joint_angles or rigid_legs or angle_spectrogram or behaviour_map or gait:   # opt-in, like the two keys above: else the reference's schema
+            result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait))
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")
@@ -678,12 +721,15 @@ class Core:
                      "behaviour_labels", "behaviour_bouts", "behaviour_occupancy", "behaviour_transitions")
     _KINEMATIC_KEYS += _SEGMENT_KEYS + tuple(k + "_rigid" for k in _SEGMENT_KEYS)
 
-    def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity, segments=None):
+    def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity, segments=None, gait=None):
         """The keys save()'s flags append, in the result's order, all read from one PoseChain of this save's triangulation.
-        `segments`: None, or (sigma, grid) of the segmentation of every map."""
-        what = "joint_angles" if joint_angles else "rigid_legs" if rigid_legs else "angle_spectrogram" if angle_spectrogram else "behaviour_map"
+        `segments`: None, or (sigma, grid) of the segmentation of every map.  `gait`: None, or the thresholds of the gait analysis."""
+        what = ("joint_angles" if joint_angles else "rigid_legs" if rigid_legs else "angle_spectrogram" if angle_spectrogram
+                else "behaviour_map" if behaviour_map else "gait")
         spectra = angle_spectrogram or behaviour_map
         fps, bank = self._wavelet_bank(what, None, {}) if spectra else (None, {})   # save()'s fps and frequencies are the method's defaults
+        if gait is not None and fps is None:
+            fps = self._gait_fps(None)   # the same rule
         chains = [self._measured_pose(what, fps)]
         keys, host = {}, lambda t: t.cpu().numpy()
         if joint_angles:
@@ -694,6 +740,10 @@ class Core:
             keys["rigid_segment_lengths"] = np.array(chains[0].fit.lengths)
             if joint_angles:
                 keys["joint_angles_rigid"] = host(chains[1].angles[0])
+        gait_keys = {}
+        if gait is not None:   # the rigid chain is the fit computed above: it never runs twice
+            for tag, chain in zip(("", "_rigid"), chains):
+                gait_keys.update({k + tag: v for k, v in zip(self._GAIT_KEYS, self._gait_values(chain.gait(**gait)))})
         # The spectra read the [T, 48] series alone, and those wait on the host too (384 bytes per frame).  Everything the chains hold
         # is dropped with them, so that a map runs beside its own spectrogram and nothing else, as it did when every key started anew.
         dev = chains[0].points3d.device
@@ -717,7 +767,7 @@ class Core:
             S = m = None   # released before the other variant's is computed: one float64 spectrogram at a time
         if angle_spectrogram:
             keys["spectrogram_freqs"], keys["spectrogram_fps"] = bank["freqs"], fps
-        return {k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}
+        return {**{k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}, **gait_keys}
 
     # -- helpers --------------------------------------------------------------------------------------
     def _correction_for(self, corrections, cam_id, img_id):

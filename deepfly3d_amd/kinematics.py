@@ -1,5 +1,6 @@
-"""`PoseChain`: the kinematic chain of one triangulated pose (DESIGN.md sections 14-18) -- body frame, joint angles, leg fit,
-unwrapping, wavelet spectrogram, behaviour map and its segmentation -- with every stage that the default arguments reach computed once.
+"""`PoseChain`: the kinematic chain of one triangulated pose (DESIGN.md sections 14-19) -- body frame, joint angles, leg fit,
+unwrapping, wavelet spectrogram, behaviour map, its segmentation and the gait analysis -- with every stage that the default arguments
+reach computed once.
 
 A chain lives for one call of `Core`: each stage once per save, nothing kept between calls, because `camNet.points3d` changes under
 corrections and re-triangulation.  It keeps the small products (frame, fit, angles, the 48 series: a few KB per frame).  The
@@ -28,9 +29,9 @@ def _unwrapped(series):
 
 class PoseChain:
     """The chain of `points3d` [T, 38, 3] float64 cuda (the layout of points3d_wo_procrustes) sampled at `fps` (needed by the
-    spectrogram alone).  The attributes are the products of the default arguments, computed on first use; a method called with
-    other arguments computes what it is asked for directly from `ops` and keeps nothing.  `measured`: the chain whose recording
-    frame this one shares (see rigid())."""
+    spectrogram and the gait analysis alone).  The attributes are the products of the default arguments, computed on first use; a
+    method called with other arguments computes what it is asked for directly from `ops` and keeps nothing.  `measured`: the chain
+    whose recording frame this one shares (see rigid())."""
 
     def __init__(self, points3d, fps=None, measured=None):
         self.points3d, self.fps, self.measured = points3d, fps, measured
@@ -87,3 +88,10 @@ class PoseChain:
         """(the BehaviourMapResult, ops.segment_map of its embedding): one map, computed once, and its segmentation."""
         m = self.behaviour_map(**behaviour_map_kwargs)
         return m, ops.segment_map(m.embedding, grid, sigma, min_peak)
+
+    def gait(self, **thresholds):
+        """ops.gait (a GaitResult) of this pose at this chain's fps in the recording frame; `thresholds`: on, off, half_window.
+        Not kept."""
+        if self.fps is None:
+            raise ValueError("this chain was built without the recording's fps, which the tip velocity needs")
+        return ops.gait(self.points3d, self.fps, self.frame, **thresholds)

@@ -1,12 +1,13 @@
 """Thin host wrappers over the C ABI for the non-network kernels: arg-max and peaks, re-layout, triangulation, Procrustes and the
-video pose, and what DESIGN.md sections 9-18 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
-overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps and their segmentation.
+video pose, and what DESIGN.md sections 9-19 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
+overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps, their segmentation and the gait analysis.
 
 Inputs/outputs are torch CUDA tensors (device memory + stream plumbing only); every computation is a
 libdf3d_hip.so kernel.  No CPU fallback: a missing library or GPU raises `_native.NativeLibraryError`.
 """
 import collections
 import ctypes
+import dataclasses
 
 import numpy as np
 import torch
@@ -1011,6 +1012,200 @@ def segment_map(Y, grid=None, sigma=None, min_peak=None):
     labels = map_labels(Y, regions, origin)
     bouts, occupancy, transitions = ethogram(labels, roots.numel())
     return BehaviourSegmentsResult(rho, origin, sigma, regions, peaks, labels, bouts, occupancy, transitions)
+
+
+# ---- gait analysis of the leg tips ---------------------------------------------------------------------------
+@dataclasses.dataclass
+class GaitResult:
+    """What `gait` returns, device tensors but for the last two: tip, vel [T, 6, 3] float64 (tip_kinematics), states [T, 6] int32
+    (gait_states), steps [S, 4] int64 and step_metrics [S, 3] float64 (gait_steps), phase [T, 6] float64 (gait_phase), coupling
+    [6, 6, 2] float64 and coupling_count [6, 6] int64 (gait_coupling), pattern [T] int32, pattern_histogram [64] and state_counts
+    [6, 3] int64 (gait_patterns), thresholds (on, off, half_window) and fps."""
+    tip: torch.Tensor
+    vel: torch.Tensor
+    states: torch.Tensor
+    steps: torch.Tensor
+    step_metrics: torch.Tensor
+    phase: torch.Tensor
+    coupling: torch.Tensor
+    coupling_count: torch.Tensor
+    pattern: torch.Tensor
+    pattern_histogram: torch.Tensor
+    state_counts: torch.Tensor
+    thresholds: tuple
+    fps: float
+
+
+def _gait_work(T, device):
+    need = _native.load().df3d_gait_work_bytes(int(T))
+    if need <= 0:
+        raise ValueError(f"no workspace for T = {T} frames: T must be at most (2^31 - 1) / 6")
+    return torch.empty((need,), dtype=torch.uint8, device=device), need
+
+
+def _need_gait(t, dtype, tail, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 1 + len(tail) and tuple(t.shape[1:]) == tail):
+        raise ValueError(f"{name} must be a {dtype} CUDA tensor of shape [T, {', '.join(str(n) for n in tail)}]")
+    return t.contiguous()
+
+
+def _gait_fps(fps):
+    if isinstance(fps, bool) or not isinstance(fps, (int, float, np.integer, np.floating)) or not (np.isfinite(fps) and fps > 0):
+        raise ValueError(f"fps must be a finite number > 0 (it is {fps!r})")
+    return float(fps)
+
+
+def gait_thresholds(on=None, off=None, half_window=None):
+    """(on, off, half_window) with config.GAIT_SWING_ON, GAIT_SWING_OFF and GAIT_DIFF_HALF for what is None.  ValueError: a threshold
+    that is not finite, on <= off, a half window that is no integer in config.GAIT_DIFF_HALF_RANGE."""
+    from . import config
+
+    on = float(config.GAIT_SWING_ON if on is None else on)
+    off = float(config.GAIT_SWING_OFF if off is None else off)
+    if not (np.isfinite(on) and np.isfinite(off)):
+        raise ValueError(f"on and off must be finite (they are {on:g} and {off:g})")
+    if not on > off:
+        raise ValueError(f"on must be above off (they are {on:g} and {off:g})")
+    lo, hi = config.GAIT_DIFF_HALF_RANGE
+    w = config.GAIT_DIFF_HALF if half_window is None else half_window
+    if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not lo <= w <= hi:
+        raise ValueError(f"half_window must be an integer in [{lo}, {hi}] (it is {w!r})")
+    return on, off, int(w)
+
+
+@_on_tensor_device
+def tip_kinematics(points3d, fps, body_frame="recording", half_window=None):
+    """(tip, vel), both [T, 6, 3] float64, of points3d [T, 38, 3] (float64 cuda, the layout of points3d_wo_procrustes) sampled at
+    `fps`: every leg's tip relative to its body-coxa joint, q(P4 - P0), and the tip's velocity q(P4[b] - P4[a]) fps / (b - a) over
+    the window a = max(t - half_window, 0), b = min(t + half_window, T - 1), in the leg coordinates of joint_angles (x anterior,
+    side-1 legs mirrored in y) and pose units (per second).  `body_frame` as in joint_angles.  NaN where an end joint is missing
+    (the velocity: P4 at a or at b), where the window is empty (T = 1) or where the frame holds a non-finite number."""
+    if not (isinstance(points3d, torch.Tensor) and points3d.is_cuda and points3d.dtype == torch.float64 and points3d.dim() == 3
+            and tuple(points3d.shape[1:]) == (38, 3)):
+        raise ValueError("points3d must be a torch.float64 CUDA tensor of shape [T, 38, 3]")
+    points3d = points3d.contiguous()
+    fps, w = _gait_fps(fps), gait_thresholds(half_window=half_window)[2]
+    T, dev = points3d.shape[0], points3d.device
+    tip = torch.empty((T, 6, 3), dtype=torch.float64, device=dev)
+    vel = torch.empty((T, 6, 3), dtype=torch.float64, device=dev)
+    if isinstance(body_frame, str):
+        if body_frame not in ("recording", "per_frame"):
+            raise ValueError('body_frame must be "recording", "per_frame" or a [3, 3] / [T, 3, 3] array')
+        frames = None
+    else:
+        frames = body_frame if isinstance(body_frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(body_frame, dtype=np.float64))
+        if tuple(frames.shape) not in ((3, 3), (1, 3, 3), (T, 3, 3)):
+            raise ValueError(f"an explicit body_frame must be [3, 3] or [T, 3, 3] with T = {T}")
+        frames = frames.to(device=dev, dtype=torch.float64).reshape(-1, 3, 3).contiguous()
+    if T == 0:
+        return tip, vel
+    if frames is None:
+        frames = recording_frame(points3d) if body_frame == "recording" else _pose_frames(points3d)
+    _bmap_call("df3d_gait_velocity", points3d.data_ptr(), T, frames.data_ptr(), frames.shape[0], fps, w, tip.data_ptr(), vel.data_ptr(),
+               _stream(points3d))
+    return tip, vel
+
+
+@_on_tensor_device
+def gait_states(vel, on=None, off=None):
+    """states [T, 6] int32 of vel [T, 6, 3] (float64 cuda, tip_kinematics'): swing/stance by hysteresis on the anterior velocity
+    u = vel[..., 0].  A sample is unknown where u is NaN, swing where u > on, stance where u < off (defaults config.GAIT_SWING_ON and
+    GAIT_SWING_OFF, a guess nobody has measured on a recording) and keeps the state otherwise; the state is that of the last
+    deciding sample at or before t: -1 unknown, 0 stance, 1 swing, and -1 before the first."""
+    vel = _need_gait(vel, torch.float64, (6, 3), "vel")
+    on, off, _ = gait_thresholds(on, off)
+    T = vel.shape[0]
+    states = torch.empty((T, 6), dtype=torch.int32, device=vel.device)
+    if T:
+        work, need = _gait_work(T, vel.device)
+        _bmap_call("df3d_gait_states", vel.data_ptr(), T, on, off, states.data_ptr(), work.data_ptr(), need, _stream(vel))
+    return states
+
+
+def _need_states(states):
+    return _need_gait(states, torch.int32, (6,), "states")
+
+
+@_on_tensor_device
+def gait_steps(states, tip, fps):
+    """(steps [S, 4] int64, metrics [S, 3] float64) of states [T, 6] (int32 cuda) and tip [T, 6, 3]: a lift-off is a frame t >= 1
+    with states 0 then 1, a touch-down the reverse; a step is a pair of consecutive lift-offs t0 < t2 of a leg with no unknown
+    state in [t0, t2], and t1 the one touch-down between them.  Rows (leg, t0, t1, t2) ordered by (leg, t0); metrics: swing duration
+    (t1 - t0) / fps, stance duration (t2 - t1) / fps, stride tip[t1, leg, 0] - tip[t0, leg, 0] (NaN where either tip is).  S is
+    read back."""
+    states = _need_states(states)
+    tip = _need_gait(tip, torch.float64, (6, 3), "tip")
+    fps = _gait_fps(fps)
+    T, dev = states.shape[0], states.device
+    if tip.shape[0] != T or tip.device != dev:
+        raise ValueError(f"tip must hold the {T} frames of states, on their device")
+    if T == 0:
+        return torch.zeros((0, 4), dtype=torch.int64, device=dev), torch.zeros((0, 3), dtype=torch.float64, device=dev)
+    steps = torch.empty((3 * T, 4), dtype=torch.int64, device=dev)
+    metrics = torch.empty((3 * T, 3), dtype=torch.float64, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    work, need = _gait_work(T, dev)
+    _bmap_call("df3d_gait_steps", states.data_ptr(), tip.data_ptr(), T, fps, steps.data_ptr(), metrics.data_ptr(), count.data_ptr(),
+               work.data_ptr(), need, _stream(states))
+    S = int(count.item())
+    return steps[:S].clone(), metrics[:S].clone()
+
+
+@_on_tensor_device
+def gait_phase(states):
+    """phase [T, 6] float64 of states [T, 6] (int32 cuda): (t - t0) / (t2 - t0) for the step of the leg with t0 <= t < t2
+    (gait_steps), NaN outside every step."""
+    states = _need_states(states)
+    T = states.shape[0]
+    phase = torch.empty((T, 6), dtype=torch.float64, device=states.device)
+    if T:
+        work, need = _gait_work(T, states.device)
+        _bmap_call("df3d_gait_phase", states.data_ptr(), T, phase.data_ptr(), work.data_ptr(), need, _stream(states))
+    return phase
+
+
+@_on_tensor_device
+def gait_coupling(phase):
+    """(mean [6, 6, 2] float64, count [6, 6] int64) of phase [T, 6] (float64 cuda): for every ordered pair of legs the mean of
+    (cos, sin)(2 pi (phase_i - phase_j)) over the count[i, j] frames where both phases are finite, NaN where there is none.  The
+    resultant length is numpy.hypot of the two components and the mean angle their arctan2."""
+    phase = _need_gait(phase, torch.float64, (6,), "phase")
+    T, dev = phase.shape[0], phase.device
+    mean = torch.full((6, 6, 2), float("nan"), dtype=torch.float64, device=dev)
+    count = torch.zeros((6, 6), dtype=torch.int64, device=dev)
+    if T:
+        work, need = _gait_work(T, dev)
+        _bmap_call("df3d_gait_coupling", phase.data_ptr(), T, mean.data_ptr(), count.data_ptr(), work.data_ptr(), need, _stream(phase))
+    return mean, count
+
+
+@_on_tensor_device
+def gait_patterns(states):
+    """(pattern [T] int32, histogram [64] int64, state_counts [6, 3] int64) of states [T, 6] (int32 cuda): every frame's mask of
+    the legs in swing (bit L = leg L; config.GAIT_TRIPODS are the two tripods), -1 where a leg is unknown; the frames of every
+    mask; every leg's unknown, stance and swing frames."""
+    states = _need_states(states)
+    T, dev = states.shape[0], states.device
+    pattern = torch.empty((T,), dtype=torch.int32, device=dev)
+    histogram = torch.zeros((64,), dtype=torch.int64, device=dev)
+    counts = torch.zeros((6, 3), dtype=torch.int64, device=dev)
+    if T:
+        _bmap_call("df3d_gait_patterns", states.data_ptr(), T, pattern.data_ptr(), histogram.data_ptr(), counts.data_ptr(), _stream(states))
+    return pattern, histogram, counts
+
+
+def gait(points3d, fps, body_frame="recording", on=None, off=None, half_window=None):
+    """The gait analysis of points3d [T, 38, 3] (float64 cuda) sampled at `fps`, a GaitResult: tip_kinematics,
+    gait_states, gait_steps, gait_phase, gait_coupling and gait_patterns, each on the one before."""
+    thresholds = gait_thresholds(on, off, half_window)   # refused before any work
+    fps = _gait_fps(fps)
+    tip, vel = tip_kinematics(points3d, fps, body_frame, thresholds[2])
+    states = gait_states(vel, thresholds[0], thresholds[1])
+    steps, metrics = gait_steps(states, tip, fps)
+    phase = gait_phase(states)
+    mean, count = gait_coupling(phase)
+    pattern, histogram, counts = gait_patterns(states)
+    return GaitResult(tip, vel, states, steps, metrics, phase, mean, count, pattern, histogram, counts, thresholds, fps)
 
 
 def gaussian_window_taps(window_size, sigma, truncate=4.0):

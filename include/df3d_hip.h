@@ -413,6 +413,49 @@ int df3d_bseg_bouts(const int* labels_dev, long long T, int num_regions, long lo
                     long long* transitions_dev, void* work_dev, long long work_len_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a15 gait analysis of the leg tips (the model is this project's own specification, defined in float64 by
+ *     tests/gait_oracle.py).  All arrays are DEVICE arrays, row-major: float64, int32, and int64 for steps and counts.  No
+ *     floating-point atomics and fixed-order sums: two calls on the same input give the same bits, on any machine.  Leg L = 3 side +
+ *     l, its joints P0 .. P4, the leg coordinates q(v) = (v . ex, +-v . ey, v . ez) (mirrored on side 1) and the missing-joint rule
+ *     are those of df3d_joint_angles.
+ * df3d_gait_velocity: pts [T, 38, 3] and the body frame(s) [nframes, 3, 3], nframes = 1 or T, as in df3d_joint_angles.  tip [T, 6, 3]
+ *     = q(P4 - P0), NaN where P0 or P4 is missing or the frame holds a non-finite number.  vel [T, 6, 3] = q(P4[b] - P4[a]) (fps /
+ *     (b - a)) with a = max(t - half_window, 0) and b = min(t + half_window, T - 1), in frame t's body frame; NaN where b = a, where
+ *     P4 is missing at a or at b, or where the frame holds a non-finite number.
+ * df3d_gait_states: states [T, 6] int32 from the anterior velocity u = vel[t, L, 0]: a sample is unknown where u is NaN, swing where
+ *     u > on, stance where u < off and undecided otherwise; the state is that of the last decided sample at or before t, as -1
+ *     (unknown), 0 (stance), 1 (swing), and -1 where there is none.
+ * df3d_gait_steps: a lift-off is a frame t >= 1 with states 0 then 1, a touch-down the reverse; a step of a leg is a pair of
+ *     consecutive lift-offs t0 < t2 with no unknown state in [t0, t2], and t1 the touch-down between them.  steps [3 T, 4] int64:
+ *     row r < S is (L, t0, t1, t2), ordered by (L, t0); metrics [3 T, 3]: swing duration (t1 - t0) / fps, stance duration (t2 - t1) /
+ *     fps and stride tip[t1, L, 0] - tip[t0, L, 0]; the rows from S on are zero; num_steps[0] = S.  A state other than 0 and 1 is
+ *     unknown.
+ * df3d_gait_phase: phase [T, 6] = (t - t0) / (t2 - t0) for the step with t0 <= t < t2, NaN outside every step.
+ * df3d_gait_coupling: mean [6, 6, 2] = the mean of (cos, sin)(2 pi (phase_i - phase_j)) over the count [6, 6] (int64) frames where both
+ *     phases are finite, NaN where there is none; summed in slices of 2 048 frames that are added in index order.
+ * df3d_gait_patterns: pattern [T] int32 = the mask of the legs in swing (bit L), -1 where a leg is unknown; histogram [64] int64 =
+ *     the frames of every mask; state_counts [6, 3] int64 = every leg's unknown, stance and swing frames.
+ * df3d_gait_work_bytes(T): the bytes of the caller-owned workspace that serves every entry above at this T (0 where T is out of
+ *     range).
+ * DF3D_EINVAL before the device is touched, with a message that names the argument: T negative or above (2^31 - 1) / 6; fps not
+ *     finite or <= 0; on or off not finite, or on <= off; half_window outside [1, 64]; nframes other than 1 or T; a null, misaligned
+ *     (16 bytes for work, 8 for float64 and int64, 4 for int32) or overlapping buffer; a workspace below the query.  T = 0 launches
+ *     nothing and returns DF3D_OK.  Every launching entry is asynchronous on `stream`, allocates nothing and keeps no host pointer.
+ * ---------------------------------------------------------------------------------------------- */
+long long df3d_gait_work_bytes(long long T);
+int df3d_gait_velocity(const double* pts_dev, long long T, const double* frame_dev, long long nframes, double fps, int half_window,
+                       double* tip_dev, double* vel_dev, void* stream);
+int df3d_gait_states(const double* vel_dev, long long T, double on, double off, int* states_dev, void* work_dev, long long work_len_bytes,
+                     void* stream);
+int df3d_gait_steps(const int* states_dev, const double* tip_dev, long long T, double fps, long long* steps_dev, double* metrics_dev,
+                    int* num_steps_dev, void* work_dev, long long work_len_bytes, void* stream);
+int df3d_gait_phase(const int* states_dev, long long T, double* phase_dev, void* work_dev, long long work_len_bytes, void* stream);
+int df3d_gait_coupling(const double* phase_dev, long long T, double* mean_dev, long long* count_dev, void* work_dev, long long work_len_bytes,
+                       void* stream);
+int df3d_gait_patterns(const int* states_dev, long long T, int* pattern_dev, long long* histogram_dev, long long* state_counts_dev,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
