@@ -122,6 +122,9 @@ PROTOTYPES = {
     "df3d_gait_phase": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p]),
     "df3d_gait_coupling": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "df3d_gait_patterns": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_repair_work_bytes": (c_longlong, [c_longlong]),
+    "df3d_repair_outliers": (c_int, [c_void_p, c_longlong, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "df3d_repair_fill": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "df3d_ba_eval": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_colsq": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_matvec": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -110,7 +110,37 @@ def parse_cli_args(argv=None):
     p.add_argument("--gait-off", dest="gait_off", type=float, default=None, metavar="V",
                    help="With --gait: the anterior tip velocity below which a leg goes into stance (default 0, a guess like --gait-on); it must "
                         "lie below --gait-on")
+    p.add_argument("--repair-pose", dest="repair_pose", action="store_true",
+                   help="Repair the triangulated pose before the kinematics: a joint that lies further from the median of the frames round it "
+                        "than --repair-threshold robust deviations (a Hampel test, per coordinate, one pass) is an outlier; outliers and missing "
+                        "joints are interpolated linearly over gaps of at most --repair-max-gap frames and set to 0 (missing) otherwise.  "
+                        "Appends, after every other key, points3d_repaired [T, 38, 3], repair_status [T, 38] (int8: 0 kept, 1 missing and "
+                        "filled, 2 outlier and filled, 3 missing and left, 4 outlier and removed), repair_counts [38, 5], repair_score [T, 38] "
+                        "and repair_params to the result, and every other opt-in key (--joint-angles, --rigid-legs, --angle-spectrogram, "
+                        "--behaviour-map, --gait) is computed from the repaired pose; points3d and points3d_wo_procrustes stay the "
+                        "triangulation's own.  The defaults are guesses that nobody has measured on a recording, and a test on positions is "
+                        "blind to a spike smaller than the threshold times the local spread of a fast-moving tip.  Works with "
+                        "--skip-pose-estimation on an earlier result")
+    p.add_argument("--repair-window", dest="repair_window", type=int, default=None, metavar="H",
+                   help="With --repair-pose: the frames to either side of a frame that its median is taken over, 1 to 64 (default 5, a guess)")
+    p.add_argument("--repair-threshold", dest="repair_threshold", type=float, default=None, metavar="K",
+                   help="With --repair-pose: the robust deviations (1.4826 times the window's median absolute deviation) beyond which a joint is "
+                        "an outlier (default 6, a guess)")
+    p.add_argument("--repair-floor", dest="repair_floor", type=float, default=None, metavar="MM",
+                   help="With --repair-pose: the deviation, in pose units (mm), below which a joint is never an outlier (default 0.05, a guess)")
+    p.add_argument("--repair-max-gap", dest="repair_max_gap", type=int, default=None, metavar="N",
+                   help="With --repair-pose: the longest run of bad frames of a joint that is interpolated, 0 to 1000000 (default 10, a guess)")
     args = p.parse_args(argv)
+    for name in ("window", "threshold", "floor", "max_gap"):
+        if getattr(args, "repair_" + name) is not None and not args.repair_pose:
+            p.error(f"--repair-{name.replace('_', '-')} sets a parameter of --repair-pose: it needs --repair-pose")
+    if args.repair_pose:
+        from . import ops
+
+        try:
+            ops.repair_params(args.repair_window, args.repair_threshold, args.repair_floor, args.repair_max_gap)
+        except ValueError as e:
+            p.error(f"--repair-window, --repair-threshold, --repair-floor and --repair-max-gap: {e}")
     if args.gait_on is not None and not args.gait:
         p.error("--gait-on sets the swing threshold of --gait: it needs --gait")
     if args.gait_off is not None and not args.gait:
@@ -176,13 +206,15 @@ _NO_IMAGES = ("--video-heatmap draws the heat-maps the network computes from the
 def run(args):
     video_heatmap = getattr(args, "video_heatmap", False)
     # what the second save appends to the result: the kinematics flags, in the order of their keys, and the map's perplexity
-    extras = {name: getattr(args, name, False) for name in ("joint_angles", "rigid_legs", "angle_spectrogram", "behaviour_map", "gait")}
+    extras = {name: getattr(args, name, False) for name in ("joint_angles", "rigid_legs", "angle_spectrogram", "behaviour_map", "gait", "repair_pose")}
     flagged = [name for name, on in extras.items() if on]
     extras["behaviour_perplexity"] = getattr(args, "behaviour_perplexity", None)
     if getattr(args, "behaviour_segments", False):   # the map's segmentation: no keys of its own flag without --behaviour-map
         extras.update(behaviour_segments=True, behaviour_sigma=getattr(args, "behaviour_sigma", None), behaviour_grid=getattr(args, "behaviour_grid", None))
     if extras["gait"]:
         extras.update(gait_on=getattr(args, "gait_on", None), gait_off=getattr(args, "gait_off", None))
+    if extras["repair_pose"]:
+        extras.update({name: getattr(args, name, None) for name in ("repair_window", "repair_threshold", "repair_floor", "repair_max_gap")})
     if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not flagged:
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0

@@ -121,6 +121,22 @@ GAIT_SWING_ON = 5.0
 GAIT_SWING_OFF = 0.0
 GAIT_TRIPODS = (21, 42)
 
+# ---- repair of the 3-D pose.  A joint is an outlier when, in any coordinate, it lies further from the median
+# of the REPAIR_HALF_WINDOW frames to either side (clipped at the recording's ends, missing frames left out) than REPAIR_THRESHOLD
+# times 1.4826 times the median absolute deviation of that window, and further than REPAIR_FLOOR pose units (mm); a window with
+# fewer than REPAIR_MIN_COUNT frames is not tested.  Missing joints and outliers are then interpolated linearly between their nearest
+# good neighbours where the gap is at most REPAIR_MAX_GAP frames long, and left (removed) otherwise.  The four defaults are guesses
+# in the sense of the gait thresholds: nobody has measured them on a real recording.  A test on positions is blind to a spike smaller
+# than the threshold times the local spread of a fast-moving tip.
+REPAIR_HALF_WINDOW = 5
+REPAIR_HALF_WINDOW_RANGE = (1, 64)
+REPAIR_THRESHOLD = 6.0
+REPAIR_FLOOR = 0.05
+REPAIR_MIN_COUNT = 3
+REPAIR_MAX_GAP = 10
+REPAIR_MAX_GAP_RANGE = (0, 1000000)
+REPAIR_MAD_TO_SIGMA = 1.4826   # the median absolute deviation of a normal sample times this estimates its standard deviation
+
 # ---- which camera sees which joint (reference df3d/skeleton_fly.py:202-250), by camera id: cameras 0-2 look at the side whose
 # joints are 0..18, cameras 4-6 at the side of joints 19..37, camera 3 faces the fly.  Pinned by tests/golden/skeleton_tables.npz.
 # Where df3d::relayout_source (csrc/geometry_dev.h) fills a joint of a side camera under the identity ordering, this table sees it;

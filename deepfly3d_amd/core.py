@@ -346,9 +346,10 @@ class Core:
         return self.next_error_in_range(range(img_id - 1, -1, -1))
 
     # -- the kinematic chain (DESIGN.md sections 14-17): one kinematics.PoseChain per call, never kept ----------------------------------
-    def _measured_pose(self, what, fps=None):
+    def _measured_pose(self, what, fps=None, repair=None):
         """The PoseChain of camNet.points3d on the device (triangulating first when there is none), with the refusals of the rank-0
-        pose queries."""
+        pose queries.  `repair`: None or False, or the chain of the repaired pose instead: True for the default
+        parameters, or a dict of ops.repair_pose's."""
         from . import distributed as dd
 
         if dd.current()[0] != 0:
@@ -359,28 +360,44 @@ class Core:
             self.camNet.triangulate()
         _native.require_gpu()
         dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
-        return PoseChain(torch.from_numpy(np.ascontiguousarray(self.camNet.points3d, dtype=np.float64)).to(dev), fps)
+        chain = PoseChain(torch.from_numpy(np.ascontiguousarray(self.camNet.points3d, dtype=np.float64)).to(dev), fps)
+        return chain.repaired(**(repair if isinstance(repair, dict) else {})) if repair else chain
 
-    def joint_angles(self, body_frame="recording", rigid=False):
+    def repair_pose(self, half_window=None, threshold=None, floor=None, max_gap=None, min_count=None):
+        """The repaired pose (ops.repair_pose) of the triangulation `camNet.points3d`, an ops.PoseRepairResult of
+        numpy arrays: points [T, 38, 3] (outliers and missing joints interpolated linearly over gaps of at most `max_gap` frames, set
+        to 0 -- missing -- where the gap is longer or touches an end of the recording), status [T, 38] int8 (0 kept, 1 missing and
+        filled, 2 outlier and filled, 3 missing and left, 4 outlier and removed), counts [38, 5], score [T, 38] (the Hampel test's
+        largest deviation / bound; NaN for a missing or untested joint) and params (half_window, threshold, floor, max_gap,
+        min_count).  The defaults, config.REPAIR_*, are guesses nobody has measured on a recording.  Triangulates first when there
+        is no points3d yet.  A rank-0 method with joint_angles' refusals."""
+        params = dict(zip(("half_window", "threshold", "floor", "max_gap", "min_count"),
+                          ops.repair_params(half_window, threshold, floor, max_gap, min_count)))   # refused before any work
+        r = self._measured_pose("repair_pose", repair=params).repair
+        return ops.PoseRepairResult(r.points.cpu().numpy(), r.status.cpu().numpy(), r.counts.cpu().numpy(), r.score.cpu().numpy(), r.params)
+
+    def joint_angles(self, body_frame="recording", rigid=False, repair=False):
         """(angles [T, 6, 8] radians, lengths [T, 6, 4]) as numpy arrays: the eight joint angles (config.LEG_ANGLE_NAMES) and four
         segment lengths of every leg (config.LEG_NAMES), ops.joint_angles of the triangulation `camNet.points3d` -- what the result
         calls points3d_wo_procrustes; the per-side Procrustes result registers the two sides separately and is not the input.
         Triangulates first when the camera network holds no points3d yet; after editing detections call camNet.triangulate() (save()
         does).  `body_frame`: "recording" (default), "per_frame" or an explicit [3, 3] / [T, 3, 3] array.  `rigid=True`: the angles of
         the constant-length pose rigid_legs() fits, whose lengths are the fixed ones; "recording" is then still
-        the recording frame of the MEASURED pose, so that both sets of angles share one frame.  A rank-0 method, like the
+        the recording frame of the MEASURED pose, so that both sets of angles share one frame.  `repair=True`: of the repaired pose
+        (repair_pose() with its defaults), whose recording frame is its own.  A rank-0 method, like the
         reprojection-error queries."""
-        chain = self._measured_pose("joint_angles")
+        chain = self._measured_pose("joint_angles", repair=repair)
         angles, lengths = (chain.rigid() if rigid else chain).joint_angles(body_frame)
         return angles.cpu().numpy(), lengths.cpu().numpy()
 
-    def rigid_legs(self, lengths="recording", anchor="per_frame"):
+    def rigid_legs(self, lengths="recording", anchor="per_frame", repair=False):
         """(points [T, 38, 3], lengths [6, 4], cost [T, 6]) as numpy arrays: the triangulation `camNet.points3d` with every leg replaced
         by the chain of constant segment lengths that lies closest to its measured joints (ops.fit_legs), the lengths used, and each
         leg's summed squared distance from the measured joints (NaN where a leg misses a joint and is left as measured).  `lengths`:
         "recording" (every segment's median over the recording) or a [6, 4] array; `anchor`: "per_frame", "recording" or a [6, 3]
-        array.  Triangulates first when there is no points3d yet.  A rank-0 method with joint_angles' refusals."""
-        fit = ops.fit_legs(self._measured_pose("rigid_legs").points3d, lengths, anchor)
+        array.  `repair=True`: the fit of the repaired pose (repair_pose() with its defaults).  Triangulates first when there is no
+        points3d yet.  A rank-0 method with joint_angles' refusals."""
+        fit = ops.fit_legs(self._measured_pose("rigid_legs", repair=repair).points3d, lengths, anchor)
         return fit.points.cpu().numpy(), np.array(fit.lengths), fit.cost.cpu().numpy()
 
     def _wavelet_bank(self, what, fps, bank):
@@ -398,42 +415,43 @@ class Core:
         freqs = bank["freqs"] if "freqs" in bank else ops.wavelet_frequencies(fps, bank.get("f_min"), bank.get("f_max"), bank.get("num"))
         return fps, dict(freqs=np.ascontiguousarray(freqs, dtype=np.float64), omega0=bank.get("omega0"), radius=bank.get("radius"))
 
-    def angle_spectrogram(self, rigid=False, body_frame="recording", fps=None, unwrap=True, **bank):
+    def angle_spectrogram(self, rigid=False, body_frame="recording", fps=None, unwrap=True, repair=False, **bank):
         """(S [T, 6, 8, F], freqs [F]) as numpy arrays: the Morlet wavelet amplitudes (ops.wavelet_spectrogram, radians) of the
         48 joint-angle series joint_angles(body_frame, rigid) returns, and the rows' frequencies in Hz.  `fps`: the sampling rate;
         None means get_fps(), and where that is None config.SPECTROGRAM_FPS.  `unwrap=True` first applies numpy.unwrap's rule
         along time to the angles that live on the full circle (config.SPECTROGRAM_UNWRAPPED_ANGLES): a wrap at +-pi is otherwise
         a step of 2 pi that lights up every row.  A series that holds a non-finite sample is left wrapped and named in one logged
-        warning.  `bank`: f_min, f_max, num (ops.wavelet_frequencies) or freqs, and omega0, radius.  A rank-0 method with
-        joint_angles' refusals."""
+        warning.  `bank`: f_min, f_max, num (ops.wavelet_frequencies) or freqs, and omega0, radius.  `repair=True`: of the repaired
+        pose (repair_pose() with its defaults).  A rank-0 method with joint_angles' refusals."""
         fps, bank = self._wavelet_bank("angle_spectrogram", fps, bank)
-        chain = self._measured_pose("angle_spectrogram", fps)
+        chain = self._measured_pose("angle_spectrogram", fps, repair)
         return (chain.rigid() if rigid else chain).spectrogram(body_frame, unwrap, **bank).cpu().numpy(), bank["freqs"]
 
-    def behaviour_map(self, rigid=False, perplexity=None, n_iter=None, max_points=None, seed=0, **spectrogram_kwargs):
+    def behaviour_map(self, rigid=False, perplexity=None, n_iter=None, max_points=None, seed=0, repair=False, **spectrogram_kwargs):
         """The behaviour map (ops.behaviour_map) of the float64 spectrogram angle_spectrogram(rigid, **spectrogram_kwargs) computes,
         every frame's [6, 8, F] amplitudes flattened to one spectrum: an ops.BehaviourMapResult of numpy arrays -- embedding [T, 2]
         (NaN for a frame whose spectrum holds a NaN), train_index [N], beta [T], info [T], kl and perplexity.  A recording too
-        short for the perplexity (3 perplexity <= frames - 1) is refused before anything is computed.  A rank-0 method with
-        angle_spectrogram's refusals."""
+        short for the perplexity (3 perplexity <= frames - 1) is refused before anything is computed.  `repair=True`: of the repaired
+        pose (repair_pose() with its defaults).  A rank-0 method with angle_spectrogram's refusals."""
         bank = dict(spectrogram_kwargs)
         body_frame, fps, unwrap = bank.pop("body_frame", "recording"), bank.pop("fps", None), bank.pop("unwrap", True)
         frames = getattr(self, "num_images", None)
         if frames is not None and self.camNet is not None and self.camNet.has_calibration():
             ops.behaviour_map_points(frames, perplexity, max_points)   # before any work
         fps, bank = self._wavelet_bank("behaviour_map", fps, bank)
-        chain = self._measured_pose("behaviour_map", fps)
+        chain = self._measured_pose("behaviour_map", fps, repair)
         r = (chain.rigid() if rigid else chain).behaviour_map(perplexity, n_iter, max_points, seed, body_frame=body_frame, unwrap=unwrap, **bank)
         return ops.BehaviourMapResult(r.embedding.cpu().numpy(), r.train_index.cpu().numpy(), r.beta.cpu().numpy(), r.info.cpu().numpy(), r.kl,
                                       r.perplexity)
 
-    def behaviour_segments(self, rigid=False, grid=None, sigma=None, min_peak=None, **behaviour_map_kwargs):
+    def behaviour_segments(self, rigid=False, grid=None, sigma=None, min_peak=None, repair=False, **behaviour_map_kwargs):
         """The segmentation (ops.segment_map) of the map behaviour_map(rigid, **behaviour_map_kwargs) computes, the map itself
         computed once: an ops.BehaviourSegmentsResult of numpy arrays -- density [G, G], origin (x0, y0, h), sigma, regions [G, G]
         int32, region_peaks [R, 2], labels [T] int32 (-1 for a frame without a place on the map, 0 for one outside every region),
         bouts [B, 3] int64 (label, start, length), occupancy [R + 1] and transitions [R + 1, R + 1] int64.  `grid`, `sigma`,
         `min_peak`: config.BEHAVIOUR_GRID, config.BEHAVIOUR_DENSITY_SIGMA_FRACTION of the map's extent and
-        config.BEHAVIOUR_MIN_PEAK by default.  A rank-0 method with behaviour_map's refusals."""
+        config.BEHAVIOUR_MIN_PEAK by default.  `repair=True`: of the repaired pose (repair_pose() with its defaults).  A rank-0 method
+        with behaviour_map's refusals."""
         kw = dict(behaviour_map_kwargs)
         perplexity, max_points = kw.pop("perplexity", None), kw.pop("max_points", None)
         n_iter, seed = kw.pop("n_iter", None), kw.pop("seed", 0)
@@ -442,7 +460,7 @@ class Core:
         if frames is not None and self.camNet is not None and self.camNet.has_calibration():
             ops.behaviour_map_points(frames, perplexity, max_points)   # before any work
         fps, bank = self._wavelet_bank("behaviour_segments", fps, kw)
-        chain = self._measured_pose("behaviour_segments", fps)
+        chain = self._measured_pose("behaviour_segments", fps, repair)
         _, s = (chain.rigid() if rigid else chain).behaviour_segments(grid, sigma, min_peak, perplexity=perplexity, n_iter=n_iter,
                                                                       max_points=max_points, seed=seed, body_frame=body_frame, unwrap=unwrap, **bank)
         return ops.BehaviourSegmentsResult(*(t.cpu().numpy() if isinstance(t, torch.Tensor) else t for t in s))
@@ -456,7 +474,7 @@ class Core:
             fps = self.get_fps()
         return float(SPECTROGRAM_FPS if fps is None else fps)
 
-    def gait(self, rigid=False, fps=None, on=None, off=None, half_window=None):
+    def gait(self, rigid=False, fps=None, on=None, off=None, half_window=None, repair=False):
         """The gait analysis (ops.gait) of the triangulation `camNet.points3d` in the recording's body frame, an
         ops.GaitResult of numpy arrays: tip and vel [T, 6, 3] (every leg's tip relative to its body-coxa joint and its velocity, in
         leg coordinates), states [T, 6] int32 (-1 unknown, 0 stance, 1 swing), steps [S, 4] int64 (leg, lift-off, touch-down, next
@@ -465,10 +483,10 @@ class Core:
         state_counts [6, 3], thresholds (on, off, half_window) and fps.  `fps`: None means get_fps(), and where that is None
         config.SPECTROGRAM_FPS.  `on`, `off`: the swing thresholds on the tip's anterior velocity, config.GAIT_SWING_ON and
         GAIT_SWING_OFF by default -- a guess nobody has measured on a recording; `half_window`: config.GAIT_DIFF_HALF.  `rigid=True`:
-        of the constant-length pose rigid_legs() fits, in the recording frame of the measured pose.  A rank-0 method with
-        joint_angles' refusals."""
+        of the constant-length pose rigid_legs() fits, in the recording frame of the measured pose.  `repair=True`: of the repaired
+        pose (repair_pose() with its defaults).  A rank-0 method with joint_angles' refusals."""
         thresholds = dict(zip(("on", "off", "half_window"), ops.gait_thresholds(on, off, half_window)))   # refused before any work
-        chain = self._measured_pose("gait", ops._gait_fps(self._gait_fps(fps)))
+        chain = self._measured_pose("gait", ops._gait_fps(self._gait_fps(fps)), repair)
         g = (chain.rigid() if rigid else chain).gait(**thresholds)
         values = (getattr(g, f.name) for f in dataclasses.fields(g))
         return ops.GaitResult(*(v.cpu().numpy() if isinstance(v, torch.Tensor) else v for v in values))
@@ -640,7 +658,8 @@ class Core:
         return None if full is None else full.cpu().numpy()
 
     def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False, behaviour_perplexity=None,
-             behaviour_segments=False, behaviour_sigma=None, behaviour_grid=None, gait=False, gait_on=None, gait_off=None):
+             behaviour_segments=False, behaviour_sigma=None, behaviour_grid=None, gait=False, gait_on=None, gait_off=None, repair_pose=False,
+             repair_window=None, repair_threshold=None, repair_floor=None, repair_max_gap=None):
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
         keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras).
         `rigid_legs=True` appends, after those, "points3d_rigid", "rigid_segment_lengths" and "rigid_fit_cost" (Core.rigid_legs()) and,
@@ -659,7 +678,12 @@ class Core:
         "gait_states" [T, 6] int8, "gait_steps" [S, 4], "gait_step_metrics" [S, 3], "gait_phase" [T, 6], "gait_coupling" [6, 6, 2],
         "gait_coupling_count" [6, 6], "gait_pattern" [T] int32, "gait_pattern_histogram" [64], "gait_state_counts" [6, 3],
         "gait_thresholds" (on, off, half_window) and "gait_fps" and, together with rigid_legs, the same thirteen with "_rigid" appended
-        (of the fit this save computed, in the measured pose's recording frame)."""
+        (of the fit this save computed, in the measured pose's recording frame).  `repair_pose=True` appends, after every other key,
+        the repaired pose of this save's triangulation (Core.repair_pose() with `repair_window`, `repair_threshold`, `repair_floor`
+        and `repair_max_gap`; the defaults are guesses nobody has measured on a recording): "points3d_repaired" [T, 38, 3],
+        "repair_status" [T, 38] int8, "repair_counts" [38, 5], "repair_score" [T, 38] and "repair_params" (half_window, threshold,
+        floor, max_gap, min_count); every other opt-in key of the same save is then computed from the repaired pose, which is repaired
+        once.  "points3d" and "points3d_wo_procrustes" stay the triangulation's own."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
@@ -673,6 +697,10 @@ class Core:
         if (gait_on is not None or gait_off is not None) and not gait:
             raise ValueError("gait_on and gait_off belong to gait: they need gait=True")
         gait = dict(zip(("on", "off", "half_window"), ops.gait_thresholds(gait_on, gait_off))) if gait else None   # refused before any work
+        if not repair_pose and any(v is not None for v in (repair_window, repair_threshold, repair_floor, repair_max_gap)):
+            raise ValueError("repair_window, repair_threshold, repair_floor and repair_max_gap belong to repair_pose: they need repair_pose=True")
+        repair = (dict(zip(("half_window", "threshold", "floor", "max_gap", "min_count"),
+                           ops.repair_params(repair_window, repair_threshold, repair_floor, repair_max_gap))) if repair_pose else None)
         segments = (behaviour_sigma, behaviour_grid) if behaviour_segments else None
         if segments is not None:   # refused before any work
             if behaviour_grid is not None:
@@ -681,13 +709,14 @@ class Core:
                 raise ValueError(f"behaviour_sigma must be finite and > 0 (it is {behaviour_sigma:g})")
         if self.is_primary:
             try:
-                self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait)
+                self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
+                                   repair)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
     def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False,
-                      behaviour_perplexity=None, segments=None, gait=None):
+                      behaviour_perplexity=None, segments=None, gait=None, repair=None):
         if behaviour_map and getattr(self, "num_images", None) is not None:   # too short for the perplexity: refused before any work
             ops.behaviour_map_points(self.num_images, behaviour_perplexity)
         result = {"points2d": np.copy(self.points2d)}
@@ -708,8 +737,9 @@ class Core:
             result["points2d_argmax"] = np.copy(self.points2d_argmax)
         if getattr(self, "_subpixel", False):   # only when this run refined its detections: without it the schema is the reference's
             result["subpixel"] = True
-        if joint_angles or rigid_legs or angle_spectrogram or behaviour_map or gait:   # opt-in, like the two keys above: else the reference's schema
-            result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait))
+        if joint_angles or rigid_legs or angle_spectrogram or behaviour_map or gait or repair:   # opt-in, like the two keys above: else the reference's schema
+            result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
+                                               repair))
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")
@@ -721,17 +751,26 @@ class Core:
                      "behaviour_labels", "behaviour_bouts", "behaviour_occupancy", "behaviour_transitions")
     _KINEMATIC_KEYS += _SEGMENT_KEYS + tuple(k + "_rigid" for k in _SEGMENT_KEYS)
 
-    def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity, segments=None, gait=None):
+    _REPAIR_KEYS = ("points3d_repaired", "repair_status", "repair_counts", "repair_score", "repair_params")
+
+    def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity, segments=None, gait=None, repair=None):
         """The keys save()'s flags append, in the result's order, all read from one PoseChain of this save's triangulation.
-        `segments`: None, or (sigma, grid) of the segmentation of every map.  `gait`: None, or the thresholds of the gait analysis."""
+        `segments`: None, or (sigma, grid) of the segmentation of every map.  `gait`: None, or the thresholds of the gait analysis.
+        `repair`: None, or the parameters of the pose repair; the one chain is then that of the repaired pose, repaired once."""
         what = ("joint_angles" if joint_angles else "rigid_legs" if rigid_legs else "angle_spectrogram" if angle_spectrogram
-                else "behaviour_map" if behaviour_map else "gait")
+                else "behaviour_map" if behaviour_map else "gait" if gait is not None else "repair_pose")
         spectra = angle_spectrogram or behaviour_map
         fps, bank = self._wavelet_bank(what, None, {}) if spectra else (None, {})   # save()'s fps and frequencies are the method's defaults
         if gait is not None and fps is None:
             fps = self._gait_fps(None)   # the same rule
-        chains = [self._measured_pose(what, fps)]
+        chains = [self._measured_pose(what, fps, repair)]
         keys, host = {}, lambda t: t.cpu().numpy()
+        repair_keys = {}
+        if repair is not None:
+            r = chains[0].repair
+            repair_keys = dict(zip(self._REPAIR_KEYS, (host(r.points), host(r.status), host(r.counts), host(r.score),
+                                                       np.array(r.params, dtype=np.float64))))
+            r = None   # the chain alone holds the repaired pose on the device, and is dropped below
         if joint_angles:
             keys["joint_angles"], keys["segment_lengths"] = map(host, chains[0].angles)
         if rigid_legs:
@@ -767,7 +806,7 @@ class Core:
             S = m = None   # released before the other variant's is computed: one float64 spectrogram at a time
         if angle_spectrogram:
             keys["spectrogram_freqs"], keys["spectrogram_fps"] = bank["freqs"], fps
-        return {**{k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}, **gait_keys}
+        return {**{k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}, **gait_keys, **repair_keys}
 
     # -- helpers --------------------------------------------------------------------------------------
     def _correction_for(self, corrections, cam_id, img_id):

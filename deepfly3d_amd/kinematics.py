@@ -1,6 +1,6 @@
 """`PoseChain`: the kinematic chain of one triangulated pose (DESIGN.md sections 14-19) -- body frame, joint angles, leg fit,
-unwrapping, wavelet spectrogram, behaviour map, its segmentation and the gait analysis -- with every stage that the default arguments
-reach computed once.
+unwrapping, wavelet spectrogram, behaviour map, its segmentation and the gait analysis, and the repair of the pose itself (section 20)
+-- with every stage that the default arguments reach computed once.
 
 A chain lives for one call of `Core`: each stage once per save, nothing kept between calls, because `camNet.points3d` changes under
 corrections and re-triangulation.  It keeps the small products (frame, fit, angles, the 48 series: a few KB per frame).  The
@@ -31,10 +31,10 @@ class PoseChain:
     """The chain of `points3d` [T, 38, 3] float64 cuda (the layout of points3d_wo_procrustes) sampled at `fps` (needed by the
     spectrogram and the gait analysis alone).  The attributes are the products of the default arguments, computed on first use; a
     method called with other arguments computes what it is asked for directly from `ops` and keeps nothing.  `measured`: the chain
-    whose recording frame this one shares (see rigid())."""
+    whose recording frame this one shares (see rigid()).  `repair`: the ops.PoseRepairResult this pose came from (see repaired())."""
 
-    def __init__(self, points3d, fps=None, measured=None):
-        self.points3d, self.fps, self.measured = points3d, fps, measured
+    def __init__(self, points3d, fps=None, measured=None, repair=None):
+        self.points3d, self.fps, self.measured, self.repair = points3d, fps, measured, repair
 
     @cached_property
     def frame(self):
@@ -53,6 +53,13 @@ class PoseChain:
         """A chain of the fitted pose, in the recording frame of THIS, the measured, pose: both sets of angles share one frame.  The
         fit is this chain's and computed once; the new chain's products are its own, so hold it."""
         return PoseChain(self.fit.points, self.fps, measured=self)
+
+    def repaired(self, **params):
+        """A chain of the repaired pose (ops.repair_pose; `params`: half_window, threshold, floor, max_gap, min_count), which keeps the
+        PoseRepairResult as `repair`.  Unlike rigid(), the new chain has its own recording frame -- the frame should profit from the
+        repair -- and its rigid() fits the repaired pose.  The repair is computed here, once: hold the chain."""
+        r = ops.repair_pose(self.points3d, **params)
+        return PoseChain(r.points, self.fps, repair=r)
 
     @cached_property
     def angles(self):

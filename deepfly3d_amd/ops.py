@@ -1,6 +1,6 @@
 """Thin host wrappers over the C ABI for the non-network kernels: arg-max and peaks, re-layout, triangulation, Procrustes and the
 video pose, and what DESIGN.md sections 9-19 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
-overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps, their segmentation and the gait analysis.
+overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps, their segmentation, the gait analysis and the pose repair.
 
 Inputs/outputs are torch CUDA tensors (device memory + stream plumbing only); every computation is a
 libdf3d_hip.so kernel.  No CPU fallback: a missing library or GPU raises `_native.NativeLibraryError`.
@@ -1206,6 +1206,111 @@ def gait(points3d, fps, body_frame="recording", on=None, off=None, half_window=N
     mean, count = gait_coupling(phase)
     pattern, histogram, counts = gait_patterns(states)
     return GaitResult(tip, vel, states, steps, metrics, phase, mean, count, pattern, histogram, counts, thresholds, fps)
+
+
+# ---- repair of the 3-D pose ---------------------------------------------------------------------------------
+@dataclasses.dataclass
+class PoseRepairResult:
+    """What `repair_pose` returns, device tensors but for the last: points [T, 38, 3] float64 (the repaired pose), status [T, 38] int8
+    (0 kept, 1 missing and filled, 2 outlier and filled, 3 missing and left, 4 outlier and removed), counts [38, 5] int64 (the frames
+    per joint and code), score [T, 38] float64 (the largest dev / threshold over the coordinates, NaN for a missing or untested joint)
+    and params (half_window, threshold, floor, max_gap, min_count)."""
+    points: torch.Tensor
+    status: torch.Tensor
+    counts: torch.Tensor
+    score: torch.Tensor
+    params: tuple
+
+
+def repair_params(half_window=None, threshold=None, floor=None, max_gap=None, min_count=None):
+    """(half_window, threshold, floor, max_gap, min_count) with config.REPAIR_HALF_WINDOW, REPAIR_THRESHOLD, REPAIR_FLOOR,
+    REPAIR_MAX_GAP and REPAIR_MIN_COUNT for what is None -- guesses nobody has measured on a recording.  ValueError: a half window that
+    is no integer in config.REPAIR_HALF_WINDOW_RANGE, a threshold that is not finite and > 0, a floor that is not finite and >= 0, a
+    max_gap that is no integer in config.REPAIR_MAX_GAP_RANGE, a min_count that is no integer in [1, 2 half_window + 1]."""
+    from . import config
+
+    def integer(v, lo, hi, name):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (it is {v!r})")
+        return int(v)
+
+    def number(v, name):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number (it is {v!r})")
+        return float(v)
+
+    h = integer(config.REPAIR_HALF_WINDOW if half_window is None else half_window, *config.REPAIR_HALF_WINDOW_RANGE, "half_window")
+    k = number(config.REPAIR_THRESHOLD if threshold is None else threshold, "threshold")
+    if not (np.isfinite(k) and k > 0.0):
+        raise ValueError(f"threshold must be finite and > 0 (it is {k:g})")
+    fl = number(config.REPAIR_FLOOR if floor is None else floor, "floor")
+    if not (np.isfinite(fl) and fl >= 0.0):
+        raise ValueError(f"floor must be finite and >= 0 (it is {fl:g})")
+    gap = integer(config.REPAIR_MAX_GAP if max_gap is None else max_gap, *config.REPAIR_MAX_GAP_RANGE, "max_gap")
+    n_min = integer(config.REPAIR_MIN_COUNT if min_count is None else min_count, 1, 2 * h + 1, "min_count")
+    return h, k, fl, gap, n_min
+
+
+def _need_pose(points3d):
+    if not (isinstance(points3d, torch.Tensor) and points3d.is_cuda and points3d.dtype == torch.float64 and points3d.dim() == 3
+            and tuple(points3d.shape[1:]) == (38, 3)):
+        raise ValueError("points3d must be a torch.float64 CUDA tensor of shape [T, 38, 3]")
+    return points3d.contiguous()
+
+
+@_on_tensor_device
+def pose_outliers(points3d, half_window=None, threshold=None, floor=None, min_count=None):
+    """(flags [T, 38] uint8, score [T, 38] float64) of points3d [T, 38, 3] (float64 cuda, the layout of points3d_wo_procrustes): a
+    Hampel test of every joint, one pass.  flags: bit 0 = the joint is missing (a non-finite coordinate, or all three 0), bit 1 = it
+    is an outlier: in some coordinate it lies further from the median of the valid frames of [t - half_window, t + half_window] than
+    max(threshold * 1.4826 * their median absolute deviation, floor).  A window with fewer than min_count valid frames is not tested.
+    score: the largest deviation / bound over the coordinates, NaN for a missing or untested joint.  Defaults: repair_params."""
+    from . import config
+
+    points3d = _need_pose(points3d)
+    h, k, fl, _, n_min = repair_params(half_window, threshold, floor, None, min_count)
+    T, dev = points3d.shape[0], points3d.device
+    flags = torch.empty((T, 38), dtype=torch.uint8, device=dev)
+    score = torch.empty((T, 38), dtype=torch.float64, device=dev)
+    if T:
+        _bmap_call("df3d_repair_outliers", points3d.data_ptr(), T, h, k * config.REPAIR_MAD_TO_SIGMA, fl, n_min, flags.data_ptr(),
+                   score.data_ptr(), _stream(points3d))
+    return flags, score
+
+
+@_on_tensor_device
+def fill_gaps(points3d, flags, max_gap=None):
+    """(points [T, 38, 3] float64, status [T, 38] int8, counts [38, 5] int64) of points3d [T, 38, 3] (float64 cuda) and flags [T, 38]
+    (uint8 cuda, pose_outliers'): a joint whose flags are not 0 is interpolated linearly between its last good frame before and its
+    first good frame after, where both exist and at most max_gap frames lie between them, and set to 0 -- missing -- otherwise.  Good
+    joints keep their bits; nothing is extrapolated.  status: 0 kept, 1 missing and filled, 2 outlier and filled, 3 missing and left,
+    4 outlier and removed; counts: the frames per joint and code."""
+    points3d = _need_pose(points3d)
+    T, dev = points3d.shape[0], points3d.device
+    if not (isinstance(flags, torch.Tensor) and flags.dtype == torch.uint8 and flags.device == dev and tuple(flags.shape) == (T, 38)):
+        raise ValueError(f"flags must be a torch.uint8 tensor of shape [{T}, 38] on the device of points3d")
+    flags = flags.contiguous()
+    gap = repair_params(max_gap=max_gap)[3]
+    points = torch.empty_like(points3d)
+    status = torch.empty((T, 38), dtype=torch.int8, device=dev)
+    counts = torch.zeros((38, 5), dtype=torch.int64, device=dev)
+    if T:
+        need = _native.load().df3d_repair_work_bytes(T)
+        if need <= 0:
+            raise ValueError(f"no workspace for T = {T} frames: T must be at most (2^31 - 1) / 38")
+        work = torch.empty((need,), dtype=torch.uint8, device=dev)
+        _bmap_call("df3d_repair_fill", points3d.data_ptr(), flags.data_ptr(), T, gap, points.data_ptr(), status.data_ptr(), counts.data_ptr(),
+                   work.data_ptr(), need, _stream(points3d))
+    return points, status, counts
+
+
+def repair_pose(points3d, half_window=None, threshold=None, floor=None, max_gap=None, min_count=None):
+    """The repaired pose of points3d [T, 38, 3] (float64 cuda), a PoseRepairResult: pose_outliers, then
+    fill_gaps of its flags."""
+    params = repair_params(half_window, threshold, floor, max_gap, min_count)   # refused before any work
+    flags, score = pose_outliers(points3d, params[0], params[1], params[2], params[4])
+    points, status, counts = fill_gaps(points3d, flags, params[3])
+    return PoseRepairResult(points, status, counts, score, params)
 
 
 def gaussian_window_taps(window_size, sigma, truncate=4.0):

@@ -456,6 +456,36 @@ int df3d_gait_patterns(const int* states_dev, long long T, int* pattern_dev, lon
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a16 repair of the 3-D pose (the model is this project's own specification, defined in float64 by
+ *     tests/pose_repair_oracle.py): a Hampel test of every joint, then linear filling of short gaps.  All arrays are DEVICE arrays,
+ *     row-major.  pts [T, 38, 3] float64 in the layout of points3d_wo_procrustes; a joint is missing by df3d_joint_angles' rule (a
+ *     non-finite coordinate, or all three exactly 0).  No floating-point atomics, no fused multiply-add: the outputs are the oracle's
+ *     bits, and two calls give the same.
+ * df3d_repair_outliers: flags [T, 38] uint8, bit 0 = missing, bit 1 = outlier.  For a joint that is not missing at t, V = the frames of
+ *     [max(t - half_window, 0), min(t + half_window, T - 1)] where it is not missing, n = |V|.  n < min_count: untested (flags 0,
+ *     score NaN).  Else per coordinate m = median over V, dev_s = |x_s - m|, mad = median of dev over V, thr = max(scale mad, floor);
+ *     an outlier where dev_t > thr in any coordinate.  The median of an even count is the mean of the two middle values.  `scale` is
+ *     the threshold times 1.4826, formed by the caller.  score [T, 38] float64 (may be null: not written) = the largest over the
+ *     coordinates of dev_t / thr (0 where dev_t = 0, +inf where thr = 0 < dev_t), NaN for a missing or untested joint.  The test is
+ *     not iterated.
+ * df3d_repair_fill: a joint is bad where its flags are not 0.  With a the last good frame before t and b the first after it, the gap
+ *     is filled when both exist and b - a - 1 <= max_gap: out = x_a + (x_b - x_a) ((t - a) / (b - a)); otherwise out = +0.0, which
+ *     is missing.  Good joints keep their bits.  status [T, 38] int8: 0 kept, 1 missing and filled, 2 outlier and filled, 3 missing
+ *     and left, 4 outlier and removed (bit 0 decides where both are set); counts [38, 5] int64: the frames per joint and code.
+ * df3d_repair_work_bytes(T): the bytes of the caller-owned workspace of df3d_repair_fill at this T (0 where T is out of range).
+ * DF3D_EINVAL before the device is touched, with a message that names the argument: T negative or above (2^31 - 1) / 38;
+ *     half_window outside [1, 64]; scale not finite or <= 0; floor not finite or < 0; min_count outside [1, 2 half_window + 1];
+ *     max_gap outside [0, 1000000]; a null (score excepted), misaligned (16 bytes for work, 8 for float64 and int64) or overlapping
+ *     buffer; a workspace below the query.  T = 0 launches nothing and returns DF3D_OK.  Every launching entry is asynchronous on
+ *     `stream`, allocates nothing and keeps no host pointer.
+ * ---------------------------------------------------------------------------------------------- */
+long long df3d_repair_work_bytes(long long T);
+int df3d_repair_outliers(const double* pts_dev, long long T, int half_window, double scale, double floor, int min_count,
+                         unsigned char* flags_dev, double* score_dev, void* stream);
+int df3d_repair_fill(const double* pts_dev, const unsigned char* flags_dev, long long T, int max_gap, double* out_dev,
+                     signed char* status_dev, long long* counts_dev, void* work_dev, long long work_len_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
