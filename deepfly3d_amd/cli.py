@@ -110,6 +110,18 @@ def parse_cli_args(argv=None):
     p.add_argument("--gait-off", dest="gait_off", type=float, default=None, metavar="V",
                    help="With --gait: the anterior tip velocity below which a leg goes into stance (default 0, a guess like --gait-on); it must "
                         "lie below --gait-on")
+    p.add_argument("--treadmill", dest="treadmill", action="store_true",
+                   help="Estimate the treadmill ball and the fictive walking path from the leg tips in stance: one sphere through the stance "
+                        "tips, the ball's rotation in every frame from their velocities, and the path the fly would have walked.  Appends, "
+                        "after the gait keys, treadmill_ball_center [3], treadmill_ball_radius, treadmill_ball_rms, treadmill_ball_count, "
+                        "treadmill_ball_status (bit 0: the fit was refused), treadmill_rotation [T, 3] (rad/s), treadmill_legs [T], "
+                        "treadmill_residual [T], treadmill_fictive [T, 3] (forward and sideways speed in mm/s, yaw rate in rad/s), "
+                        "treadmill_path [T, 3] (x, y, heading), treadmill_skipped, treadmill_params and treadmill_fps to the result.  The "
+                        "swing thresholds are --gait's defaults, guesses that nobody has measured on a recording; a spiked tip shows here "
+                        "first, which --repair-pose is for.  Works with --skip-pose-estimation on an earlier result")
+    p.add_argument("--ball-radius", dest="ball_radius", type=float, default=None, metavar="MM",
+                   help="With --treadmill: the ball's known radius in pose units (mm); without it the radius is fitted, and noise on the "
+                        "tips biases the fitted radius low")
     p.add_argument("--repair-pose", dest="repair_pose", action="store_true",
                    help="Repair the triangulated pose before the kinematics: a joint that lies further from the median of the frames round it "
                         "than --repair-threshold robust deviations (a Hampel test, per coordinate, one pass) is an outlier; outliers and missing "
@@ -141,6 +153,15 @@ def parse_cli_args(argv=None):
             ops.repair_params(args.repair_window, args.repair_threshold, args.repair_floor, args.repair_max_gap)
         except ValueError as e:
             p.error(f"--repair-window, --repair-threshold, --repair-floor and --repair-max-gap: {e}")
+    if args.ball_radius is not None and not args.treadmill:
+        p.error("--ball-radius sets the radius of --treadmill: it needs --treadmill")
+    if args.treadmill:
+        from . import ops
+
+        try:
+            ops.treadmill_params(args.ball_radius)
+        except ValueError as e:
+            p.error(f"--ball-radius: {e}")
     if args.gait_on is not None and not args.gait:
         p.error("--gait-on sets the swing threshold of --gait: it needs --gait")
     if args.gait_off is not None and not args.gait:
@@ -206,13 +227,16 @@ _NO_IMAGES = ("--video-heatmap draws the heat-maps the network computes from the
 def run(args):
     video_heatmap = getattr(args, "video_heatmap", False)
     # what the second save appends to the result: the kinematics flags, in the order of their keys, and the map's perplexity
-    extras = {name: getattr(args, name, False) for name in ("joint_angles", "rigid_legs", "angle_spectrogram", "behaviour_map", "gait", "repair_pose")}
+    extras = {name: getattr(args, name, False) for name in ("joint_angles", "rigid_legs", "angle_spectrogram", "behaviour_map", "gait", "treadmill",
+                                                                "repair_pose")}
     flagged = [name for name, on in extras.items() if on]
     extras["behaviour_perplexity"] = getattr(args, "behaviour_perplexity", None)
     if getattr(args, "behaviour_segments", False):   # the map's segmentation: no keys of its own flag without --behaviour-map
         extras.update(behaviour_segments=True, behaviour_sigma=getattr(args, "behaviour_sigma", None), behaviour_grid=getattr(args, "behaviour_grid", None))
     if extras["gait"]:
         extras.update(gait_on=getattr(args, "gait_on", None), gait_off=getattr(args, "gait_off", None))
+    if extras["treadmill"]:
+        extras.update(ball_radius=getattr(args, "ball_radius", None))
     if extras["repair_pose"]:
         extras.update({name: getattr(args, name, None) for name in ("repair_window", "repair_threshold", "repair_floor", "repair_max_gap")})
     if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not flagged:

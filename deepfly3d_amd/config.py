@@ -137,6 +137,19 @@ REPAIR_MAX_GAP = 10
 REPAIR_MAX_GAP_RANGE = (0, 1000000)
 REPAIR_MAD_TO_SIGMA = 1.4826   # the median absolute deviation of a normal sample times this estimates its standard deviation
 
+# ---- the treadmill ball and the fictive path.  One sphere is fitted to the stance tips of a recording; with a
+# known radius its centre takes BALL_FIT_ITERATIONS Gauss-Newton steps (within BALL_FIT_ITERATIONS_RANGE) from the algebraic centre.
+# A fit is refused where a Cholesky pivot of its normal matrix is at or below BALL_PIVOT_MIN times the largest diagonal entry; a
+# frame's rotation is NaN with fewer than BALL_MIN_LEGS stance legs (within BALL_MIN_LEGS_RANGE; one leg leaves the spin about its own
+# radius free) or with a pivot at or below BALL_FRAME_PIVOT_MIN times the trace.  Each default is a guess: the 8 steps were enough on
+# planted data alone (the step fell below 1e-12 by step 7 at 0.1 mm of tip noise), and nobody has measured any of them on a recording.
+BALL_FIT_ITERATIONS = 8
+BALL_FIT_ITERATIONS_RANGE = (1, 64)
+BALL_PIVOT_MIN = 1e-10
+BALL_MIN_LEGS = 2
+BALL_MIN_LEGS_RANGE = (2, 6)
+BALL_FRAME_PIVOT_MIN = 1e-10
+
 # ---- which camera sees which joint (reference df3d/skeleton_fly.py:202-250), by camera id: cameras 0-2 look at the side whose
 # joints are 0..18, cameras 4-6 at the side of joints 19..37, camera 3 faces the fly.  Pinned by tests/golden/skeleton_tables.npz.
 # Where df3d::relayout_source (csrc/geometry_dev.h) fills a joint of a side camera under the identity ordering, this table sees it;

@@ -499,6 +499,42 @@ class Core:
                 host(g.coupling_count), host(g.pattern), host(g.pattern_histogram), host(g.state_counts), np.array(g.thresholds, dtype=np.float64),
                 g.fps)
 
+    _TREADMILL_KEYS = ("treadmill_ball_center", "treadmill_ball_radius", "treadmill_ball_rms", "treadmill_ball_count", "treadmill_ball_status",
+                       "treadmill_rotation", "treadmill_legs", "treadmill_residual", "treadmill_fictive", "treadmill_path", "treadmill_skipped",
+                       "treadmill_params", "treadmill_fps")
+
+    def treadmill(self, fps=None, radius=None, on=None, off=None, half_window=None, min_legs=None, repair=False):
+        """The treadmill ball and the fictive walking path (ops.treadmill) of the triangulation `camNet.points3d`
+        in the recording's body frame, an ops.TreadmillResult of numpy arrays: tip and vel [T, 6, 3] (every leg's tip relative to the
+        mean of the coxa medians and its velocity, in body coordinates), states [T, 6] int32, ball (an ops.BallFit: center [3], radius,
+        rms, count, status -- bit 0: the fit was refused and everything after it is NaN), rotation [T, 3] (the ball's rotation
+        vector, rad/s), legs [T] int32 (the stance legs it was fitted to), residual [T], fictive [T, 3] (forward and sideways speed
+        in pose units (mm) per second, yaw rate in rad/s), path [T, 3] (x, y, theta), skipped (the frames that moved nothing), params
+        (radius or NaN, on, off, half_window, min_legs, iterations) and fps.  `radius`: the ball's known radius in mm; None fits it,
+        and noise biases the fitted radius low.  `fps`, `on`, `off`, `half_window`: gait()'s; `min_legs`: config.BALL_MIN_LEGS.  Every
+        default is a guess nobody has measured on a recording.  `repair=True`: of the repaired pose (repair_pose() with its
+        defaults), which is what a spiked tip asks for.  A rank-0 method with joint_angles' refusals."""
+        params = dict(zip(("radius", "min_legs"), ops.treadmill_params(radius, min_legs)))   # refused before any work
+        params.update(zip(("on", "off", "half_window"), ops.gait_thresholds(on, off, half_window)))
+        chain = self._measured_pose("treadmill", ops._gait_fps(self._gait_fps(fps)), repair)
+        r = chain.treadmill(**params)
+        host = lambda v: v.cpu().numpy() if isinstance(v, torch.Tensor) else v   # noqa: E731
+        values = {f.name: host(getattr(r, f.name)) for f in dataclasses.fields(r)}
+        values["ball"] = ops.BallFit(host(r.ball.ball), host(r.ball.info), host(r.ball.sums))
+        values["skipped"] = int(values["skipped"])
+        return ops.TreadmillResult(**values)
+
+    @staticmethod
+    def _treadmill_values(r, thresholds=None):
+        """The values of _TREADMILL_KEYS from a TreadmillResult of device tensors.  `thresholds`: the (on, off) behind states that were
+        handed in, for the stored parameters."""
+        host = lambda t: t.cpu().numpy()   # noqa: E731
+        ball, info = host(r.ball.ball), host(r.ball.info)
+        if thresholds is not None:
+            r = dataclasses.replace(r, params=(r.params[0], *thresholds, *r.params[3:]))
+        return (ball[:3].copy(), float(ball[3]), float(ball[4]), int(info[0]), int(info[1]), host(r.rotation), host(r.legs), host(r.residual),
+                host(r.fictive), host(r.path), int(r.skipped.item()), np.array(r.params, dtype=np.float64), r.fps)
+
     # -- manual corrections (DESIGN.md section 11; reference df3d/core.py:253-296, 477-479, 509-544) ---------------------------------
     _MOVE_THRESHOLD = 30   # pixels, per coordinate: a pose that differs less from the estimate on every checked joint is not stored
 
@@ -659,7 +695,7 @@ class Core:
 
     def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False, behaviour_perplexity=None,
              behaviour_segments=False, behaviour_sigma=None, behaviour_grid=None, gait=False, gait_on=None, gait_off=None, repair_pose=False,
-             repair_window=None, repair_threshold=None, repair_floor=None, repair_max_gap=None):
+             repair_window=None, repair_threshold=None, repair_floor=None, repair_max_gap=None, treadmill=False, ball_radius=None):
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
         keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras).
         `rigid_legs=True` appends, after those, "points3d_rigid", "rigid_segment_lengths" and "rigid_fit_cost" (Core.rigid_legs()) and,
@@ -683,7 +719,14 @@ class Core:
         and `repair_max_gap`; the defaults are guesses nobody has measured on a recording): "points3d_repaired" [T, 38, 3],
         "repair_status" [T, 38] int8, "repair_counts" [38, 5], "repair_score" [T, 38] and "repair_params" (half_window, threshold,
         floor, max_gap, min_count); every other opt-in key of the same save is then computed from the repaired pose, which is repaired
-        once.  "points3d" and "points3d_wo_procrustes" stay the triangulation's own."""
+        once.  "points3d" and "points3d_wo_procrustes" stay the triangulation's own.  `treadmill=True` appends, after the gait keys and
+        before the repair keys, the treadmill ball and the fictive path of this save's triangulation (Core.treadmill() with its
+        defaults and the known radius `ball_radius`, in mm; None fits the radius): "treadmill_ball_center" [3],
+        "treadmill_ball_radius", "treadmill_ball_rms", "treadmill_ball_count", "treadmill_ball_status" (bit 0: refused),
+        "treadmill_rotation" [T, 3], "treadmill_legs" [T] int32, "treadmill_residual" [T], "treadmill_fictive" [T, 3] (forward,
+        sideways, yaw rate), "treadmill_path" [T, 3] (x, y, theta), "treadmill_skipped", "treadmill_params" (radius or NaN, on, off,
+        half_window, min_legs, iterations) and "treadmill_fps".  There are no "_rigid" twins: the ball is one object.  Together with
+        gait, the swing/stance states of the measured pose are computed once and shared."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
@@ -701,6 +744,9 @@ class Core:
             raise ValueError("repair_window, repair_threshold, repair_floor and repair_max_gap belong to repair_pose: they need repair_pose=True")
         repair = (dict(zip(("half_window", "threshold", "floor", "max_gap", "min_count"),
                            ops.repair_params(repair_window, repair_threshold, repair_floor, repair_max_gap))) if repair_pose else None)
+        if ball_radius is not None and not treadmill:
+            raise ValueError("ball_radius belongs to treadmill: it needs treadmill=True")
+        treadmill = {"radius": ops.treadmill_params(ball_radius)[0]} if treadmill else None   # refused before any work
         segments = (behaviour_sigma, behaviour_grid) if behaviour_segments else None
         if segments is not None:   # refused before any work
             if behaviour_grid is not None:
@@ -710,13 +756,13 @@ class Core:
         if self.is_primary:
             try:
                 self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
-                                   repair)
+                                   repair, treadmill)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
     def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False,
-                      behaviour_perplexity=None, segments=None, gait=None, repair=None):
+                      behaviour_perplexity=None, segments=None, gait=None, repair=None, treadmill=None):
         if behaviour_map and getattr(self, "num_images", None) is not None:   # too short for the perplexity: refused before any work
             ops.behaviour_map_points(self.num_images, behaviour_perplexity)
         result = {"points2d": np.copy(self.points2d)}
@@ -737,9 +783,10 @@ class Core:
             result["points2d_argmax"] = np.copy(self.points2d_argmax)
         if getattr(self, "_subpixel", False):   # only when this run refined its detections: without it the schema is the reference's
             result["subpixel"] = True
-        if joint_angles or rigid_legs or angle_spectrogram or behaviour_map or gait or repair:   # opt-in, like the two keys above: else the reference's schema
+        # opt-in, like the two keys above: else the reference's schema
+        if joint_angles or rigid_legs or angle_spectrogram or behaviour_map or gait or repair or treadmill:
             result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
-                                               repair))
+                                               repair, treadmill))
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")
@@ -753,15 +800,17 @@ class Core:
 
     _REPAIR_KEYS = ("points3d_repaired", "repair_status", "repair_counts", "repair_score", "repair_params")
 
-    def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity, segments=None, gait=None, repair=None):
+    def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity, segments=None, gait=None, repair=None,
+                        treadmill=None):
         """The keys save()'s flags append, in the result's order, all read from one PoseChain of this save's triangulation.
         `segments`: None, or (sigma, grid) of the segmentation of every map.  `gait`: None, or the thresholds of the gait analysis.
-        `repair`: None, or the parameters of the pose repair; the one chain is then that of the repaired pose, repaired once."""
+        `repair`: None, or the parameters of the pose repair; the one chain is then that of the repaired pose, repaired once.
+        `treadmill`: None, or the parameters of the treadmill analysis; with `gait` it takes the measured pose's states from that."""
         what = ("joint_angles" if joint_angles else "rigid_legs" if rigid_legs else "angle_spectrogram" if angle_spectrogram
-                else "behaviour_map" if behaviour_map else "gait" if gait is not None else "repair_pose")
+                else "behaviour_map" if behaviour_map else "gait" if gait is not None else "treadmill" if treadmill is not None else "repair_pose")
         spectra = angle_spectrogram or behaviour_map
         fps, bank = self._wavelet_bank(what, None, {}) if spectra else (None, {})   # save()'s fps and frequencies are the method's defaults
-        if gait is not None and fps is None:
+        if (gait is not None or treadmill is not None) and fps is None:
             fps = self._gait_fps(None)   # the same rule
         chains = [self._measured_pose(what, fps, repair)]
         keys, host = {}, lambda t: t.cpu().numpy()
@@ -779,10 +828,18 @@ class Core:
             keys["rigid_segment_lengths"] = np.array(chains[0].fit.lengths)
             if joint_angles:
                 keys["joint_angles_rigid"] = host(chains[1].angles[0])
-        gait_keys = {}
+        gait_keys, states = {}, None
         if gait is not None:   # the rigid chain is the fit computed above: it never runs twice
             for tag, chain in zip(("", "_rigid"), chains):
-                gait_keys.update({k + tag: v for k, v in zip(self._GAIT_KEYS, self._gait_values(chain.gait(**gait)))})
+                g = chain.gait(**gait)
+                if not tag and treadmill is not None:
+                    states = g.states   # save()'s gait and treadmill share thresholds and window: the states are the same
+                gait_keys.update({k + tag: v for k, v in zip(self._GAIT_KEYS, self._gait_values(g))})
+                g = None
+        if treadmill is not None:   # of the measured (or repaired) pose alone: the ball is one object
+            shared = None if states is None else (gait["on"], gait["off"])
+            gait_keys.update(zip(self._TREADMILL_KEYS, self._treadmill_values(chains[0].treadmill(states, **treadmill), shared)))
+            states = None
         # The spectra read the [T, 48] series alone, and those wait on the host too (384 bytes per frame).  Everything the chains hold
         # is dropped with them, so that a map runs beside its own spectrogram and nothing else, as it did when every key started anew.
         dev = chains[0].points3d.device

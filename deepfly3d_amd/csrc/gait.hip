@@ -26,37 +26,22 @@
 
 #include "buffer_check.h"
 #include "common.h"
+#include "gait_dev.h"
 
 // Built with -ffp-contract=off (build.py): the tip and the velocity are the oracle's subtractions, products and sums one by one, never
 // a fused multiply-add, and the thresholds then see the numbers the bar of the velocity was derived for.
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / df3d::WAVE;
-constexpr int JOINTS = 38;
-constexpr int LEGS = 6;
-constexpr int HALF_MIN = 1, HALF_MAX = 64;
+using namespace df3d::gait_dev;   // the vectors, the missing rule, the window and the block scan, shared with treadmill.hip
+
 constexpr int EVENT_SERIES = 4;                  // last lift-off, first lift-off (reversed), last unknown, last touch-down
 constexpr int SCAN_ROWS = EVENT_SERIES * LEGS;   // the most rows one max-scan call carries
 constexpr int SLICE = 2048;                      // frames per block of the coupling: a constant, never the CU count
 constexpr int SLICE_PER_LANE = SLICE / THREADS;
 constexpr int PAIRS = LEGS * (LEGS + 1) / 2;     // i <= j
 constexpr int PATTERNS = 64;
-constexpr long long T_MAX = 0x7fffffffLL / LEGS;   // 6 T flags are numbered by an int32 sum-scan
 constexpr double TWO_PI = 6.283185307179586476925286766559;
-
-struct V3 {
-    double x, y, z;
-};
-
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 load3(const double* p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ bool finite3(V3 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
-
-// section 14's rule: all three coordinates exactly zero (the DLT's "fewer than two views"), or any of them not finite
-__device__ __forceinline__ bool missing(V3 p) { return (p.x == 0.0 && p.y == 0.0 && p.z == 0.0) || !finite3(p); }
 
 // ------------------------------------------------------------------------------------------------------------------ tip, velocity
 __global__ __launch_bounds__(THREADS) void gait_velocity_kernel(const double* __restrict__ pts, long long T, const double* __restrict__ frames,
@@ -67,7 +52,7 @@ __global__ __launch_bounds__(THREADS) void gait_velocity_kernel(const double* __
     const long long t = g / LEGS;
     const int leg = (int)(g - t * LEGS);
     const int side = leg / 3;
-    const size_t coxa = 19 * side + 5 * (leg - 3 * side);   // P0; the tip P4 is four joints on
+    const size_t coxa = (size_t)coxa_of(leg);   // P0; the tip P4 is four joints on
     const double* F = frames + (per_frame ? (size_t)t * 9 : 0);
     const V3 ex = load3(F), ey = load3(F + 3), ez = load3(F + 6);
     const bool frame_ok = finite3(ex) && finite3(ey) && finite3(ez);
@@ -82,7 +67,8 @@ __global__ __launch_bounds__(THREADS) void gait_velocity_kernel(const double* __
     tp[1] = tip_ok ? sigma * dot(r, ey) : nan;
     tp[2] = tip_ok ? dot(r, ez) : nan;
 
-    const long long a = t - w > 0 ? t - w : 0, b = t + w < T - 1 ? t + w : T - 1;
+    long long a, b;
+    window(t, w, T, a, b);
     const V3 Pa = load3(pts + ((size_t)a * JOINTS + coxa + 4) * 3), Pb = load3(pts + ((size_t)b * JOINTS + coxa + 4) * 3);
     const V3 d = sub(Pb, Pa);
     const bool vel_ok = frame_ok && b > a && !missing(Pa) && !missing(Pb);
@@ -97,21 +83,7 @@ __global__ __launch_bounds__(THREADS) void gait_velocity_kernel(const double* __
 // The inclusive max-scan of v over the block; `exclusive`: that of the lanes before this one (-1 for lane 0); `total`: the block's
 // max.  lds: THREADS ints.
 __device__ __forceinline__ int block_max_scan(int v, int* lds, int& exclusive, int& total) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    int s = v;
-    for (int o = 1; o < THREADS; o <<= 1) {
-        const int other = t >= o ? lds[t - o] : -1;
-        __syncthreads();
-        s = s > other ? s : other;
-        lds[t] = s;
-        __syncthreads();
-    }
-    exclusive = t ? lds[t - 1] : -1;
-    total = lds[THREADS - 1];
-    __syncthreads();   // the next call may write lds
-    return s;
+    return block_scan(v, -1, MaxOp(), lds, exclusive, total);
 }
 
 // series [rows, T] int32, every entry -1 or its own index.  blockIdx.y = the row.  sums [rows, nb].
@@ -214,20 +186,9 @@ __global__ __launch_bounds__(THREADS) void gait_step_flags_kernel(const int* __r
 
 // The exclusive scan of v over the block, the block's sum in `total` (the scan of behaviour_segment.hip).  lds: THREADS ints.
 __device__ __forceinline__ int block_exclusive_sum(int v, int* lds, int& total) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    int s = v;
-    for (int o = 1; o < THREADS; o <<= 1) {
-        const int add = t >= o ? lds[t - o] : 0;
-        __syncthreads();
-        s += add;
-        lds[t] = s;
-        __syncthreads();
-    }
-    total = lds[THREADS - 1];
-    __syncthreads();
-    return s - v;
+    int exclusive;
+    block_scan(v, 0, SumOp(), lds, exclusive, total);
+    return exclusive;
 }
 
 __global__ __launch_bounds__(THREADS) void gait_sum_blocks_kernel(const int* __restrict__ in, long long n, int* __restrict__ sums) {
@@ -417,10 +378,7 @@ __global__ __launch_bounds__(THREADS) void gait_pattern_kernel(const int* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host side
-long long round64(long long b) { return (b + 63) / 64 * 64; }
-long long blocks_of(long long n) { return (n + THREADS - 1) / THREADS; }
 long long slices_of(long long T) { return (T + SLICE - 1) / SLICE; }
-unsigned grid_of(long long n) { return (unsigned)blocks_of(n); }
 
 // One workspace layout serves every entry: the scanned series [24, T] and their block results [24, nb], the step flags and their
 // numbers [6 T] with the sum-scan's block results, and the coupling's partials [slices, 36, 3].
@@ -439,11 +397,6 @@ Layout layout_of(long long T) {
     l.bytes = l.coupling + round64(slices_of(T) * LEGS * LEGS * 3 * 8);
     if (l.bytes < 64) l.bytes = 64;   // 0 is the answer for a T outside the range
     return l;
-}
-
-template <typename P>
-P* at(void* work, long long offset) {
-    return reinterpret_cast<P*>(static_cast<char*>(work) + offset);
 }
 
 // series [rows, T] -> its inclusive max-scan along T, in place

@@ -1,6 +1,6 @@
 """`PoseChain`: the kinematic chain of one triangulated pose (DESIGN.md sections 14-19) -- body frame, joint angles, leg fit,
-unwrapping, wavelet spectrogram, behaviour map, its segmentation and the gait analysis, and the repair of the pose itself (section 20)
--- with every stage that the default arguments reach computed once.
+unwrapping, wavelet spectrogram, behaviour map, its segmentation, the gait analysis and the treadmill ball (section 21), and the
+repair of the pose itself (section 20) -- with every stage that the default arguments reach computed once.
 
 A chain lives for one call of `Core`: each stage once per save, nothing kept between calls, because `camNet.points3d` changes under
 corrections and re-triangulation.  It keeps the small products (frame, fit, angles, the 48 series: a few KB per frame).  The
@@ -102,3 +102,10 @@ class PoseChain:
         if self.fps is None:
             raise ValueError("this chain was built without the recording's fps, which the tip velocity needs")
         return ops.gait(self.points3d, self.fps, self.frame, **thresholds)
+
+    def treadmill(self, states=None, **params):
+        """ops.treadmill (a TreadmillResult) of this pose at this chain's fps in the recording frame; `states`: the states of a gait
+        analysis of this pose that its caller already holds; `params`: radius, on, off, half_window, min_legs, iterations.  Not kept."""
+        if self.fps is None:
+            raise ValueError("this chain was built without the recording's fps, which the tip velocity needs")
+        return ops.treadmill(self.points3d, self.fps, self.frame, states, **params)

@@ -1,6 +1,7 @@
 """Thin host wrappers over the C ABI for the non-network kernels: arg-max and peaks, re-layout, triangulation, Procrustes and the
 video pose, and what DESIGN.md sections 9-19 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
-overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps, their segmentation, the gait analysis and the pose repair.
+overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps, their segmentation, the gait analysis, the pose repair and
+the treadmill ball (section 21).
 
 Inputs/outputs are torch CUDA tensors (device memory + stream plumbing only); every computation is a
 libdf3d_hip.so kernel.  No CPU fallback: a missing library or GPU raises `_native.NativeLibraryError`.
@@ -1206,6 +1207,208 @@ def gait(points3d, fps, body_frame="recording", on=None, off=None, half_window=N
     mean, count = gait_coupling(phase)
     pattern, histogram, counts = gait_patterns(states)
     return GaitResult(tip, vel, states, steps, metrics, phase, mean, count, pattern, histogram, counts, thresholds, fps)
+
+
+# ---- the treadmill ball and the fictive walking path --------------------------------------------------------
+@dataclasses.dataclass
+class BallFit:
+    """What `fit_ball` returns, device tensors that nothing reads back: ball [8] float64 (centre, radius, rms and three zeros, the
+    layout df3d_ball_rotation reads), info [2] int64 (count, status) and sums [17] float64 (the folded slice sums of the algebraic
+    fit, include/df3d_hip.h).  center, radius, rms, count and status are views of them.  status bit 0: the fit was refused (centre,
+    radius and rms NaN); bit 1: a known-radius fit without an algebraic centre, started beyond the tips' mean."""
+    ball: torch.Tensor
+    info: torch.Tensor
+    sums: torch.Tensor
+
+    center = property(lambda self: self.ball[:3])
+    radius = property(lambda self: self.ball[3])
+    rms = property(lambda self: self.ball[4])
+    count = property(lambda self: self.info[0])
+    status = property(lambda self: self.info[1])
+
+
+@dataclasses.dataclass
+class TreadmillResult:
+    """What `treadmill` returns, device tensors but for the last two: tip, vel [T, 6, 3] float64 (body_tips), states [T, 6] int32, ball
+    (a BallFit), rotation [T, 3] float64 (rad/s, body coordinates), legs [T] int32, residual [T] and fictive [T, 3] (forward mm/s,
+    sideways mm/s, yaw rad/s; ball_rotation), path [T, 3] (x, y, theta) and skipped (a 0-dim int64 tensor; fictive_path), params
+    (radius or NaN, on, off, half_window, min_legs, iterations; on and off NaN where the states were handed in) and fps."""
+    tip: torch.Tensor
+    vel: torch.Tensor
+    states: torch.Tensor
+    ball: BallFit
+    rotation: torch.Tensor
+    legs: torch.Tensor
+    residual: torch.Tensor
+    fictive: torch.Tensor
+    path: torch.Tensor
+    skipped: torch.Tensor
+    params: tuple
+    fps: float
+
+
+def treadmill_params(radius=None, min_legs=None, iterations=None):
+    """(radius or None, min_legs, iterations) with config.BALL_MIN_LEGS and BALL_FIT_ITERATIONS for what is None -- guesses nobody has
+    measured on a recording.  ValueError: a radius that is no finite number > 0, a min_legs that is no integer in
+    config.BALL_MIN_LEGS_RANGE, iterations that are no integer in config.BALL_FIT_ITERATIONS_RANGE."""
+    from . import config
+
+    if radius is not None:
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not (np.isfinite(radius) and radius > 0):
+            raise ValueError(f"radius must be a finite number > 0 (it is {radius!r})")
+        radius = float(radius)
+    out = []
+    for v, default, (lo, hi), name in ((min_legs, config.BALL_MIN_LEGS, config.BALL_MIN_LEGS_RANGE, "min_legs"),
+                                       (iterations, config.BALL_FIT_ITERATIONS, config.BALL_FIT_ITERATIONS_RANGE, "iterations")):
+        v = default if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (it is {v!r})")
+        out.append(int(v))
+    return (radius, *out)
+
+
+def _ball_work(T, device):
+    need = _native.load().df3d_ball_work_bytes(int(T))
+    if need <= 0:
+        raise ValueError(f"no workspace for T = {T} frames: T must be at most (2^31 - 1) / 6")
+    return torch.empty((need,), dtype=torch.uint8, device=device), need
+
+
+def _same_frames(t, T, dev, name):
+    if t.shape[0] != T or t.device != dev:
+        raise ValueError(f"{name} must hold the {T} frames of tips, on their device")
+
+
+@_on_tensor_device
+def body_tips(points3d, fps, body_frame="recording", half_window=None):
+    """(tips, vel), both [T, 6, 3] float64, of points3d [T, 38, 3] (float64 cuda, the layout of points3d_wo_procrustes) sampled at
+    `fps`: every leg's tip in the recording's body frame, F (P4 - o) with o the mean of the six body-coxa temporal medians -- neither
+    mirrored nor relative to the coxa, unlike tip_kinematics -- and its velocity F (P4[b] - P4[a]) fps / (b - a) over gait's window.
+    `body_frame`: "recording" or an explicit [3, 3] array or tensor (rows ex, ey, ez).  NaN where the tip is missing (the velocity: at
+    a or at b), where the window is empty (T = 1) or where the frame or o holds a non-finite number."""
+    points3d = _need_pose(points3d)
+    fps, w = _gait_fps(fps), gait_thresholds(half_window=half_window)[2]
+    T, dev = points3d.shape[0], points3d.device
+    if isinstance(body_frame, str):
+        if body_frame != "recording":
+            raise ValueError('body_frame must be "recording" or a [3, 3] array: the ball is one object in one frame')
+        frame = None
+    else:
+        frame = body_frame if isinstance(body_frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(body_frame, dtype=np.float64))
+        if tuple(frame.shape) not in ((3, 3), (1, 3, 3)):
+            raise ValueError("an explicit body_frame must be [3, 3]: the ball is one object in one frame")
+        frame = frame.to(device=dev, dtype=torch.float64).reshape(3, 3).contiguous()
+    tips = torch.empty((T, 6, 3), dtype=torch.float64, device=dev)
+    vel = torch.empty((T, 6, 3), dtype=torch.float64, device=dev)
+    if T == 0:
+        return tips, vel
+    coxa = _coxa_medians(points3d)[1].contiguous()
+    if frame is None:
+        frame = recording_frame(points3d).reshape(3, 3).contiguous()
+    _bmap_call("df3d_ball_tips", points3d.data_ptr(), T, frame.data_ptr(), coxa.data_ptr(), fps, w, tips.data_ptr(), vel.data_ptr(),
+               _stream(points3d))
+    return tips, vel
+
+
+@_on_tensor_device
+def fit_ball(tips, states, radius=None, iterations=None):
+    """The sphere through the stance tips, a BallFit: tips [T, 6, 3] (float64 cuda, body_tips') and states [T, 6] (int32 cuda,
+    gait_states'); a sample is a (t, L) with states 0 and a finite tip.  `radius=None`: the algebraic (Kasa) fit on coordinates
+    centred at the samples' mean -- its radius is biased low by noise.  A known `radius` (pose units, mm): the centre takes
+    `iterations` (config.BALL_FIT_ITERATIONS) Gauss-Newton steps on sum (|tip - c| - radius)^2 from the algebraic centre.  Refused
+    (NaN, status bit 0): fewer than 4 samples (3 with a known radius) or a pivot at or below config.BALL_PIVOT_MIN times the largest
+    diagonal entry.  Nothing is read back."""
+    from . import config
+
+    tips = _need_gait(tips, torch.float64, (6, 3), "tips")
+    states = _need_states(states)
+    radius, _, iterations = treadmill_params(radius, None, iterations)
+    T, dev = tips.shape[0], tips.device
+    _same_frames(states, T, dev, "states")
+    ball = torch.full((8,), float("nan"), dtype=torch.float64, device=dev)
+    ball[5:] = 0.0
+    info = torch.tensor([0, 1], dtype=torch.int64, device=dev)   # no frames: no samples, a refused fit
+    sums = torch.zeros((17,), dtype=torch.float64, device=dev)
+    if T:
+        work, need = _ball_work(T, dev)
+        _bmap_call("df3d_ball_fit", tips.data_ptr(), states.data_ptr(), T, 0 if radius is None else 1, 0.0 if radius is None else radius,
+                   iterations, float(config.BALL_PIVOT_MIN), ball.data_ptr(), info.data_ptr(), sums.data_ptr(), work.data_ptr(), need,
+                   _stream(tips))
+    return BallFit(ball, info, sums)
+
+
+@_on_tensor_device
+def ball_rotation(tips, vel, states, ball, min_legs=None):
+    """(rotation [T, 3], legs [T] int32, residual [T], fictive [T, 3]) of tips and vel [T, 6, 3] (body_tips'), states [T, 6] and `ball`
+    (a BallFit, or its [8] float64 tensor: centre, radius, ...): per frame the rotation vector of the ball (rad/s, body coordinates)
+    that best carries the stance tips, r = tip - c, sum (|r|^2 I - r r^T) omega = sum r x vel over the legs with states 0 and finite
+    tip and vel; NaN with fewer than `min_legs` of them (config.BALL_MIN_LEGS), with a pivot at or below config.BALL_FRAME_PIVOT_MIN
+    times the trace, or with a refused ball.  residual: the root mean square of vel - omega x r; fictive: the fly's forward and
+    sideways speed (pose units per second) and yaw rate (rad/s)."""
+    from . import config
+
+    tips = _need_gait(tips, torch.float64, (6, 3), "tips")
+    vel = _need_gait(vel, torch.float64, (6, 3), "vel")
+    states = _need_states(states)
+    min_legs = treadmill_params(None, min_legs)[1]
+    T, dev = tips.shape[0], tips.device
+    _same_frames(vel, T, dev, "vel")
+    _same_frames(states, T, dev, "states")
+    ball = ball.ball if isinstance(ball, BallFit) else ball
+    if not (isinstance(ball, torch.Tensor) and ball.dtype == torch.float64 and ball.device == dev and tuple(ball.shape) == (8,)):
+        raise ValueError("ball must be a BallFit or its torch.float64 tensor of shape [8] on the device of tips")
+    ball = ball.contiguous()
+    rotation = torch.empty((T, 3), dtype=torch.float64, device=dev)
+    legs = torch.empty((T,), dtype=torch.int32, device=dev)
+    residual = torch.empty((T,), dtype=torch.float64, device=dev)
+    fictive = torch.empty((T, 3), dtype=torch.float64, device=dev)
+    if T:
+        _bmap_call("df3d_ball_rotation", tips.data_ptr(), vel.data_ptr(), states.data_ptr(), T, ball.data_ptr(), min_legs,
+                   float(config.BALL_FRAME_PIVOT_MIN), rotation.data_ptr(), legs.data_ptr(), residual.data_ptr(), fictive.data_ptr(),
+                   _stream(tips))
+    return rotation, legs, residual, fictive
+
+
+@_on_tensor_device
+def fictive_path(fictive, fps):
+    """(path [T, 3] float64 = (x, y, theta), skipped, a 0-dim int64 tensor) of fictive [T, 3] (float64 cuda, ball_rotation's) sampled at
+    `fps`: theta_0 = 0, theta_{t+1} = theta_t + yaw_t / fps; (x, y)_0 = 0, (x, y)_{t+1} = (x, y)_t + Rot(theta_t)(forward_t,
+    sideways_t) / fps.  A frame with a non-finite component moves nothing and is counted in `skipped`."""
+    fictive = _need_gait(fictive, torch.float64, (3,), "fictive")
+    fps = _gait_fps(fps)
+    T, dev = fictive.shape[0], fictive.device
+    path = torch.empty((T, 3), dtype=torch.float64, device=dev)
+    skipped = torch.zeros((1,), dtype=torch.int64, device=dev)
+    if T:
+        work, need = _ball_work(T, dev)
+        _bmap_call("df3d_ball_path", fictive.data_ptr(), T, fps, path.data_ptr(), skipped.data_ptr(), work.data_ptr(), need, _stream(fictive))
+    return path, skipped[0]
+
+
+def treadmill(points3d, fps, body_frame="recording", states=None, radius=None, on=None, off=None, half_window=None, min_legs=None,
+              iterations=None):
+    """The treadmill analysis of points3d [T, 38, 3] (float64 cuda) sampled at `fps`, a TreadmillResult:
+    body_tips, fit_ball over the stance samples, ball_rotation and fictive_path, each on the one before.  `states`: the swing/stance
+    states [T, 6] of gait_states, handed in by whoever has them; None computes them from the anterior tip velocity with gait's
+    rule and `on`, `off` (gait_thresholds).  `radius`: the ball's known radius in pose units (mm), else it is fitted."""
+    radius, min_legs, iterations = treadmill_params(radius, min_legs, iterations)   # refused before any work
+    thresholds = gait_thresholds(on, off, half_window)
+    if states is not None and (on is not None or off is not None):
+        raise ValueError("on and off decide the states that treadmill computes: with states handed in they have nothing to decide")
+    fps = _gait_fps(fps)
+    tip, vel = body_tips(points3d, fps, body_frame, thresholds[2])
+    if states is None:
+        states = gait_states(vel, thresholds[0], thresholds[1])   # the anterior velocity is tip_kinematics' own: F (P4[b] - P4[a]) . ex
+        on, off = thresholds[:2]
+    else:
+        states = _need_states(states)
+        _same_frames(states, tip.shape[0], tip.device, "states")
+        on = off = float("nan")
+    ball = fit_ball(tip, states, radius, iterations)
+    rotation, legs, residual, fictive = ball_rotation(tip, vel, states, ball, min_legs)
+    path, skipped = fictive_path(fictive, fps)
+    params = (float("nan") if radius is None else radius, on, off, thresholds[2], min_legs, iterations)
+    return TreadmillResult(tip, vel, states, ball, rotation, legs, residual, fictive, path, skipped, params, fps)
 
 
 # ---- repair of the 3-D pose (DESIGN.md section 20) ---------------------------------------------------------------------------------

@@ -486,6 +486,48 @@ int df3d_repair_fill(const double* pts_dev, const unsigned char* flags_dev, long
                      signed char* status_dev, long long* counts_dev, void* work_dev, long long work_len_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a17 the treadmill ball and the fictive walking path from the stance tips (the model is this project's own
+ *     specification, defined in float64 by tests/treadmill_oracle.py).  All arrays are DEVICE arrays, row-major: float64, int32 for
+ *     states and legs, int64 for info and skipped.  No floating-point atomics and fixed-order sums: two calls on the same input give
+ *     the same bits, on any machine.  The legs, the tip P4, the window and the missing-joint rule are those of a15.
+ * df3d_ball_tips: pts [T, 38, 3], the recording's body frame [3, 3] (rows ex, ey, ez) and coxa [6, 3], the temporal medians of the six
+ *     body-coxa joints; the origin o is their sum in leg order divided by 6.  tip [T, 6, 3] = F (P4 - o), neither mirrored nor relative
+ *     to the coxa; NaN where P4 is missing or the frame or o holds a non-finite number.  vel [T, 6, 3] = F (P4[b] - P4[a]) (fps / (b -
+ *     a)) with a15's window and NaN rules.
+ * df3d_ball_fit: one sphere through the samples (t, L) with states 0 and a finite tip.  With m their mean and q = tip - m, the
+ *     algebraic fit minimises sum (|q|^2 - 2 a . q - k)^2: centre a + m, radius sqrt(k + |a|^2).  known_radius = 1: the radius is
+ *     `radius`, and the centre takes `iterations` Gauss-Newton steps on sum (|tip - c| - radius)^2 from the algebraic centre -- or,
+ *     where there is none (three samples, a flat set), from m (1 + radius / |m|), the point beyond the tips as seen from the body's
+ *     origin (status bit 1).  Refused (status bit 0; centre, radius and rms NaN): fewer than 4 samples (3 with a known radius), a
+ *     Cholesky pivot at or below pivot_min times the largest diagonal entry of its normal matrix, or k + |a|^2 <= 0.  ball [8] =
+ *     centre, radius, rms of |tip - c| - radius, and three zeros; info [2] int64 = count, status; sums [17] = the count, the sum of
+ *     tip [3], and sum qx qx, qx qy, qx qz, qx, qy qy, qy qz, qy, qz qz, qz, qx |q|^2, qy |q|^2, qz |q|^2, |q|^2.  Every sum is
+ *     taken in slices of 2 048 samples of the flattened [6 T] that are added in index order.
+ * df3d_ball_rotation: per frame, over the legs with states 0 and finite tip and vel, r = tip - c: omega [T, 3] solves sum (|r|^2 I -
+ *     r r^T) omega = sum r x vel, summed in leg order; NaN with fewer than min_legs legs, with a pivot at or below pivot_min times the
+ *     trace, or with a refused ball.  legs [T] int32; residual [T] = the root mean square over those legs of |vel - omega x r|;
+ *     fictive [T, 3] = (forward, sideways, yaw rate) = (s . ex, s . ey, -omega . u) with u = -c / |c| and s = -(omega x radius u).
+ * df3d_ball_path: path [T, 3] = (x, y, theta), two exclusive prefix sums: theta of yaw / fps, then (x, y) of Rot(theta_t)(forward,
+ *     sideways) / fps.  A frame with a non-finite fictive component moves nothing and is counted in skipped [1] int64.
+ * df3d_ball_work_bytes(T): the bytes of the caller-owned workspace of df3d_ball_fit and df3d_ball_path at this T (0 where T is out of
+ *     range).
+ * DF3D_EINVAL before the device is touched, with a message that names the argument: T negative or above (2^31 - 1) / 6; fps not
+ *     finite or <= 0; half_window outside [1, 64]; known_radius other than 0 or 1 and, with 1, a radius not finite or <= 0 or
+ *     iterations outside [1, 64]; pivot_min outside [0, 1); min_legs outside [2, 6]; a null, misaligned (16 bytes for work, 8 for
+ *     float64 and int64, 4 for int32) or overlapping buffer; a workspace below the query.  T = 0 launches nothing and returns DF3D_OK.
+ *     Every launching entry is asynchronous on `stream`, allocates nothing and keeps no host pointer.
+ * ---------------------------------------------------------------------------------------------- */
+long long df3d_ball_work_bytes(long long T);
+int df3d_ball_tips(const double* pts_dev, long long T, const double* frame_dev, const double* coxa_dev, double fps, int half_window,
+                   double* tip_dev, double* vel_dev, void* stream);
+int df3d_ball_fit(const double* tip_dev, const int* states_dev, long long T, int known_radius, double radius, int iterations, double pivot_min,
+                  double* ball_dev, long long* info_dev, double* sums_dev, void* work_dev, long long work_len_bytes, void* stream);
+int df3d_ball_rotation(const double* tip_dev, const double* vel_dev, const int* states_dev, long long T, const double* ball_dev, int min_legs,
+                       double pivot_min, double* omega_dev, int* legs_dev, double* residual_dev, double* fictive_dev, void* stream);
+int df3d_ball_path(const double* fictive_dev, long long T, double fps, double* path_dev, long long* skipped_dev, void* work_dev,
+                   long long work_len_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
