@@ -132,6 +132,9 @@ PROTOTYPES = {
     "df3d_ball_rotation": (c_int, [c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p]),
     "df3d_ball_path": (c_int, [c_void_p, c_longlong, c_double, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_track_work_bytes": (c_longlong, [c_longlong, c_longlong, c_int, c_int]),
+    "df3d_track_peaks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_int, c_int, c_double, c_double, c_double, c_double, c_double,
+                         c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "df3d_ba_eval": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_colsq": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_matvec": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -57,6 +57,19 @@ def parse_cli_args(argv=None):
     p.add_argument("--correct-only-flagged", dest="correct_only_flagged", action="store_true",
                    help="With --auto-correct: keep the correction only on the joints whose reprojection error exceeds the per-joint "
                         "threshold (40 px) on the arg-max detections; every other detection stays the arg-max one")
+    p.add_argument("--track-2d", dest="track_2d", action="store_true",
+                   help="Track the 2-D detections through time before the first save: for every camera and network joint, the sequence of "
+                        "heat-map peaks that is jointly best over the whole recording (an exact Viterbi solve: a peak pays for the heat-map "
+                        "value it gives up against the frame's best and for its jump from the frame before) replaces the per-frame arg-max; "
+                        "the arg-max detections are kept as points2d_argmax, followed by track_choice [7, T, 19], track_cost [7, 19] and "
+                        "track_params.  --track-tau and the two weights are guesses that nobody has measured on a recording.  Not together "
+                        "with --auto-correct or --skip-pose-estimation")
+    p.add_argument("--track-tau", dest="track_tau", type=float, default=None, metavar="PX",
+                   help="With --track-2d: the jump between consecutive frames, in pixels, beyond which every jump costs the same (default 30)")
+    p.add_argument("--track-motion", dest="track_motion", type=float, default=None, metavar="W",
+                   help="With --track-2d: the weight of the jump term, 0 to 1024 (default 1); 0 leaves every detection the arg-max")
+    p.add_argument("--track-value", dest="track_value", type=float, default=None, metavar="W",
+                   help="With --track-2d: the weight of the heat-map value term, 0 to 1024 (default 1)")
     p.add_argument("--subpixel", action="store_true",
                    help="Refine every 2-D detection inside its heat-map cell (up to half a cell, 3.75 px, per axis) from the 3 x 3 values round the "
                         "maximum instead of reporting the cell itself; the result then carries the key subpixel.  Off by default: the default is the "
@@ -187,6 +200,20 @@ def parse_cli_args(argv=None):
         p.error("--behaviour-perplexity sets the perplexity of --behaviour-map: it needs --behaviour-map")
     if args.behaviour_perplexity is not None and not (math.isfinite(args.behaviour_perplexity) and args.behaviour_perplexity > 1.0):
         p.error("--behaviour-perplexity must be finite and > 1")
+    for name in ("tau", "motion", "value"):
+        if getattr(args, "track_" + name) is not None and not args.track_2d:
+            p.error(f"--track-{name} sets a parameter of --track-2d: it needs --track-2d")
+    if args.track_2d:
+        from . import ops
+
+        if args.skip_estimation:
+            p.error("--track-2d needs the heat-map peaks of this run's pose estimation: it cannot be combined with --skip-pose-estimation")
+        if args.auto_correct:
+            p.error("--track-2d and --auto-correct both start from the arg-max detections, so the later one would undo the other: choose one")
+        try:
+            ops.track_params(args.track_tau, args.track_motion, args.track_value)
+        except ValueError as e:
+            p.error(f"--track-tau, --track-motion and --track-value: {e}")
     if args.auto_correct and args.skip_estimation:
         p.error("--auto-correct needs the heat-map peaks of this run's pose estimation: it cannot be combined with --skip-pose-estimation")
     if args.subpixel and args.skip_estimation:
@@ -259,8 +286,13 @@ def run(args):
     if not args.skip_estimation:
         from .config import PICTORIAL_DEFAULTS
 
-        core.pose2d_estimation(args.batch_size, args.pin_memory_disabled, num_peaks=PICTORIAL_DEFAULTS["num_peaks"] if auto else 0,
+        track = getattr(args, "track_2d", False)
+        core.pose2d_estimation(args.batch_size, args.pin_memory_disabled, num_peaks=PICTORIAL_DEFAULTS["num_peaks"] if auto or track else 0,
                                subpixel=getattr(args, "subpixel", False))
+        if track:   # before the first save: the calibration then starts from the tracked detections
+            given = {"tau": getattr(args, "track_tau", None), "w_motion": getattr(args, "track_motion", None),
+                     "w_value": getattr(args, "track_value", None)}
+            core.track_detections(**{name: v for name, v in given.items() if v is not None})
         core.save()
     # the heat-map video needs the images and the weights only: without an earlier result to reopen there is no pose to calibrate or save
     pose_free = args.skip_estimation and core.points2d is None and video_heatmap and not args.video_2d and not args.video_3d

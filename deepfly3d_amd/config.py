@@ -44,6 +44,21 @@ PICTORIAL_DEFAULTS = {
     "w_bone": 1.0,
 }
 
+# ---- tracking of the 2-D detections through time: per (camera, network joint), the sequence of heat-map peaks
+# that is jointly best over the recording.  tau truncates the squared jump between consecutive frames (pixels; the number section 9
+# truncates its reprojection term at), w_motion weighs that jump and w_value the heat-map value a peak gives up against the frame's
+# best; block_frames is the time block of the solve and changes no bit of the result.  tau and the two weights are guesses: nobody has
+# measured them on a recording.
+TRACK_DEFAULTS = {
+    "tau": 30.0,
+    "w_motion": 1.0,
+    "w_value": 1.0,
+    "block_frames": 256,
+}
+TRACK_WEIGHT_MAX = 1024.0
+TRACK_BLOCK_FRAMES_RANGE = (1, 4096)
+TRACK_NUM_PEAKS_RANGE = (1, 16)
+
 # ---- suspect detections: joint j of a frame is flagged when its largest per-camera reprojection error
 # exceeds REPROJ_THR[j] pixels.  The reference's `config["reproj_thr"]` (df3d/config.py:41): 40 for each of the 38 joints.
 REPROJ_THR = np.full(38, 40.0, dtype=np.float64)

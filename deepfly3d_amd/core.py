@@ -105,7 +105,8 @@ class Core:
         self._points2d_shard = None  # multi-GPU: this rank's frames of points2d (device tensor, normalised), kept for the sharded DLT
         self.peaks = None             # (count, points, values) of pose2d_estimation(num_peaks=K), numpy [7, T, 19, ...]; rank 0
         self.points2d_argmax = None   # the arg-max detections, once auto_correct() has replaced points2d
-        self._corrected = False       # every rank: auto_correct() ran (save() then triangulates on rank 0 alone)
+        self._corrected = False       # every rank: auto_correct() or track_detections() ran (save() then triangulates on rank 0 alone)
+        self._track = None            # rank 0: {choice, cost, params} of track_detections(), while points2d holds its result
         self._subpixel = False        # pose2d_estimation(subpixel=True) ran: save() appends the key "subpixel"
         self._heatmap_cache = None    # (img_id, luma [7, H, W], heat-maps [7, 19, 64, 128]) device tensors of the last heatmaps() call
         self._heatmap_proven = False  # a reduced-precision engine passed the canary on this recording's views (heatmaps())
@@ -204,7 +205,7 @@ class Core:
         # 19 -> 38 layout on the device, then (N > 1) ONE gather of the device tensors: no host round trip before it
         points2d = ops.relayout_19_to_38(points19.contiguous(), self.camera_ordering)
         self._points2d_shard = points2d if world > 1 else None
-        self._corrected, self.points2d_argmax = False, None
+        self._corrected, self.points2d_argmax, self._track = False, None, None
         self._subpixel = bool(subpixel)
         if dd.collective_needed(world):
             gathered = dd.gather_packed([(points2d, 1), (conf, 1)] + [(p, 1) for p in peaks], self.num_images)
@@ -268,6 +269,7 @@ class Core:
             corrected = torch.where(flagged[None, :, :, None], res.points2d, am)
         self.points2d_argmax = np.array(argmax2d, dtype=np.float64, copy=True)
         self.points2d = corrected.cpu().numpy()
+        self._track = None   # the correction started from the arg-max detections: an earlier tracking is gone
         np.copyto(self.camNet.points2d, self.points2d * self.image_shape[::-1])
         self.camNet.drop_smoothed()
         changed = int((self.points2d != self.points2d_argmax).any(axis=-1).sum())
@@ -276,6 +278,51 @@ class Core:
             print(f"Auto-correction changed {changed} detections; {energy}")
         else:
             print(f"Auto-correction changed {changed} detections on {int(flagged.sum())} flagged joints; {energy}")
+
+    def track_detections(self, **params):
+        """Track the 2-D detections through time on the device: for every (camera, network joint) the sequence of
+        heat-map peaks that is jointly best over the whole recording replaces the per-frame arg-max, in `points2d` and, when there is
+        one, in the camera network's points; the arg-max detections are kept in `points2d_argmax`, and save() then writes
+        "track_choice", "track_cost" and "track_params".  Needs the peaks of pose2d_estimation(num_peaks=K), no calibration.  It always
+        starts from the arg-max detections, as auto_correct() does: of the two, the later call wins.  `params` override
+        config.TRACK_DEFAULTS (tau, w_motion, w_value, block_frames); tau and the weights are guesses nobody has measured on a
+        recording.  Multi-GPU: every rank calls this, rank 0 solves, a failure there is raised on every rank (`distributed.agree`)."""
+        from . import distributed as dd
+        from .config import TRACK_DEFAULTS
+
+        error = None
+        if self.is_primary:
+            try:
+                unknown = set(params) - set(TRACK_DEFAULTS)
+                if unknown:
+                    raise TypeError(f"track_detections: unknown parameters {sorted(unknown)}")
+                p = ops.track_params(**params)   # refused before any device work
+                if self.peaks is None or self.points2d is None or self.peaks[0].shape[1] != self.points2d.shape[1]:
+                    raise RuntimeError("track_detections needs the heat-map peaks of this recording: run pose2d_estimation(num_peaks=K) first")
+                self._track_primary(p)
+            except Exception as e:  # noqa: BLE001  (re-raised by agree, on every rank)
+                error = e
+        dd.agree(error, "track_detections")
+        self._corrected = True
+
+    def _track_primary(self, p):
+        _native.require_gpu()
+        dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
+        count, pts, vals = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in self.peaks)
+        argmax2d = self.points2d_argmax if self.points2d_argmax is not None else self.points2d
+        am = torch.from_numpy(np.ascontiguousarray(argmax2d, dtype=np.float64)).to(dev)
+        res = ops.track_peaks(count, pts, vals, self.image_shape, *p)
+        tracked = ops.tracked_points2d(am, self.camera_ordering, pts, res.choice)
+        self.points2d_argmax = np.array(argmax2d, dtype=np.float64, copy=True)
+        self.points2d = tracked.cpu().numpy()
+        if self.camNet is not None and self.camNet.points2d is not None and self.camNet.points2d.shape == self.points2d.shape:
+            np.copyto(self.camNet.points2d, self.points2d * self.image_shape[::-1])
+            self.camNet.drop_smoothed()
+        self._track = {"choice": res.choice.cpu().numpy().astype(np.int8), "cost": res.cost_float.cpu().numpy(),
+                       "params": np.array(p[:3], dtype=np.float64)}
+        moved = int((self._track["choice"] != 0).sum())
+        print(f"Tracking moved {moved} of {self._track['choice'].size} detections off the arg-max peak; "
+              f"mean cost per chain {float(self._track['cost'].mean()) if self._track['cost'].size else 0.0:.4f}")
 
     # -- suspect detections (DESIGN.md section 10; reference df3d/core.py:205-227, 481-507) -----------------------------------------
     # Rank-0 methods on the camera network's detections (pixels, with auto-corrections and the manual corrections that
@@ -726,7 +773,9 @@ class Core:
         "treadmill_rotation" [T, 3], "treadmill_legs" [T] int32, "treadmill_residual" [T], "treadmill_fictive" [T, 3] (forward,
         sideways, yaw rate), "treadmill_path" [T, 3] (x, y, theta), "treadmill_skipped", "treadmill_params" (radius or NaN, on, off,
         half_window, min_legs, iterations) and "treadmill_fps".  There are no "_rigid" twins: the ball is one object.  Together with
-        gait, the swing/stance states of the measured pose are computed once and shared."""
+        gait, the swing/stance states of the measured pose are computed once and shared.  After track_detections() the result holds,
+        directly after "points2d_argmax", "track_choice" [7, T, 19] int8 (the slot every chain took in every frame), "track_cost"
+        [7, 19] float64 (each chain's minimum) and "track_params" (tau, w_motion, w_value); without it no key is added."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
@@ -781,6 +830,9 @@ class Core:
         result["heatmap_confidence"] = self.conf
         if getattr(self, "_corrected", False) and self.points2d_argmax is not None:
             result["points2d_argmax"] = np.copy(self.points2d_argmax)
+            if getattr(self, "_track", None) is not None:   # track_detections() ran last: what it chose, directly after the arg-max detections
+                result["track_choice"], result["track_cost"] = np.copy(self._track["choice"]), np.copy(self._track["cost"])
+                result["track_params"] = np.copy(self._track["params"])
         if getattr(self, "_subpixel", False):   # only when this run refined its detections: without it the schema is the reference's
             result["subpixel"] = True
         # opt-in, like the two keys above: else the reference's schema

@@ -1,7 +1,7 @@
 """Thin host wrappers over the C ABI for the non-network kernels: arg-max and peaks, re-layout, triangulation, Procrustes and the
 video pose, and what DESIGN.md sections 9-19 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
-overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps, their segmentation, the gait analysis, the pose repair and
-the treadmill ball (section 21).
+overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps, their segmentation, the gait analysis, the pose repair,
+the treadmill ball (section 21) and the tracking of the detections through time (section 22).
 
 Inputs/outputs are torch CUDA tensors (device memory + stream plumbing only); every computation is a
 libdf3d_hip.so kernel.  No CPU fallback: a missing library or GPU raises `_native.NativeLibraryError`.
@@ -1514,6 +1514,117 @@ def repair_pose(points3d, half_window=None, threshold=None, floor=None, max_gap=
     flags, score = pose_outliers(points3d, params[0], params[1], params[2], params[4])
     points, status, counts = fill_gaps(points3d, flags, params[3])
     return PoseRepairResult(points, status, counts, score, params)
+
+
+# ---- tracking of the 2-D detections through time ------------------------------------------------------------
+@dataclasses.dataclass
+class TrackResult:
+    """What `track_peaks` returns, device tensors but for the last: choice [C, T, J] int32 (the slot of every frame on the jointly best
+    sequence of its chain; 0 on a frame without a valid peak), cost [C, J] int64 (the minimum, in units of 2^-20; `cost_float` divides)
+    and params (tau, w_motion, w_value, block_frames)."""
+    choice: torch.Tensor
+    cost: torch.Tensor
+    params: tuple
+
+    @property
+    def cost_float(self):
+        return self.cost.to(torch.float64) / 2.0 ** 20
+
+
+def track_params(tau=None, w_motion=None, w_value=None, block_frames=None):
+    """(tau, w_motion, w_value, block_frames) with config.TRACK_DEFAULTS for what is None -- tau and the weights are guesses nobody has
+    measured on a recording.  ValueError: a tau that is not finite and > 0, a weight that is not finite or outside [0,
+    config.TRACK_WEIGHT_MAX], a block_frames that is no integer in config.TRACK_BLOCK_FRAMES_RANGE."""
+    from . import config
+
+    def number(v, name):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number (it is {v!r})")
+        return float(v)
+
+    d = config.TRACK_DEFAULTS
+    t = number(d["tau"] if tau is None else tau, "tau")
+    if not (np.isfinite(t) and t > 0.0):
+        raise ValueError(f"tau must be finite and > 0 (it is {t:g})")
+    weights = []
+    for name, v in (("w_motion", w_motion), ("w_value", w_value)):
+        w = number(d[name] if v is None else v, name)
+        if not (np.isfinite(w) and 0.0 <= w <= config.TRACK_WEIGHT_MAX):
+            raise ValueError(f"{name} must be finite and in [0, {config.TRACK_WEIGHT_MAX:g}] (it is {w:g})")
+        weights.append(w)
+    b = d["block_frames"] if block_frames is None else block_frames
+    lo, hi = config.TRACK_BLOCK_FRAMES_RANGE
+    if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not lo <= b <= hi:
+        raise ValueError(f"block_frames must be an integer in [{lo}, {hi}] (it is {b!r})")
+    return t, weights[0], weights[1], int(b)
+
+
+def _need_peaks(peak_count, peak_pts, peak_val):
+    """(C, T, J, K) of count [C, T, J] int32, points [C, T, J, K, 2] float32 and values [C, T, J, K] float32 on one CUDA device."""
+    from . import config
+
+    _need(peak_count, torch.int32, "peak_count")
+    _need(peak_pts, torch.float32, "peak_pts")
+    _need(peak_val, torch.float32, "peak_val")
+    if peak_count.dim() != 3 or peak_pts.dim() != 5 or tuple(peak_pts.shape[:3]) != tuple(peak_count.shape) or peak_pts.shape[4] != 2 or \
+            tuple(peak_val.shape) != tuple(peak_pts.shape[:4]):
+        raise ValueError("peaks must be count [C, T, J], points [C, T, J, K, 2] and values [C, T, J, K]")
+    if peak_pts.device != peak_count.device or peak_val.device != peak_count.device:
+        raise ValueError("the peaks must be on one device")
+    C, T, J, K = peak_val.shape
+    lo, hi = config.TRACK_NUM_PEAKS_RANGE
+    if not lo <= K <= hi:
+        raise ValueError(f"the peaks kept per heat-map, K, must be in [{lo}, {hi}] (it is {K})")
+    if C < 1 or J < 1:
+        raise ValueError("the peaks must hold at least one camera and one joint")
+    return C, T, J, K
+
+
+@_on_tensor_device
+def track_peaks(peak_count, peak_pts, peak_val, image_shape, tau=None, w_motion=None, w_value=None, block_frames=None):
+    """The jointly best sequence of heat-map peaks of every chain (camera, joint) over the recording (df3d_track_peaks, DESIGN.md section
+    22), a TrackResult.  Peaks as heatmap_peaks returns them per camera: count [C, T, J] int32, points [C, T, J, K, 2] float32, values
+    [C, T, J, K] float32 (cuda); image_shape [W, H].  A path pays w_value min(v_best - v, 1) for a peak whose value lies below the
+    frame's best and w_motion min(|jump|^2, tau^2) / tau^2 for the jump from the peak of the frame before, in pixels; costs are quantised
+    to multiples of 2^-20 and the solve is exact, so the result does not depend on block_frames.  Defaults and refusals: track_params."""
+    t, wm, wv, b = track_params(tau, w_motion, w_value, block_frames)   # refused before any device work
+    C, T, J, K = _need_peaks(peak_count, peak_pts, peak_val)
+    W, H = float(image_shape[0]), float(image_shape[1])
+    dev = peak_count.device
+    choice = torch.empty((C, T, J), dtype=torch.int32, device=dev)
+    cost = torch.zeros((C, J), dtype=torch.int64, device=dev)
+    if T:
+        need = _native.load().df3d_track_work_bytes(C * J, T, K, b)
+        if need <= 0:
+            raise ValueError(f"no workspace for {C * J} chains of {T} frames: C J must be at most 2^20, T at most 2^31 - 1 and C J T at most 2^36")
+        work = torch.empty((need,), dtype=torch.uint8, device=dev)
+        _bmap_call("df3d_track_peaks", peak_count.data_ptr(), peak_pts.data_ptr(), peak_val.data_ptr(), C, T, J, K, H, W, t, wm, wv, b,
+                   choice.data_ptr(), cost.data_ptr(), work.data_ptr(), need, _stream(peak_count))
+    return TrackResult(choice, cost, (t, wm, wv, b))
+
+
+def tracked_points2d(points2d, camera_ordering, peak_pts, choice):
+    """[7, T, 38, 2] float64: points2d [7, T, 38, 2] (float64 cuda, the re-layout of the arg-max detections) with every entry whose chain
+    chose another slot than 0 replaced by the chosen peak of peak_pts [7, T, 19, K, 2], passed through relayout_19_to_38 -- flip and
+    layout follow that one rule.  An entry whose chain chose slot 0 (a frame without a valid peak included), and every entry no chain
+    fills, keeps its bits.  choice [7, T, 19] int32 (TrackResult.choice)."""
+    _need(points2d, torch.float64, "points2d")
+    _need(peak_pts, torch.float32, "peak_pts")
+    _need(choice, torch.int32, "choice")
+    if points2d.dim() != 4 or points2d.shape[0] != 7 or tuple(points2d.shape[2:]) != (38, 2):
+        raise ValueError("points2d must be [7, T, 38, 2]")
+    T = points2d.shape[1]
+    if peak_pts.dim() != 5 or tuple(peak_pts.shape[:3]) != (7, T, 19) or peak_pts.shape[4] != 2 or tuple(choice.shape) != (7, T, 19):
+        raise ValueError("peak_pts must be [7, T, 19, K, 2] and choice [7, T, 19] of the recording of points2d")
+    if peak_pts.device != points2d.device or choice.device != points2d.device:
+        raise ValueError("points2d, peak_pts and choice must be on one device")
+    K = peak_pts.shape[3]
+    slot = choice.to(torch.int64).clamp(0, K - 1)
+    chosen = torch.gather(peak_pts, 3, slot[..., None, None].expand(7, T, 19, 1, 2)).squeeze(3).contiguous()
+    # which of the 38 entries a moved chain fills: the re-layout leaves the row component as it is, and fills 0 where no chain does
+    moved = (choice != 0).to(torch.float32)[..., None].expand(7, T, 19, 2).contiguous()
+    replace = relayout_19_to_38(moved, camera_ordering)[..., 0] != 0.0
+    return torch.where(replace[..., None], relayout_19_to_38(chosen, camera_ordering), points2d)
 
 
 def gaussian_window_taps(window_size, sigma, truncate=4.0):

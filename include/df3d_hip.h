@@ -528,6 +528,35 @@ int df3d_ball_path(const double* fictive_dev, long long T, double fps, double* p
                    long long work_len_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a18 tracking of the 2-D detections through time: an exact Viterbi solve over the heat-map peaks (the model is
+ *     this project's own specification, defined in float64 / int64 by tests/track_oracle.py).  All arrays are DEVICE arrays, row-major,
+ *     laid out as df3d_heatmap_peaks leaves them per camera: count [C, T, J] int32, pts [C, T, J, K, 2] float32 (row / H, col / W),
+ *     val [C, T, J, K] float32.  A chain is one (camera, joint); the C J chains are independent.
+ * df3d_track_peaks: slot k of a frame is valid when k < count and its value and both coordinates are finite; a frame without a valid
+ *     slot is a placeholder frame: slot 0 alone is valid, its unary cost is 0 and every pair cost to or from it is w_motion.  Unary
+ *     cost u = w_value min(v_best - v, 1) with v_best the largest valid value of the frame; pair cost d = w_motion min(dr^2 + dc^2,
+ *     tau^2) / tau^2 between slot k of frame t and slot k' of frame t - 1, dr and dc the pixel differences (normalised x height_px, x
+ *     width_px).  Both are formed in float64 in that order, without contraction, and rounded once: rint(x 2^20) as int64; an invalid
+ *     slot costs 2^61, where sums saturate.  choice [C, T, J] int32 minimises the sum of u over the frames and d over the frames after
+ *     the first; among the optimal paths it is the one whose reversed sequence is lexicographically smallest (the last frame takes
+ *     the lowest minimal slot, every back-pointer the lowest minimising predecessor); 0 on a placeholder frame.  cost [C, J] int64:
+ *     the minimum, in units of 2^-20.  The recurrence runs in blocks of block_frames frames, which changes no bit of either output.
+ *     No atomics: two calls on the same input give the same bits.
+ * df3d_track_work_bytes(nchain, T, K, block_frames): the bytes of the caller-owned workspace at nchain = C J chains (0 where an
+ *     argument is out of range): 2 193 bytes per chain and block and 16 per chain and frame, each part rounded up to 64.
+ * DF3D_EINVAL before the device is touched, with a message that names the argument: C or J below 1 or C J above 2^20; T negative,
+ *     above 2^31 - 1 or C J T above 2^36; K outside [1, 16]; height_px, width_px or tau not finite or <= 0; w_motion or w_value not
+ *     finite or outside [0, 1024]; block_frames outside [1, 4096]; T (w_motion + w_value) 2^20 at or above 2^60; more than 2^31 - 1
+ *     (chain, block) pairs; a workspace below the query; a null, misaligned (16 bytes for work, 8 for cost, 4 for the rest) or
+ *     overlapping buffer.  T = 0 launches nothing and returns DF3D_OK.  Asynchronous on `stream`, allocates nothing and keeps no
+ *     host pointer.
+ * ---------------------------------------------------------------------------------------------- */
+long long df3d_track_work_bytes(long long nchain, long long T, int K, int block_frames);
+int df3d_track_peaks(const int* count_dev, const float* pts_dev, const float* val_dev, int C, long long T, int J, int K, double height_px,
+                     double width_px, double tau, double w_motion, double w_value, int block_frames, int* choice_dev, long long* cost_dev,
+                     void* work_dev, long long work_len_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
