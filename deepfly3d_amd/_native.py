@@ -135,6 +135,10 @@ PROTOTYPES = {
     "df3d_track_work_bytes": (c_longlong, [c_longlong, c_longlong, c_int, c_int]),
     "df3d_track_peaks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_int, c_int, c_double, c_double, c_double, c_double, c_double,
                          c_int, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_consensus_work_bytes": (c_longlong, [c_int, c_int, c_int]),
+    "df3d_consensus_candidates": (c_int, [POINTER(c_double), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "df3d_triangulate_consensus": (c_int, [POINTER(c_double), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_int, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "df3d_ba_eval": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_colsq": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_matvec": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

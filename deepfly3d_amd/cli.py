@@ -155,7 +155,34 @@ def parse_cli_args(argv=None):
                    help="With --repair-pose: the deviation, in pose units (mm), below which a joint is never an outlier (default 0.05, a guess)")
     p.add_argument("--repair-max-gap", dest="repair_max_gap", type=int, default=None, metavar="N",
                    help="With --repair-pose: the longest run of bad frames of a joint that is interpolated, 0 to 1000000 (default 10, a guess)")
+    p.add_argument("--robust-triangulation", dest="robust_triangulation", action="store_true",
+                   help="Triangulate every joint from the largest set of cameras that agree: every subset of the cameras that see a joint is "
+                        "triangulated, a subset qualifies when each of its cameras reprojects its point within --robust-tau pixels, and the "
+                        "largest qualifying subset wins (ties to the smaller squared error).  Appends, after every other key, "
+                        "points3d_robust [T, 38, 3], robust_cameras [T, 38] (bit c: camera c was used), robust_status [T, 38] (int8: 0 fewer "
+                        "than two views, 1 all views agree, 2 a subset was chosen, 3 none qualified: the plain triangulation), robust_error "
+                        "[7, T, 38], robust_counts [38, 4], points2d_robust [7, T, 38, 2] (rejected detections replaced by the projection) "
+                        "and robust_params to the result, and every other opt-in key is computed from the robust pose (repaired afterwards "
+                        "with --repair-pose); points3d, points3d_wo_procrustes and points2d stay the plain triangulation's.  Two views that "
+                        "agree with each other cannot be told from two correct ones: with three views a wrong detection near an epipolar "
+                        "line wins.  The default threshold is a guess that nobody has measured on a recording.  Works with "
+                        "--skip-pose-estimation on an earlier result")
+    p.add_argument("--robust-tau", dest="robust_tau", type=float, default=None, metavar="PX",
+                   help="With --robust-triangulation: the reprojection error, in pixels, within which a camera agrees with a subset's point "
+                        "(default 20, a guess)")
+    p.add_argument("--robust-min-views", dest="robust_min_views", type=int, default=None, metavar="N",
+                   help="With --robust-triangulation: the fewest cameras a subset may hold, 2 to 8 (default 2)")
     args = p.parse_args(argv)
+    for name in ("tau", "min_views"):
+        if getattr(args, "robust_" + name) is not None and not args.robust_triangulation:
+            p.error(f"--robust-{name.replace('_', '-')} sets a parameter of --robust-triangulation: it needs --robust-triangulation")
+    if args.robust_triangulation:
+        from . import ops
+
+        try:
+            ops.consensus_params(args.robust_tau, args.robust_min_views)
+        except ValueError as e:
+            p.error(f"--robust-tau and --robust-min-views: {e}")
     for name in ("window", "threshold", "floor", "max_gap"):
         if getattr(args, "repair_" + name) is not None and not args.repair_pose:
             p.error(f"--repair-{name.replace('_', '-')} sets a parameter of --repair-pose: it needs --repair-pose")
@@ -266,6 +293,9 @@ def run(args):
         extras.update(ball_radius=getattr(args, "ball_radius", None))
     if extras["repair_pose"]:
         extras.update({name: getattr(args, name, None) for name in ("repair_window", "repair_threshold", "repair_floor", "repair_max_gap")})
+    if getattr(args, "robust_triangulation", False):   # after the other flags: its keys come last
+        flagged.append("robust_triangulation")
+        extras.update(robust_triangulation=True, robust_tau=getattr(args, "robust_tau", None), robust_min_views=getattr(args, "robust_min_views", None))
     if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not flagged:
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0

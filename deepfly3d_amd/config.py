@@ -63,6 +63,13 @@ TRACK_NUM_PEAKS_RANGE = (1, 16)
 # exceeds REPROJ_THR[j] pixels.  The reference's `config["reproj_thr"]` (df3d/config.py:41): 40 for each of the 38 joints.
 REPROJ_THR = np.full(38, 40.0, dtype=np.float64)
 
+# ---- consensus triangulation: a subset of a joint's views qualifies when every one of its cameras reprojects
+# the subset's own DLT point within ROBUST_TAU[j] pixels, and it must hold at least ROBUST_MIN_VIEWS cameras (2 .. 8).  20 px for each
+# of the 38 joints is a guess: nobody has measured it on a recording.
+ROBUST_TAU = np.full(38, 20.0, dtype=np.float64)
+ROBUST_MIN_VIEWS = 2
+ROBUST_MIN_VIEWS_RANGE = (2, 8)
+
 # ---- leg joint angles.  Leg L = 3 side + l (l = 0, 1, 2: front, mid, hind) owns the five joints
 # 19 side + 5 l + k; its eight angles come in this order: thorax-coxa yaw, pitch and roll, coxa-trochanter pitch and roll,
 # femur-tibia pitch and roll, tibia-tarsus pitch; its four segment lengths are coxa, femur, tibia, tarsus.

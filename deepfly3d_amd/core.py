@@ -392,22 +392,74 @@ class Core:
         """The previous image before `img_id` with a flagged joint, or None (reference df3d/core.py:217-227)."""
         return self.next_error_in_range(range(img_id - 1, -1, -1))
 
-    # -- the kinematic chain (DESIGN.md sections 14-17): one kinematics.PoseChain per call, never kept ----------------------------------
-    def _measured_pose(self, what, fps=None, repair=None):
-        """The PoseChain of camNet.points3d on the device (triangulating first when there is none), with the refusals of the rank-0
-        pose queries.  `repair`: None or False, or the chain of the repaired pose instead (DESIGN.md section 20): True for the default
-        parameters, or a dict of ops.repair_pose's."""
+    # -- consensus triangulation (DESIGN.md section 23): rank-0 methods on the detections save() triangulates, like the queries above ---
+    def _robust_on(self, what, tau, min_views, ids=None, X=None):
+        """(ops.ConsensusResult on the device, the pixel detections [7, n, 38, 2] it was computed from) of the frames `ids` (default
+        all), with the refusals of _reprojection_on.  `tau`, `min_views`: ops.consensus_params' values.  `X`: the triangulation
+        [T, 38, 3] of these very detections as a numpy array, where the caller has just computed it (save()); else it is computed here."""
         from . import distributed as dd
 
         if dd.current()[0] != 0:
             raise RuntimeError(f"{what} is a rank-0 method: the camera network lives on rank 0")
         if self.camNet is None or not self.camNet.has_calibration():
             raise RuntimeError(f"{what} needs calibrated cameras: run calibrate_calc() first")
-        if self.camNet.points3d is None:
+        px = self.camNet.points2d
+        if ids is not None:
+            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+            if ids.size and (ids.min() < 0 or ids.max() >= px.shape[1]):
+                raise IndexError(f"image ids must lie in [0, {px.shape[1]})")
+            px = px[:, ids]
+        _native.require_gpu()
+        dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
+        P = np.stack([c.P for c in self.camNet.cam_list])
+        px = torch.from_numpy(np.ascontiguousarray(px, dtype=np.float64)).to(dev)
+        if X is not None:
+            X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev)
+        return ops.triangulate_consensus(P, px, X, tau=tau, min_views=min_views), px
+
+    def robust_triangulation(self, tau=None, min_views=None):
+        """The consensus triangulation (ops.triangulate_consensus) of the camera network's detections -- the ones
+        save() triangulates, stored corrections included -- an ops.ConsensusResult of numpy arrays: points3d [T, 38, 3] (in the layout
+        of points3d_wo_procrustes), cameras [T, 38] int32 (bit c: camera c was used), status [T, 38] int8 (0 fewer than two views, 1
+        all views agree, 2 a proper subset was chosen, 3 no subset qualified: the plain triangulation), error [7, T, 38] pixels (every
+        view against the chosen point), fixed_px [7, T, 38, 2] (the detections with every rejected view replaced by the projection of
+        the chosen point), counts [38, 4] and params (tau [38], min_views).  `tau`: pixels, one value or one per joint; the default,
+        config.ROBUST_TAU, is a guess nobody has measured on a recording.  A rank-0 method with the refusals of the
+        reprojection-error queries."""
+        t, m = ops.consensus_params(tau, min_views)   # refused before any work
+        r, _ = self._robust_on("robust_triangulation", t, m)
+        return ops.ConsensusResult(*(v.cpu().numpy() for v in (r.points3d, r.cameras, r.status, r.error, r.fixed_px, r.counts)), r.params)
+
+    def outlier_cameras(self, img_id, joint_id=None):
+        """The cameras whose detection of joint `joint_id` on image `img_id` the consensus triangulation rejects (config.ROBUST_TAU,
+        config.ROBUST_MIN_VIEWS), as a list of camera ids: the views to correct first.  `joint_id=None`: a dict joint id -> list, of
+        the joints with a rejected view.  A rank-0 method with the refusals of the reprojection-error queries."""
+        t, m = ops.consensus_params()
+        r, px = self._robust_on("outlier_cameras", t, m, [img_id])
+        view = (px[:, 0] != 0.0).all(dim=2).cpu().numpy()                        # [7, 38]
+        used = (r.cameras[0].cpu().numpy()[None] >> np.arange(view.shape[0])[:, None]) & 1
+        rejected = view & (used == 0) & (r.status[0].cpu().numpy() == 2)[None]
+        if joint_id is not None:
+            return [int(c) for c in np.nonzero(rejected[:, int(joint_id)])[0]]
+        return {int(j): [int(c) for c in np.nonzero(rejected[:, j])[0]] for j in np.nonzero(rejected.any(axis=0))[0]}
+
+    # -- the kinematic chain (DESIGN.md sections 14-17): one kinematics.PoseChain per call, never kept ----------------------------------
+    def _measured_pose(self, what, fps=None, repair=None, pose=None):
+        """The PoseChain of camNet.points3d on the device (triangulating first when there is none), with the refusals of the rank-0
+        pose queries.  `repair`: None or False, or the chain of the repaired pose instead (DESIGN.md section 20): True for the default
+        parameters, or a dict of ops.repair_pose's.  `pose`: a [T, 38, 3] float64 device tensor to build the chain from in place of
+        camNet.points3d (save()'s robust pose)."""
+        from . import distributed as dd
+
+        if dd.current()[0] != 0:
+            raise RuntimeError(f"{what} is a rank-0 method: the camera network lives on rank 0")
+        if self.camNet is None or not self.camNet.has_calibration():
+            raise RuntimeError(f"{what} needs calibrated cameras: run calibrate_calc() first")
+        if pose is None and self.camNet.points3d is None:
             self.camNet.triangulate()
         _native.require_gpu()
         dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
-        chain = PoseChain(torch.from_numpy(np.ascontiguousarray(self.camNet.points3d, dtype=np.float64)).to(dev), fps)
+        chain = PoseChain(torch.from_numpy(np.ascontiguousarray(self.camNet.points3d, dtype=np.float64)).to(dev) if pose is None else pose, fps)
         return chain.repaired(**(repair if isinstance(repair, dict) else {})) if repair else chain
 
     def repair_pose(self, half_window=None, threshold=None, floor=None, max_gap=None, min_count=None):
@@ -742,7 +794,8 @@ class Core:
 
     def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False, behaviour_perplexity=None,
              behaviour_segments=False, behaviour_sigma=None, behaviour_grid=None, gait=False, gait_on=None, gait_off=None, repair_pose=False,
-             repair_window=None, repair_threshold=None, repair_floor=None, repair_max_gap=None, treadmill=False, ball_radius=None):
+             repair_window=None, repair_threshold=None, repair_floor=None, repair_max_gap=None, treadmill=False, ball_radius=None,
+             robust_triangulation=False, robust_tau=None, robust_min_views=None):
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
         keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras).
         `rigid_legs=True` appends, after those, "points3d_rigid", "rigid_segment_lengths" and "rigid_fit_cost" (Core.rigid_legs()) and,
@@ -775,7 +828,15 @@ class Core:
         half_window, min_legs, iterations) and "treadmill_fps".  There are no "_rigid" twins: the ball is one object.  Together with
         gait, the swing/stance states of the measured pose are computed once and shared.  After track_detections() the result holds,
         directly after "points2d_argmax", "track_choice" [7, T, 19] int8 (the slot every chain took in every frame), "track_cost"
-        [7, 19] float64 (each chain's minimum) and "track_params" (tau, w_motion, w_value); without it no key is added."""
+        [7, 19] float64 (each chain's minimum) and "track_params" (tau, w_motion, w_value); without it no key is added.
+        `robust_triangulation=True` appends, after every other key (after the repair keys), the consensus triangulation of the detections
+        this save triangulates (Core.robust_triangulation() with `robust_tau`, pixels, one value or one per joint, and
+        `robust_min_views`; the default tau is a guess nobody has measured on a recording): "points3d_robust" [T, 38, 3] in the layout
+        of points3d_wo_procrustes, "robust_cameras" [T, 38] int32, "robust_status" [T, 38] int8, "robust_error" [7, T, 38],
+        "robust_counts" [38, 4], "points2d_robust" [7, T, 38, 2] (the detections with every rejected view replaced by the projection of
+        the robust point, divided by the image size like "points2d") and "robust_params" (the 38 values of tau, then min_views); every
+        other opt-in key of the same save is then computed from the robust pose -- repaired afterwards with repair_pose -- which is
+        computed once.  "points3d", "points3d_wo_procrustes" and "points2d" stay the plain triangulation's."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
@@ -796,6 +857,11 @@ class Core:
         if ball_radius is not None and not treadmill:
             raise ValueError("ball_radius belongs to treadmill: it needs treadmill=True")
         treadmill = {"radius": ops.treadmill_params(ball_radius)[0]} if treadmill else None   # refused before any work
+        if not robust_triangulation and (robust_tau is not None or robust_min_views is not None):
+            raise ValueError("robust_tau and robust_min_views belong to robust_triangulation: they need robust_triangulation=True")
+        robust = ops.consensus_params(robust_tau, robust_min_views) if robust_triangulation else None   # refused before any work
+        if robust is not None and robust[0].shape not in ((1,), (config["num_joints"],)):
+            raise ValueError(f"robust_tau must hold one value, or one per joint ({config['num_joints']})")
         segments = (behaviour_sigma, behaviour_grid) if behaviour_segments else None
         if segments is not None:   # refused before any work
             if behaviour_grid is not None:
@@ -805,13 +871,13 @@ class Core:
         if self.is_primary:
             try:
                 self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
-                                   repair, treadmill)
+                                   repair, treadmill, robust)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
     def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False,
-                      behaviour_perplexity=None, segments=None, gait=None, repair=None, treadmill=None):
+                      behaviour_perplexity=None, segments=None, gait=None, repair=None, treadmill=None, robust=None):
         if behaviour_map and getattr(self, "num_images", None) is not None:   # too short for the perplexity: refused before any work
             ops.behaviour_map_points(self.num_images, behaviour_perplexity)
         result = {"points2d": np.copy(self.points2d)}
@@ -836,9 +902,9 @@ class Core:
         if getattr(self, "_subpixel", False):   # only when this run refined its detections: without it the schema is the reference's
             result["subpixel"] = True
         # opt-in, like the two keys above: else the reference's schema
-        if joint_angles or rigid_legs or angle_spectrogram or behaviour_map or gait or repair or treadmill:
+        if joint_angles or rigid_legs or angle_spectrogram or behaviour_map or gait or repair or treadmill or robust is not None:
             result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
-                                               repair, treadmill))
+                                               repair, treadmill, robust))
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")
@@ -851,21 +917,33 @@ class Core:
     _KINEMATIC_KEYS += _SEGMENT_KEYS + tuple(k + "_rigid" for k in _SEGMENT_KEYS)
 
     _REPAIR_KEYS = ("points3d_repaired", "repair_status", "repair_counts", "repair_score", "repair_params")
+    _ROBUST_KEYS = ("points3d_robust", "robust_cameras", "robust_status", "robust_error", "robust_counts", "points2d_robust", "robust_params")
 
     def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity, segments=None, gait=None, repair=None,
-                        treadmill=None):
+                        treadmill=None, robust=None):
         """The keys save()'s flags append, in the result's order, all read from one PoseChain of this save's triangulation.
         `segments`: None, or (sigma, grid) of the segmentation of every map.  `gait`: None, or the thresholds of the gait analysis.
         `repair`: None, or the parameters of the pose repair; the one chain is then that of the repaired pose, repaired once.
-        `treadmill`: None, or the parameters of the treadmill analysis; with `gait` it takes the measured pose's states from that."""
+        `treadmill`: None, or the parameters of the treadmill analysis; with `gait` it takes the measured pose's states from that.
+        `robust`: None, or (tau, min_views) of the consensus triangulation; the one chain is then that of the robust pose (repaired
+        afterwards when `repair` is set), computed once."""
         what = ("joint_angles" if joint_angles else "rigid_legs" if rigid_legs else "angle_spectrogram" if angle_spectrogram
-                else "behaviour_map" if behaviour_map else "gait" if gait is not None else "treadmill" if treadmill is not None else "repair_pose")
+                else "behaviour_map" if behaviour_map else "gait" if gait is not None else "treadmill" if treadmill is not None
+                else "repair_pose" if repair is not None else "robust_triangulation")
         spectra = angle_spectrogram or behaviour_map
         fps, bank = self._wavelet_bank(what, None, {}) if spectra else (None, {})   # save()'s fps and frequencies are the method's defaults
         if (gait is not None or treadmill is not None) and fps is None:
             fps = self._gait_fps(None)   # the same rule
-        chains = [self._measured_pose(what, fps, repair)]
         keys, host = {}, lambda t: t.cpu().numpy()
+        robust_keys, pose = {}, None
+        if robust is not None:
+            r, _ = self._robust_on(what, *robust, X=self.camNet.points3d)   # _write_result has just triangulated these detections
+            scale = torch.tensor([float(v) for v in self.image_shape[::-1]], dtype=torch.float64, device=r.fixed_px.device)
+            robust_keys = dict(zip(self._ROBUST_KEYS, (host(r.points3d), host(r.cameras), host(r.status), host(r.error), host(r.counts),
+                                                       host(r.fixed_px / scale), np.append(r.params[0], float(r.params[1])))))
+            pose, r = r.points3d, None
+        chains = [self._measured_pose(what, fps, repair, pose)]
+        pose = None
         repair_keys = {}
         if repair is not None:
             r = chains[0].repair
@@ -915,7 +993,7 @@ class Core:
             S = m = None   # released before the other variant's is computed: one float64 spectrogram at a time
         if angle_spectrogram:
             keys["spectrogram_freqs"], keys["spectrogram_fps"] = bank["freqs"], fps
-        return {**{k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}, **gait_keys, **repair_keys}
+        return {**{k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}, **gait_keys, **repair_keys, **robust_keys}
 
     # -- helpers --------------------------------------------------------------------------------------
     def _correction_for(self, corrections, cam_id, img_id):

@@ -1,7 +1,8 @@
 """Thin host wrappers over the C ABI for the non-network kernels: arg-max and peaks, re-layout, triangulation, Procrustes and the
 video pose, and what DESIGN.md sections 9-19 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
 overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps, their segmentation, the gait analysis, the pose repair,
-the treadmill ball (section 21) and the tracking of the detections through time (section 22).
+the treadmill ball (section 21), the tracking of the detections through time (section 22) and the consensus triangulation over camera
+subsets (section 23).
 
 Inputs/outputs are torch CUDA tensors (device memory + stream plumbing only); every computation is a
 libdf3d_hip.so kernel.  No CPU fallback: a missing library or GPU raises `_native.NativeLibraryError`.
@@ -1625,6 +1626,112 @@ def tracked_points2d(points2d, camera_ordering, peak_pts, choice):
     moved = (choice != 0).to(torch.float32)[..., None].expand(7, T, 19, 2).contiguous()
     replace = relayout_19_to_38(moved, camera_ordering)[..., 0] != 0.0
     return torch.where(replace[..., None], relayout_19_to_38(chosen, camera_ordering), points2d)
+
+
+# ---- consensus triangulation over camera subsets ------------------------------------------------------------
+@dataclasses.dataclass
+class ConsensusResult:
+    """What `triangulate_consensus` returns, device tensors but for the last: points3d [T, J, 3] float64, cameras [T, J] int32 (bit c set
+    for each camera used), status [T, J] int8 (0 fewer than two views, 1 all views agree, 2 a proper subset was chosen, 3 no subset
+    qualified: the all-views point), error [ncam, T, J] float64 (every view's reprojection error against the chosen point, rejected
+    views included), fixed_px [ncam, T, J, 2] float64 (the detections with every rejected view replaced by the projection of the chosen
+    point), counts [J, 4] int64 (how often each status occurred per joint) and params (tau [J], min_views)."""
+    points3d: torch.Tensor
+    cameras: torch.Tensor
+    status: torch.Tensor
+    error: torch.Tensor
+    fixed_px: torch.Tensor
+    counts: torch.Tensor
+    params: tuple
+
+
+def consensus_params(tau=None, min_views=None):
+    """(tau, min_views) with config.ROBUST_TAU (20 px for each of the 38 joints, a guess nobody has measured on a recording) and
+    config.ROBUST_MIN_VIEWS for what is None.  tau: one number for every joint, or one per joint; returned as a float64 array of one or
+    J values.  ValueError: a tau that is no number, negative or NaN (+inf accepts every finite error), a min_views that is no integer
+    in config.ROBUST_MIN_VIEWS_RANGE."""
+    from . import config
+
+    if tau is None:
+        t = np.array(config.ROBUST_TAU, dtype=np.float64)
+    else:
+        if isinstance(tau, (bool, str)) or (isinstance(tau, (list, tuple, np.ndarray)) and np.asarray(tau).dtype.kind not in "fiu"):
+            raise ValueError(f"tau must be a number or one number per joint (it is {tau!r})")
+        try:
+            t = np.array(tau, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"tau must be a number or one number per joint (it is {tau!r})") from None
+    if t.size == 0 or not bool(np.all(t >= 0.0)):
+        raise ValueError("tau must be >= 0 and not NaN (+inf accepts every finite error)")
+    m = config.ROBUST_MIN_VIEWS if min_views is None else min_views
+    lo, hi = config.ROBUST_MIN_VIEWS_RANGE
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not lo <= m <= hi:
+        raise ValueError(f"min_views must be an integer in [{lo}, {hi}] (it is {m!r})")
+    return t, int(m)
+
+
+def _consensus_inputs(P, points2d_px, X):
+    """(Ph, X, ncam, T, J): the checks consensus_candidates and triangulate_consensus share; X = triangulate() when None."""
+    _need(points2d_px, torch.float64, "points2d_px")
+    if points2d_px.dim() != 4 or points2d_px.shape[3] != 2:
+        raise ValueError("points2d_px must be [ncam, T, J, 2]")
+    ncam, T, J, _ = points2d_px.shape
+    if not (1 <= ncam <= 8 and 1 <= J <= 64):
+        raise ValueError("points2d_px must hold 1 to 8 cameras and 1 to 64 joints")
+    Ph = np.ascontiguousarray(P.detach().cpu().numpy() if isinstance(P, torch.Tensor) else P, dtype=np.float64)
+    if Ph.shape != (ncam, 3, 4):
+        raise ValueError("P must be [ncam, 3, 4]")
+    if X is None:
+        X = triangulate(Ph, points2d_px)
+    else:
+        _need(X, torch.float64, "X")
+        if tuple(X.shape) != (T, J, 3) or X.device != points2d_px.device:
+            raise ValueError("X must be [T, J, 3] on the device of points2d_px")
+    return Ph, X, ncam, T, J
+
+
+@_on_tensor_device
+def consensus_candidates(P, points2d_px, X=None):
+    """Every candidate of the consensus triangulation at min_views = 2 (df3d_consensus_candidates), indexed by
+    camera bitmask: (cand_X [T, J, 2^ncam, 3], cand_q [T, J, 2^ncam, ncam]) float64 on the device -- the DLT point of every subset of
+    at least two views and the squared reprojection error of each of its cameras (+inf where the error is); 0 where a bitmask is no
+    candidate.  Arguments as triangulate_consensus.  For tests: the production path never stores the candidates."""
+    Ph, X, ncam, T, J = _consensus_inputs(P, points2d_px, X)
+    dev = points2d_px.device
+    cand_X = torch.zeros((T, J, 1 << ncam, 3), dtype=torch.float64, device=dev)
+    cand_q = torch.zeros((T, J, 1 << ncam, ncam), dtype=torch.float64, device=dev)
+    if T:
+        _bmap_call("df3d_consensus_candidates", Ph.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), points2d_px.data_ptr(), X.data_ptr(), ncam, T, J,
+                   cand_X.data_ptr(), cand_q.data_ptr(), _stream(points2d_px))
+    return cand_X, cand_q
+
+
+@_on_tensor_device
+def triangulate_consensus(P, points2d_px, X=None, tau=None, min_views=None):
+    """The 3-D point of every (frame, joint) from the largest set of cameras that agree (df3d_triangulate_consensus, DESIGN.md section
+    23), a ConsensusResult.  P [ncam, 3, 4] float64 (numpy or tensor, pixels); points2d_px [ncam, T, J, 2] float64 cuda (row_px, col_px);
+    X [T, J, 3] float64 cuda = triangulate() of the same detections, computed when None.  Every subset of a joint's views with at least
+    min_views cameras is triangulated; a subset qualifies when each of its cameras reprojects its point within tau[j] pixels; the
+    largest qualifying subset wins, ties to the smaller sum of squared errors, then to the smaller bitmask.  Two views that agree with
+    each other cannot be told from two correct ones: with three views and one wrong detection the wrong pair wins whenever the wrong
+    detection lies near an epipolar line.  Defaults and refusals: consensus_params."""
+    t, m = consensus_params(tau, min_views)   # refused before any device work
+    Ph, X, ncam, T, J = _consensus_inputs(P, points2d_px, X)
+    if t.shape not in ((1,), (J,)):
+        raise ValueError(f"tau must hold one value, or one per joint ({J})" + (" (config.ROBUST_TAU is for 38)" if tau is None else ""))
+    t = np.ascontiguousarray(np.broadcast_to(t, (J,)))
+    dev = points2d_px.device
+    out = ConsensusResult(torch.empty((T, J, 3), dtype=torch.float64, device=dev), torch.empty((T, J), dtype=torch.int32, device=dev),
+                          torch.empty((T, J), dtype=torch.int8, device=dev), torch.empty((ncam, T, J), dtype=torch.float64, device=dev),
+                          torch.empty((ncam, T, J, 2), dtype=torch.float64, device=dev), torch.zeros((J, 4), dtype=torch.int64, device=dev), (t, m))
+    if T:
+        need = _native.load().df3d_consensus_work_bytes(ncam, T, J)
+        work = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _bmap_call("df3d_triangulate_consensus", Ph.ctypes.data_as(dp), points2d_px.data_ptr(), X.data_ptr(), ncam, T, J, t.ctypes.data_as(dp), m,
+                   out.points3d.data_ptr(), out.cameras.data_ptr(), out.status.data_ptr(), out.error.data_ptr(), out.fixed_px.data_ptr(),
+                   out.counts.data_ptr(), work.data_ptr(), need, _stream(points2d_px))
+    return out
 
 
 def gaussian_window_taps(window_size, sigma, truncate=4.0):

@@ -557,6 +557,41 @@ int df3d_track_peaks(const int* count_dev, const float* pts_dev, const float* va
                      void* work_dev, long long work_len_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a19 consensus triangulation over camera subsets (the model is this project's own specification, stated in
+ *     float64 numpy by tests/consensus_oracle.py).  P_host [ncam, 3, 4] HOST float64 (pixels, no distortion: the DLT's model),
+ *     pts_px_dev [ncam, T, J, 2] (row_px, col_px), X_full_dev [T, J, 3] = df3d_triangulate of the same detections (the all-views
+ *     candidate is taken from it, not recomputed).  Per point (t, j): a camera is a view when both coordinates are non-zero (a6);
+ *     every subset S of the views with |S| >= max(min_views, 2) is a candidate; X_S is its DLT (the views' 4x4 contributions added in
+ *     ascending camera order, the a6 solve); camera c's error against a point is e = sqrt(q), q = du du + dv dv, du = u / w - col,
+ *     dv = v / w - row, [u, v, w] = P_c [X; 1] in left-to-right sums, e = +inf when w > 0 fails or e is not finite.  S qualifies
+ *     when every c in S has a finite e <= tau[j].  Chosen: the largest qualifying |S|, then the smaller sum of q over S (ascending
+ *     camera order from 0.0), then the smaller bitmask.
+ * df3d_triangulate_consensus: status_dev [T, J] int8: 0 = fewer than two views (X = 0, cameras = 0), 1 = the all-views set qualified
+ *     (X = X_full), 2 = a proper subset was chosen (X = X_S), 3 = no subset qualified (X = X_full, cameras = all views).  X_dev
+ *     [T, J, 3]; cameras_dev [T, J] int32, bit c set for each camera used; err_dev [ncam, T, J]: every view's e against the chosen X,
+ *     rejected views included, 0 for non-views and at status 0; fixed_px_dev [ncam, T, J, 2] (may be NULL): the input detections with
+ *     every rejected view (a view outside the chosen set) replaced by (v / w, u / w) of the chosen X; counts_dev [J, 4] int64 (may be
+ *     NULL): how often each status occurred per joint, counted in slices of 256 frames added in index order.  tau_host [J] HOST
+ *     float64, each >= 0 and not NaN (+inf accepts every finite error).  One launch for the points, two small ones for the counts;
+ *     the candidates are never stored.  No atomics: two calls on the same input give the same bits.
+ * df3d_consensus_candidates: every candidate of min_views = 2, indexed by camera bitmask: cand_X_dev [T, J, 2^ncam, 3] and
+ *     cand_q_dev [T, J, 2^ncam, ncam] (q of the cameras in the candidate, +inf where e is); entries that belong to no candidate are
+ *     0, the all-views entry holds X_full.  The candidate code is the fused entry's own; it exists so that the choice can be tested
+ *     against an oracle that is given the device's candidate points.
+ * df3d_consensus_work_bytes(ncam, T, J): the bytes of work_dev (0 where an argument is out of range): 32 J per slice of 256 frames.
+ * 1 <= ncam <= 8, 1 <= J <= 64, T >= 0 (T = 0 launches nothing and returns DF3D_OK), 2 <= min_views <= 8.  DF3D_EINVAL before the
+ *     device is touched, with a message, for a value outside those ranges, a bad tau, a workspace below the query, a null,
+ *     misaligned (8 bytes for float64 / int64, 4 for cameras) or overlapping buffer.  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------------------------------- */
+long long df3d_consensus_work_bytes(int ncam, int T, int J);
+int df3d_consensus_candidates(const double* P_host, const double* pts_px_dev, const double* X_full_dev, int ncam, int T, int J,
+                              double* cand_X_dev, double* cand_q_dev, void* stream);
+int df3d_triangulate_consensus(const double* P_host, const double* pts_px_dev, const double* X_full_dev, int ncam, int T, int J,
+                               const double* tau_host, int min_views, double* X_dev, int* cameras_dev, signed char* status_dev,
+                               double* err_dev, double* fixed_px_dev, long long* counts_dev, void* work_dev, long long work_bytes,
+                               void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
