@@ -139,6 +139,13 @@ PROTOTYPES = {
     "df3d_consensus_candidates": (c_int, [POINTER(c_double), c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "df3d_triangulate_consensus": (c_int, [POINTER(c_double), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_int, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_trajectory_work_bytes": (c_longlong, [c_int, c_int, c_int, c_int]),
+    "df3d_trajectory_linearize": (c_int, [POINTER(c_double), c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_trajectory_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_double), c_double, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_longlong, c_void_p]),
+    "df3d_triangulate_trajectory": (c_int, [POINTER(c_double), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_double, c_int, c_int,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
     "df3d_ba_eval": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_colsq": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_matvec": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -172,7 +172,41 @@ def parse_cli_args(argv=None):
                         "(default 20, a guess)")
     p.add_argument("--robust-min-views", dest="robust_min_views", type=int, default=None, metavar="N",
                    help="With --robust-triangulation: the fewest cameras a subset may hold, 2 to 8 (default 2)")
+    p.add_argument("--trajectory-triangulation", dest="trajectory_triangulation", action="store_true",
+                   help="Fit every joint's 3-D trajectory to the 2-D detections of the whole recording: per joint the points minimise a Huber "
+                        "loss (--trajectory-huber pixels) of every camera's reprojection error plus --trajectory-lambda times the squared "
+                        "second differences of the trajectory.  A frame one camera sees is fitted to that view and its neighbours instead "
+                        "of being written as missing, a detection that jumps away from the trajectory is down-weighted, and depth along a "
+                        "ray is smoothed more than the directions across it.  Appends, after every other key, points3d_trajectory "
+                        "[T, 38, 3], trajectory_status [T, 38] (int8: 0 outside every segment, the plain triangulation; 1 fitted; 2 filled "
+                        "from fewer than two views; 3 filled without a view; 4 the joint's fit did not converge), trajectory_weight "
+                        "[7, T, 38] (below 1: the camera to correct), trajectory_error [7, T, 38], trajectory_iterations [38], "
+                        "trajectory_cost [38, 2], trajectory_counts [38, 5] and trajectory_params to the result, and every other opt-in "
+                        "key is computed from the trajectory pose (repaired afterwards with --repair-pose); with --robust-triangulation "
+                        "the fit starts from the robust points and uses only the views the consensus kept.  points3d, "
+                        "points3d_wo_procrustes and points2d stay the plain triangulation's.  On clean detections the gain over the plain "
+                        "triangulation is small.  The defaults are guesses that nobody has measured on a recording.  Works with "
+                        "--skip-pose-estimation on an earlier result")
+    p.add_argument("--trajectory-lambda", dest="trajectory_lambda", type=float, default=None, metavar="L",
+                   help="With --trajectory-triangulation: the weight of the smoothness term, in px^2 / mm^2, >= 0 (default 1e3, a guess; 0 "
+                        "decouples the frames)")
+    p.add_argument("--trajectory-huber", dest="trajectory_huber", type=float, default=None, metavar="PX",
+                   help="With --trajectory-triangulation: the reprojection error, in pixels, beyond which a view's loss grows linearly "
+                        "(default 10, a guess; inf is plain least squares)")
+    p.add_argument("--trajectory-max-gap", dest="trajectory_max_gap", type=int, default=None, metavar="N",
+                   help="With --trajectory-triangulation: the longest run of frames without two views that a segment bridges, 0 to 1000000 "
+                        "(default 10, a guess)")
     args = p.parse_args(argv)
+    for name in ("lambda", "huber", "max_gap"):
+        if getattr(args, "trajectory_" + name) is not None and not args.trajectory_triangulation:
+            p.error(f"--trajectory-{name.replace('_', '-')} sets a parameter of --trajectory-triangulation: it needs --trajectory-triangulation")
+    if args.trajectory_triangulation:
+        from . import ops
+
+        try:
+            ops.trajectory_params(args.trajectory_lambda, args.trajectory_huber, args.trajectory_max_gap)
+        except ValueError as e:
+            p.error(f"--trajectory-lambda, --trajectory-huber and --trajectory-max-gap: {e}")
     for name in ("tau", "min_views"):
         if getattr(args, "robust_" + name) is not None and not args.robust_triangulation:
             p.error(f"--robust-{name.replace('_', '-')} sets a parameter of --robust-triangulation: it needs --robust-triangulation")
@@ -296,6 +330,10 @@ def run(args):
     if getattr(args, "robust_triangulation", False):   # after the other flags: its keys come last
         flagged.append("robust_triangulation")
         extras.update(robust_triangulation=True, robust_tau=getattr(args, "robust_tau", None), robust_min_views=getattr(args, "robust_min_views", None))
+    if getattr(args, "trajectory_triangulation", False):   # after the robust keys
+        flagged.append("trajectory_triangulation")
+        extras.update(trajectory_triangulation=True, trajectory_lambda=getattr(args, "trajectory_lambda", None),
+                      trajectory_huber=getattr(args, "trajectory_huber", None), trajectory_max_gap=getattr(args, "trajectory_max_gap", None))
     if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not flagged:
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0

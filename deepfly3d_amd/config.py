@@ -70,6 +70,35 @@ ROBUST_TAU = np.full(38, 20.0, dtype=np.float64)
 ROBUST_MIN_VIEWS = 2
 ROBUST_MIN_VIEWS_RANGE = (2, 8)
 
+# ---- trajectory triangulation: per joint, the 3-D points of a whole recording minimise the Huber loss
+# (TRAJECTORY_HUBER pixels) of every view's reprojection error plus TRAJECTORY_LAMBDA[j] (px^2 / mm^2) times the squared second
+# differences of the trajectory.  The two defaults come from a sweep of tests/trajectory_oracle.py on planted trajectories (section 24
+# holds it) and are guesses: nobody has measured them on a recording.  Segments bridge at most REPAIR_MAX_GAP frames without a pair
+# of views unless max_gap says otherwise.  The damped Gauss-Newton iteration starts at TRAJECTORY_MU_INIT, divides the damping by 10
+# after an accepted trial (never below TRAJECTORY_MU_MIN: a frame no camera sees needs it when lambda is 0) and multiplies it by 10
+# after a rejected one; a trial is accepted when its cost is at most (1 + TRAJECTORY_SLACK) times the cost before; a chain has
+# converged when no coordinate of a step moves by TRAJECTORY_STEP_TOL mm, has stalled when the damping passes TRAJECTORY_MU_MAX and is
+# out of iterations after TRAJECTORY_MAX_ITER trials.  trajectory_block_frames(T) frames are one lane's share of the banded solve: the
+# lanes' interiors are serial in the block's frames and the separators' system in the number of blocks, so the block grows with the
+# square root of the recording (32 frames at 1 000, the best of DESIGN.md section 24's table) and both serial parts with it.
+TRAJECTORY_LAMBDA = np.full(38, 1e3, dtype=np.float64)
+TRAJECTORY_HUBER = 10.0
+TRAJECTORY_MU_INIT = 1e-3
+TRAJECTORY_MU_MIN = 1e-6
+TRAJECTORY_MU_MAX = 1e12
+TRAJECTORY_SLACK = 1e-12
+TRAJECTORY_STEP_TOL = 1e-8
+TRAJECTORY_MAX_ITER = 300
+TRAJECTORY_BLOCK_FRAMES_RANGE = (3, 1 << 20)
+TRAJECTORY_MAX_FRAMES = 1 << 20
+
+
+def trajectory_block_frames(frames):
+    """The default block of the trajectory fit's banded solve for a recording of `frames` frames: ceil(sqrt(frames)), within the range."""
+    lo, hi = TRAJECTORY_BLOCK_FRAMES_RANGE
+    return int(min(max(lo, int(np.ceil(np.sqrt(max(int(frames), 0))))), hi))
+
+
 # ---- leg joint angles (DESIGN.md section 14).  Leg L = 3 side + l (l = 0, 1, 2: front, mid, hind) owns the five joints
 # 19 side + 5 l + k; its eight angles come in this order: thorax-coxa yaw, pitch and roll, coxa-trochanter pitch and roll,
 # femur-tibia pitch and roll, tibia-tarsus pitch; its four segment lengths are coxa, femur, tibia, tarsus.

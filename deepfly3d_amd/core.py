@@ -443,6 +443,48 @@ class Core:
             return [int(c) for c in np.nonzero(rejected[:, int(joint_id)])[0]]
         return {int(j): [int(c) for c in np.nonzero(rejected[:, j])[0]] for j in np.nonzero(rejected.any(axis=0))[0]}
 
+    # -- trajectory triangulation: a rank-0 method on the detections save() triangulates ------------------------------
+    def _trajectory_on(self, what, params, X=None, robust=None):
+        """The ops.TrajectoryResult on the device of the camera network's detections, with the refusals of _robust_on.  `params`:
+        ops.trajectory_params' values.  `X`: the triangulation [T, 38, 3] of these very detections as a numpy array where the caller
+        has just computed it (save()); else it is computed here.  `robust`: None, or what _robust_on returned for these detections:
+        the fit then starts from the robust points and sees only the views the consensus kept -- a rejected view is zeroed, not
+        replaced by its projection, which would count the point's own projection as evidence."""
+        from . import distributed as dd
+
+        if dd.current()[0] != 0:
+            raise RuntimeError(f"{what} is a rank-0 method: the camera network lives on rank 0")
+        if self.camNet is None or not self.camNet.has_calibration():
+            raise RuntimeError(f"{what} needs calibrated cameras: run calibrate_calc() first")
+        _native.require_gpu()
+        dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
+        P = np.stack([c.P for c in self.camNet.cam_list])
+        if robust is not None:
+            r, px = robust
+            kept = ((r.cameras[None] >> torch.arange(px.shape[0], device=px.device)[:, None, None]) & 1) != 0
+            kept |= (r.status == 0)[None]   # fewer than two views: the consensus rejected nothing there, and the lone view is evidence
+            px, X = torch.where(kept[..., None], px, torch.zeros_like(px)), r.points3d
+        else:
+            px = torch.from_numpy(np.ascontiguousarray(self.camNet.points2d, dtype=np.float64)).to(dev)
+            if X is not None:
+                X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev)
+        lam, huber, max_gap, _ = params
+        return ops.triangulate_trajectory(P, px.contiguous(), X, lam=lam, huber=huber, max_gap=max_gap)
+
+    def trajectory_triangulation(self, lam=None, huber=None, max_gap=None):
+        """The trajectory triangulation (ops.triangulate_trajectory) of the camera network's detections -- the
+        ones save() triangulates, stored corrections included -- an ops.TrajectoryResult of numpy arrays: points3d [T, 38, 3] (in the
+        layout of points3d_wo_procrustes), status [T, 38] int8 (0 outside every segment: the plain triangulation's point, 1 anchor, 2
+        a frame fewer than two cameras see, filled from its one view and its neighbours, 3 a frame no camera sees, 4 a frame of a joint
+        whose fit did not converge), weight [7, T, 38] (below 1: the camera to correct), error [7, T, 38] pixels, iterations [38],
+        cost [38, 2], counts [38, 5] and params (lam [38], huber, max_gap, block_frames).  `lam`: px^2 / mm^2, one value or one per
+        joint; `huber`: pixels; both defaults (config.TRAJECTORY_LAMBDA, config.TRAJECTORY_HUBER) are guesses nobody has measured on
+        a recording.  A rank-0 method with the refusals of the reprojection-error queries."""
+        params = ops.trajectory_params(lam, huber, max_gap)   # refused before any work
+        r = self._trajectory_on("trajectory_triangulation", params)
+        return ops.TrajectoryResult(*(v.cpu().numpy() for v in (r.points3d, r.status, r.weight, r.error, r.iterations, r.cost, r.counts)),
+                                    r.params)
+
     # -- the kinematic chain (DESIGN.md sections 14-17): one kinematics.PoseChain per call, never kept ----------------------------------
     def _measured_pose(self, what, fps=None, repair=None, pose=None):
         """The PoseChain of camNet.points3d on the device (triangulating first when there is none), with the refusals of the rank-0
@@ -795,6 +837,7 @@ class Core:
     def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False, behaviour_perplexity=None,
              behaviour_segments=False, behaviour_sigma=None, behaviour_grid=None, gait=False, gait_on=None, gait_off=None, repair_pose=False,
              repair_window=None, repair_threshold=None, repair_floor=None, repair_max_gap=None, treadmill=False, ball_radius=None,
+             trajectory_triangulation=False, trajectory_lambda=None, trajectory_huber=None, trajectory_max_gap=None,
              robust_triangulation=False, robust_tau=None, robust_min_views=None):
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
         keys "joint_angles" and "segment_lengths" (Core.joint_angles() of this save's triangulation; needs calibrated cameras).
@@ -836,7 +879,16 @@ class Core:
         "robust_counts" [38, 4], "points2d_robust" [7, T, 38, 2] (the detections with every rejected view replaced by the projection of
         the robust point, divided by the image size like "points2d") and "robust_params" (the 38 values of tau, then min_views); every
         other opt-in key of the same save is then computed from the robust pose -- repaired afterwards with repair_pose -- which is
-        computed once.  "points3d", "points3d_wo_procrustes" and "points2d" stay the plain triangulation's."""
+        computed once.  "points3d", "points3d_wo_procrustes" and "points2d" stay the plain triangulation's.
+        `trajectory_triangulation=True` appends, after every other key (after the robust keys), the trajectory triangulation of the
+        detections this save triangulates (Core.trajectory_triangulation() with `trajectory_lambda`, px^2 / mm^2, one value or one per
+        joint, `trajectory_huber`, pixels, and `trajectory_max_gap`; the defaults are guesses nobody has measured on a recording):
+        "points3d_trajectory" [T, 38, 3] in the layout of points3d_wo_procrustes, "trajectory_status" [T, 38] int8, "trajectory_weight"
+        and "trajectory_error" [7, T, 38], "trajectory_iterations" [38], "trajectory_cost" [38, 2], "trajectory_counts" [38, 5] and
+        "trajectory_params" (the 38 values of lambda, then huber, then max_gap).  The stages run in the order robust, trajectory,
+        repair: together with robust_triangulation the fit starts from the robust points and sees only the views the consensus kept;
+        every other opt-in key of the same save is computed from the trajectory pose (repaired afterwards with repair_pose), which is
+        computed once."""
         from . import distributed as dd
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
@@ -862,6 +914,13 @@ class Core:
         robust = ops.consensus_params(robust_tau, robust_min_views) if robust_triangulation else None   # refused before any work
         if robust is not None and robust[0].shape not in ((1,), (config["num_joints"],)):
             raise ValueError(f"robust_tau must hold one value, or one per joint ({config['num_joints']})")
+        if not trajectory_triangulation and any(v is not None for v in (trajectory_lambda, trajectory_huber, trajectory_max_gap)):
+            raise ValueError("trajectory_lambda, trajectory_huber and trajectory_max_gap belong to trajectory_triangulation: "
+                             "they need trajectory_triangulation=True")
+        trajectory = (ops.trajectory_params(trajectory_lambda, trajectory_huber, trajectory_max_gap)
+                      if trajectory_triangulation else None)   # refused before any work
+        if trajectory is not None and trajectory[0].shape not in ((1,), (config["num_joints"],)):
+            raise ValueError(f"trajectory_lambda must hold one value, or one per joint ({config['num_joints']})")
         segments = (behaviour_sigma, behaviour_grid) if behaviour_segments else None
         if segments is not None:   # refused before any work
             if behaviour_grid is not None:
@@ -871,13 +930,13 @@ class Core:
         if self.is_primary:
             try:
                 self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
-                                   repair, treadmill, robust)
+                                   repair, treadmill, robust, trajectory)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
     def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False,
-                      behaviour_perplexity=None, segments=None, gait=None, repair=None, treadmill=None, robust=None):
+                      behaviour_perplexity=None, segments=None, gait=None, repair=None, treadmill=None, robust=None, trajectory=None):
         if behaviour_map and getattr(self, "num_images", None) is not None:   # too short for the perplexity: refused before any work
             ops.behaviour_map_points(self.num_images, behaviour_perplexity)
         result = {"points2d": np.copy(self.points2d)}
@@ -902,9 +961,10 @@ class Core:
         if getattr(self, "_subpixel", False):   # only when this run refined its detections: without it the schema is the reference's
             result["subpixel"] = True
         # opt-in, like the two keys above: else the reference's schema
-        if joint_angles or rigid_legs or angle_spectrogram or behaviour_map or gait or repair or treadmill or robust is not None:
+        if (joint_angles or rigid_legs or angle_spectrogram or behaviour_map or gait or repair or treadmill or robust is not None
+                or trajectory is not None):
             result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
-                                               repair, treadmill, robust))
+                                               repair, treadmill, robust, trajectory))
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")
@@ -918,30 +978,41 @@ class Core:
 
     _REPAIR_KEYS = ("points3d_repaired", "repair_status", "repair_counts", "repair_score", "repair_params")
     _ROBUST_KEYS = ("points3d_robust", "robust_cameras", "robust_status", "robust_error", "robust_counts", "points2d_robust", "robust_params")
+    _TRAJECTORY_KEYS = ("points3d_trajectory", "trajectory_status", "trajectory_weight", "trajectory_error", "trajectory_iterations",
+                        "trajectory_cost", "trajectory_counts", "trajectory_params")
 
     def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity, segments=None, gait=None, repair=None,
-                        treadmill=None, robust=None):
+                        treadmill=None, robust=None, trajectory=None):
         """The keys save()'s flags append, in the result's order, all read from one PoseChain of this save's triangulation.
         `segments`: None, or (sigma, grid) of the segmentation of every map.  `gait`: None, or the thresholds of the gait analysis.
         `repair`: None, or the parameters of the pose repair; the one chain is then that of the repaired pose, repaired once.
         `treadmill`: None, or the parameters of the treadmill analysis; with `gait` it takes the measured pose's states from that.
         `robust`: None, or (tau, min_views) of the consensus triangulation; the one chain is then that of the robust pose (repaired
-        afterwards when `repair` is set), computed once."""
+        afterwards when `repair` is set), computed once.  `trajectory`: None, or ops.trajectory_params' values of the trajectory
+        triangulation, which runs after the consensus and before the repair; the one chain is then that of the trajectory pose."""
         what = ("joint_angles" if joint_angles else "rigid_legs" if rigid_legs else "angle_spectrogram" if angle_spectrogram
                 else "behaviour_map" if behaviour_map else "gait" if gait is not None else "treadmill" if treadmill is not None
-                else "repair_pose" if repair is not None else "robust_triangulation")
+                else "repair_pose" if repair is not None else "robust_triangulation" if robust is not None else "trajectory_triangulation")
         spectra = angle_spectrogram or behaviour_map
         fps, bank = self._wavelet_bank(what, None, {}) if spectra else (None, {})   # save()'s fps and frequencies are the method's defaults
         if (gait is not None or treadmill is not None) and fps is None:
             fps = self._gait_fps(None)   # the same rule
         keys, host = {}, lambda t: t.cpu().numpy()
-        robust_keys, pose = {}, None
+        robust_keys, trajectory_keys, pose, kept = {}, {}, None, None
         if robust is not None:
-            r, _ = self._robust_on(what, *robust, X=self.camNet.points3d)   # _write_result has just triangulated these detections
+            r, px = self._robust_on(what, *robust, X=self.camNet.points3d)   # _write_result has just triangulated these detections
+            kept = (r, px) if trajectory is not None else None   # the fit then sees the views the consensus kept, and starts from its points
+            px = None
             scale = torch.tensor([float(v) for v in self.image_shape[::-1]], dtype=torch.float64, device=r.fixed_px.device)
             robust_keys = dict(zip(self._ROBUST_KEYS, (host(r.points3d), host(r.cameras), host(r.status), host(r.error), host(r.counts),
                                                        host(r.fixed_px / scale), np.append(r.params[0], float(r.params[1])))))
             pose, r = r.points3d, None
+        if trajectory is not None:
+            r = self._trajectory_on(what, trajectory, X=self.camNet.points3d, robust=kept)
+            trajectory_keys = dict(zip(self._TRAJECTORY_KEYS, (host(r.points3d), host(r.status), host(r.weight), host(r.error), host(r.iterations),
+                                                               host(r.cost), host(r.counts),
+                                                               np.append(r.params[0], [float(r.params[1]), float(r.params[2])]))))
+            pose, r, kept = r.points3d, None, None
         chains = [self._measured_pose(what, fps, repair, pose)]
         pose = None
         repair_keys = {}
@@ -993,7 +1064,7 @@ class Core:
             S = m = None   # released before the other variant's is computed: one float64 spectrogram at a time
         if angle_spectrogram:
             keys["spectrogram_freqs"], keys["spectrogram_fps"] = bank["freqs"], fps
-        return {**{k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}, **gait_keys, **repair_keys, **robust_keys}
+        return {**{k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}, **gait_keys, **repair_keys, **robust_keys, **trajectory_keys}
 
     # -- helpers --------------------------------------------------------------------------------------
     def _correction_for(self, corrections, cam_id, img_id):

@@ -1,8 +1,8 @@
 """Thin host wrappers over the C ABI for the non-network kernels: arg-max and peaks, re-layout, triangulation, Procrustes and the
 video pose, and what DESIGN.md sections 9-19 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
 overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps, their segmentation, the gait analysis, the pose repair,
-the treadmill ball (section 21), the tracking of the detections through time (section 22) and the consensus triangulation over camera
-subsets (section 23).
+the treadmill ball (section 21), the tracking of the detections through time (section 22), the consensus triangulation over camera
+subsets (section 23) and the trajectory triangulation (section 24).
 
 Inputs/outputs are torch CUDA tensors (device memory + stream plumbing only); every computation is a
 libdf3d_hip.so kernel.  No CPU fallback: a missing library or GPU raises `_native.NativeLibraryError`.
@@ -1731,6 +1731,148 @@ def triangulate_consensus(P, points2d_px, X=None, tau=None, min_views=None):
         _bmap_call("df3d_triangulate_consensus", Ph.ctypes.data_as(dp), points2d_px.data_ptr(), X.data_ptr(), ncam, T, J, t.ctypes.data_as(dp), m,
                    out.points3d.data_ptr(), out.cameras.data_ptr(), out.status.data_ptr(), out.error.data_ptr(), out.fixed_px.data_ptr(),
                    out.counts.data_ptr(), work.data_ptr(), need, _stream(points2d_px))
+    return out
+
+
+# ---- trajectory triangulation: robust smoothing on the 2-D evidence ------------------------------------------
+@dataclasses.dataclass
+class TrajectoryResult:
+    """What `triangulate_trajectory` returns, device tensors but for the last: points3d [T, J, 3] float64, status [T, J] int8 (0 not in
+    a segment: the input's bits, 1 anchor, 2 filled frame with at least one view, 3 filled frame without a view, 4 a frame of a chain
+    that did not converge: the last accepted iterate), weight [ncam, T, J] float64 (every view's final IRLS weight; below 1 names the
+    camera to correct), error [ncam, T, J] float64 (every view's reprojection error against the final point), iterations [J] int32,
+    cost [J, 2] float64 (start, final), counts [J, 5] int64 and params (lam [J], huber, max_gap, block_frames)."""
+    points3d: torch.Tensor
+    status: torch.Tensor
+    weight: torch.Tensor
+    error: torch.Tensor
+    iterations: torch.Tensor
+    cost: torch.Tensor
+    counts: torch.Tensor
+    params: tuple
+
+
+def trajectory_params(lam=None, huber=None, max_gap=None, block_frames=None):
+    """(lam, huber, max_gap, block_frames) with config.TRAJECTORY_LAMBDA (1e3 px^2 / mm^2 for each of the 38 joints),
+    config.TRAJECTORY_HUBER (pixels) and config.REPAIR_MAX_GAP for what is None -- lam and huber are guesses nobody has measured on a
+    recording; a block_frames of None stays None: the fit then takes config.trajectory_block_frames(T), which grows with sqrt(T).  lam: one number for every joint, or one per joint; returned as a float64 array of one
+    or J values.  ValueError: a lam that is no number, negative or not finite, a huber that is no number, negative or NaN (+inf is plain
+    least squares), a max_gap that is no integer in config.REPAIR_MAX_GAP_RANGE, a block_frames that is no integer in
+    config.TRAJECTORY_BLOCK_FRAMES_RANGE."""
+    from . import config
+
+    if lam is None:
+        l = np.array(config.TRAJECTORY_LAMBDA, dtype=np.float64)
+    else:
+        if isinstance(lam, (bool, str)) or (isinstance(lam, (list, tuple, np.ndarray)) and np.asarray(lam).dtype.kind not in "fiu"):
+            raise ValueError(f"lam must be a number or one number per joint (it is {lam!r})")
+        try:
+            l = np.array(lam, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"lam must be a number or one number per joint (it is {lam!r})") from None
+    if l.size == 0 or not bool(np.all((l >= 0.0) & np.isfinite(l))):
+        raise ValueError("lam must be >= 0 and finite")
+    h = config.TRAJECTORY_HUBER if huber is None else huber
+    if isinstance(h, (bool, str)) or not isinstance(h, (int, float, np.integer, np.floating)):
+        raise ValueError(f"huber must be a number (it is {h!r})")
+    if not float(h) >= 0.0:
+        raise ValueError("huber must be >= 0 and not NaN (+inf is plain least squares)")
+
+    def integer(v, lo, hi, name):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (it is {v!r})")
+        return int(v)
+
+    gap = integer(config.REPAIR_MAX_GAP if max_gap is None else max_gap, *config.REPAIR_MAX_GAP_RANGE, "max_gap")
+    b = None if block_frames is None else integer(block_frames, *config.TRAJECTORY_BLOCK_FRAMES_RANGE, "block_frames")
+    return l, float(h), gap, b
+
+
+def _trajectory_lambda(l, J, default):
+    if l.shape not in ((1,), (J,)):
+        raise ValueError(f"lam must hold one value, or one per joint ({J})" + (" (config.TRAJECTORY_LAMBDA is for 38)" if default else ""))
+    return np.ascontiguousarray(np.broadcast_to(l, (J,)))
+
+
+def _trajectory_work(ncam, T, J, b, dev):
+    """(work, bytes, block_frames): the workspace of the fit and the solve; block_frames None is config.trajectory_block_frames(T)."""
+    from . import config
+
+    b = config.trajectory_block_frames(T) if b is None else b
+    need = _native.load().df3d_trajectory_work_bytes(ncam, T, J, b)
+    if need <= 0:
+        raise ValueError(f"no workspace for {T} frames: T must be at most {config.TRAJECTORY_MAX_FRAMES}")
+    return torch.empty((need,), dtype=torch.uint8, device=dev), need, b
+
+
+@_on_tensor_device
+def trajectory_linearize(P, points2d_px, X, huber=None):
+    """(H [T, J, 6], g [T, J, 3], weight [ncam, T, J], error [ncam, T, J], cost [J]) float64 on the device: the Gauss-Newton terms of every
+    frame's views at X [T, J, 3] (df3d_trajectory_linearize) and each chain's sum of Huber terms.  For tests."""
+    h = trajectory_params(huber=huber)[1]
+    Ph, X, ncam, T, J = _consensus_inputs(P, points2d_px, X)
+    X, points2d_px = X.contiguous(), points2d_px.contiguous()
+    dev = points2d_px.device
+    out = (torch.zeros((T, J, 6), dtype=torch.float64, device=dev), torch.zeros((T, J, 3), dtype=torch.float64, device=dev),
+           torch.zeros((ncam, T, J), dtype=torch.float64, device=dev), torch.zeros((ncam, T, J), dtype=torch.float64, device=dev),
+           torch.zeros((J,), dtype=torch.float64, device=dev))
+    if T:
+        work = torch.empty((T * J,), dtype=torch.float64, device=dev)
+        _bmap_call("df3d_trajectory_linearize", Ph.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), points2d_px.data_ptr(), X.data_ptr(), ncam, T, J,
+                   h, *(o.data_ptr() for o in out), work.data_ptr(), T * J * 8, _stream(points2d_px))
+    return out
+
+
+@_on_tensor_device
+def trajectory_solve(H, g, segment, lam, mu, block_frames=None):
+    """(d [T, J, 3] float64, ok [J] int32): one damped banded solve (H + lam K + mu I) d = -g of every chain (df3d_trajectory_solve, DESIGN.md
+    section 24).  H [T, J, 6], g [T, J, 3] float64 cuda (the whole gradient), segment [T, J] int8 cuda (non-zero: the frame is an
+    unknown).  For tests."""
+    l, _, _, b = trajectory_params(lam=lam, block_frames=block_frames)
+    _need(H, torch.float64, "H")
+    _need(g, torch.float64, "g")
+    _need(segment, torch.int8, "segment")
+    if H.dim() != 3 or H.shape[2] != 6 or tuple(g.shape) != tuple(H.shape[:2]) + (3,) or tuple(segment.shape) != tuple(H.shape[:2]):
+        raise ValueError("H must be [T, J, 6], g [T, J, 3] and segment [T, J]")
+    T, J, _ = H.shape
+    if not 1 <= J <= 64:
+        raise ValueError("H must hold 1 to 64 joints")
+    l = _trajectory_lambda(l, J, False)
+    dev = H.device
+    d = torch.zeros((T, J, 3), dtype=torch.float64, device=dev)
+    ok = torch.ones((J,), dtype=torch.int32, device=dev)
+    if T:
+        work, need, b = _trajectory_work(1, T, J, b, dev)
+        _bmap_call("df3d_trajectory_solve", H.contiguous().data_ptr(), g.contiguous().data_ptr(), segment.contiguous().data_ptr(), T, J,
+                   l.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(mu), b, d.data_ptr(), ok.data_ptr(), None, work.data_ptr(), need, _stream(H))
+    return d, ok
+
+
+@_on_tensor_device
+def triangulate_trajectory(P, points2d_px, X=None, lam=None, huber=None, max_gap=None, block_frames=None):
+    """The 3-D trajectory of every joint over the whole recording (df3d_triangulate_trajectory), a TrajectoryResult.
+    P [ncam, 3, 4] float64 (numpy or tensor, pixels); points2d_px [ncam, T, J, 2] float64 cuda (row_px, col_px); X [T, J, 3] float64 cuda
+    = triangulate() of the same detections, the start, computed when None.  Per joint the points minimise the Huber loss (huber, px) of
+    every view's reprojection error plus lam (px^2 / mm^2) times the squared second differences of the trajectory, over every segment:
+    a run of frames that starts and ends at a frame with two views and bridges at most max_gap frames without.  A frame one camera sees
+    is fitted to that view and its neighbours; a frame outside every segment keeps its input.  The result does not depend on
+    block_frames beyond rounding.  At most config.TRAJECTORY_MAX_FRAMES frames; a joint's whole iteration is one workgroup's work, about
+    0.1 s per 1 000 frames of the slowest joint on an MI355X and not measured beyond 20 000 frames.  Defaults and refusals: trajectory_params."""
+    l, h, gap, b = trajectory_params(lam, huber, max_gap, block_frames)   # refused before any device work
+    Ph, X, ncam, T, J = _consensus_inputs(P, points2d_px, X)
+    l = _trajectory_lambda(l, J, lam is None)
+    dev = points2d_px.device
+    out = TrajectoryResult(torch.empty((T, J, 3), dtype=torch.float64, device=dev), torch.empty((T, J), dtype=torch.int8, device=dev),
+                           torch.empty((ncam, T, J), dtype=torch.float64, device=dev), torch.empty((ncam, T, J), dtype=torch.float64, device=dev),
+                           torch.zeros((J,), dtype=torch.int32, device=dev), torch.zeros((J, 2), dtype=torch.float64, device=dev),
+                           torch.zeros((J, 5), dtype=torch.int64, device=dev), (l, h, gap, b))
+    if T:
+        work, need, b = _trajectory_work(ncam, T, J, b, dev)
+        out.params = (l, h, gap, b)
+        dp = ctypes.POINTER(ctypes.c_double)
+        _bmap_call("df3d_triangulate_trajectory", Ph.ctypes.data_as(dp), points2d_px.contiguous().data_ptr(), X.contiguous().data_ptr(), ncam, T, J,
+                   l.ctypes.data_as(dp), h, gap, b, out.points3d.data_ptr(), out.status.data_ptr(), out.weight.data_ptr(), out.error.data_ptr(),
+                   out.iterations.data_ptr(), out.cost.data_ptr(), out.counts.data_ptr(), work.data_ptr(), need, _stream(points2d_px))
     return out
 
 

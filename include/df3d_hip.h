@@ -592,6 +592,54 @@ int df3d_triangulate_consensus(const double* P_host, const double* pts_px_dev, c
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a20 trajectory triangulation (the model is this project's own specification, stated in float64 numpy by
+ *     tests/trajectory_oracle.py, whose header lists every operation).  P_host [ncam, 3, 4] HOST float64; pts_px_dev [ncam, T, J, 2]
+ *     (row_px, col_px); a camera is a view of (t, j) when both coordinates are non-zero (a6).  Per joint j (a chain) the points
+ *     X[0 .. T - 1] minimise  sum over frames and views of huber_delta(e) + lambda[j] sum |X[t - 1] - 2 X[t] + X[t + 1]|^2,  e the
+ *     reprojection error of a19, huber(e) = e e for e <= delta, else 2 delta e - delta delta; a view with w > 0 false or a non-finite
+ *     error has weight 0.  An anchor is a frame with at least two views and a finite X0; the unknowns (the active frames) are the
+ *     anchors and the frames between two anchors at most max_gap frames apart, where at least three such frames are consecutive;
+ *     every other frame keeps the bits of X0.  Damped Gauss-Newton with IRLS weights (1, or delta / e beyond delta), one damping and
+ *     one accept / reject decision per chain.
+ * df3d_trajectory_linearize: at X_dev [T, J, 3], every frame: H_dev [T, J, 6] (sum of weight J^T J over the valid views in ascending
+ *     camera order; entries 00 01 02 11 12 22), g_dev [T, J, 3] (sum of weight J^T r), weight_dev and err_dev [ncam, T, J] (0 for a
+ *     non-view; an invalid view has weight 0 and error +inf), cost_dev [J] (the sum of the frames' huber terms in the model's fixed
+ *     order: lane k adds the frames k, k + 256, ...; the 256 partial sums are halved 128, 64, ... 1).  work_dev: 8 T J bytes.
+ * df3d_trajectory_solve: d_dev [T, J, 3] = -(H + lambda K + mu I)^-1 g on the frames where segment_dev [T, J] (int8) is non-zero, 0
+ *     elsewhere; K is the Gram matrix of the second differences over the triples of consecutive non-zero frames, times I3; g_dev is
+ *     the whole gradient.  The chain is cut into blocks of min(block_frames, max(T, 3)) frames, each lane eliminates its block's
+ *     interior, the separators (the last two frames of every block) are solved as one banded system, the interiors are substituted
+ *     back; block_frames >= T is the serial factorisation.  ok_dev [J] int32: 1 when every pivot was > 0.  ticks_dev [J, 4] int64 (may be NULL): the
+ *     device's wall clock after the assembly, the interiors, the separators and the substitution of each chain, for
+ *     tests/perf/bench_trajectory.py.
+ * df3d_triangulate_trajectory: the whole fit from X0_dev [T, J, 3] (df3d_triangulate of the same detections), one persistent workgroup
+ *     per chain.  X_dev [T, J, 3]; status_dev [T, J] int8: 0 not active (copied), 1 anchor, 2 filled frame with at least one view, 3
+ *     filled frame without a view, 4 active frame of a chain that did not converge (the last accepted iterate); weight_dev, err_dev
+ *     [ncam, T, J] at the final X (0 where the frame is not active); iterations_dev [J] int32 (accepted trials); cost_dev [J, 2]
+ *     (start, final); counts_dev [J, 5] int64.  lambda_host [J] HOST float64, px^2 / mm^2, each >= 0 and finite; delta >= 0, not NaN
+ *     (+inf: plain least squares).
+ * df3d_trajectory_work_bytes(ncam, T, J, block_frames): the bytes of work_dev for the fit and the solve (0 where an argument is out
+ *     of range, and for T = 0).
+ * 1 <= ncam <= 8, 1 <= J <= 64, 0 <= T <= 1048576 (T = 0 launches nothing and returns DF3D_OK), 3 <= block_frames <= 1048576,
+ *     0 <= max_gap <= 1000000, 0 <= mu <= 1e13.  DF3D_EINVAL before the device is touched, with a message, for a value outside those
+ *     ranges, a bad lambda or delta, a workspace below the query, a null, misaligned (8 bytes for float64 / int64, 4 for int32) or
+ *     overlapping buffer.  No atomics: two calls on the same input give the same bits.  Asynchronous on `stream`.
+ *     A chain's whole iteration is one workgroup's launch: 0.11 s per 1 000 frames and 1.1 s per 20 000 on an MI355X at the fly layout
+ *     (the slowest chain's 128 and 151 iterations); longer recordings were not measured, and 2^20 frames would run for about a minute.
+ * ---------------------------------------------------------------------------------------------- */
+long long df3d_trajectory_work_bytes(int ncam, int T, int J, int block_frames);
+int df3d_trajectory_linearize(const double* P_host, const double* pts_px_dev, const double* X_dev, int ncam, int T, int J, double delta,
+                              double* H_dev, double* g_dev, double* weight_dev, double* err_dev, double* cost_dev, void* work_dev,
+                              long long work_bytes, void* stream);
+int df3d_trajectory_solve(const double* H_dev, const double* g_dev, const signed char* segment_dev, int T, int J, const double* lambda_host,
+                          double mu, int block_frames, double* d_dev, int* ok_dev, long long* ticks_dev, void* work_dev, long long work_bytes,
+                          void* stream);
+int df3d_triangulate_trajectory(const double* P_host, const double* pts_px_dev, const double* X0_dev, int ncam, int T, int J,
+                                const double* lambda_host, double delta, int max_gap, int block_frames, double* X_dev,
+                                signed char* status_dev, double* weight_dev, double* err_dev, int* iterations_dev, double* cost_dev,
+                                long long* counts_dev, void* work_dev, long long work_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];

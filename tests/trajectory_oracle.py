@@ -1,0 +1,327 @@
+"""Float64 numpy statement of the trajectory triangulation of DESIGN.md section 24 (df3d_trajectory_linearize, df3d_trajectory_solve,
+df3d_triangulate_trajectory).  TEST INFRASTRUCTURE ONLY.  Every function takes `dtype` (numpy.float64, or numpy.longdouble to measure
+what rounding alone moves).
+
+Per joint j (a chain), frames t = 0 .. T - 1, detections (row_px, col_px), ncam <= 8:
+    views       camera c is a view of (t, j) when both coordinates are non-zero (a6)
+    anchor      a frame with at least two views whose initial point X0[t, j] is finite
+    in a run    an anchor, or a frame between two anchors la < t < fa with fa - la - 1 <= max_gap
+    centre      c(t): t - 1, t and t + 1 are all in a run (two neighbouring frames in runs are always in the same one)
+    active      in a run of at least three frames: c(t - 1) or c(t) or c(t + 1).  The active frames are the unknowns; a maximal run of
+                them is a segment.  Every other frame keeps the bits of X0.
+    start       anchors X0; the other active frames A + (B - A) w, w = (t - la) / (fa - la): pose_repair_oracle.fill_gaps' operations
+    view terms  [u, v, w] = P_c [X; 1] (reproj_oracle.project); pu = u / w, pv = v / w, du = pu - col, dv = pv - row, q = du du + dv dv,
+                e = sqrt(q); a view is valid when w > 0 and e is finite (else: weight 0, cost 0, reported error +inf);
+                weight 1 for e <= delta, else delta / e; rho = q for e <= delta, else 2 delta e - delta delta;
+                Ju[k] = (P[0][k] - pu P[2][k]) / w, Jv[k] = (P[1][k] - pv P[2][k]) / w
+    frame sums  over the valid views in ascending camera order, from 0.0: H[a][b] += weight (Ju[a] Ju[b] + Jv[a] Jv[b]) (a <= b, stored
+                00 01 02 11 12 22), g[a] += weight (Ju[a] du + Jv[a] dv), cost += rho
+    smoothness  s(t) = (X[t - 1] - 2 X[t]) + X[t + 1] where c(t);  KX(t) = [c(t-1)] s(t-1) + [c(t)] (-2 s(t)) + [c(t+1)] s(t+1) from 0.0;
+                a frame's smoothness cost lambda (s0 s0 + s1 s1 + s2 s2) where c(t)
+    chain sum   of one value per frame: partial[k] = the values of the frames t = k, k + 256, ... added in ascending order from 0.0;
+                then partial[k] += partial[k + h] for h = 128, 64, ... 1; the sum is partial[0]
+    cost        E = chain sum over the active frames of (view cost + smoothness cost)
+    system      A d = b, A = H + lambda K + mu I on the active frames (K the Gram matrix of the second differences, times I3), the
+                identity on every other frame; b = -(g + lambda KX) on the active frames, 0 elsewhere.  Scalar unknown i = 3 t + a; A is
+                banded with half bandwidth 6 (8 with the fill of the factorisation).
+    iteration   mu = MU_INIT; E = cost(start).  A trial: linearise at X, solve, small = max |d| < STEP_TOL, E' = cost(X + d); it is
+                accepted when every pivot was > 0 and (small or E' <= E (1 + SLACK)): X += d, E = E', mu = max(mu / 10, MU_MIN), and the
+                chain has converged when small; else mu = 10 mu, and the chain has stalled when mu > MU_MAX.  A chain still running
+                after MAX_ITER trials is out of iterations.  One mu and one decision per chain.
+    status      0 not active; 1 anchor; 2 a filled frame with at least one view; 3 a filled frame without a view; 4 an active frame
+                of a chain that did not converge
+    weight      [ncam, T, J] the weights at the final X (0 for non-views, invalid views and frames that are not active); error likewise
+                (+inf for an invalid view); counts [J, 5]; iterations [J] the accepted trials; cost [J, 2] (start, final)
+"""
+import numpy as np
+
+from deepfly3d_amd import config
+
+RUNNING, CONVERGED, OUT_OF_ITERATIONS, STALLED = -2, 0, 1, 2
+LANES = 256
+
+
+def views(px):
+    px = np.asarray(px)
+    return (px[..., 0] != 0.0) & (px[..., 1] != 0.0)
+
+
+def anchors(px, X0):
+    return (views(px).sum(axis=0) >= 2) & np.isfinite(np.asarray(X0, np.float64)).all(axis=-1)
+
+
+def _neighbours(anchor):
+    """(la, fa) [T, J]: the last anchor at or before t (-1: none), the first at or after t (T: none)."""
+    T = anchor.shape[0]
+    t = np.arange(T)[:, None]
+    la = np.maximum.accumulate(np.where(anchor, t, -1), axis=0)
+    fa = np.minimum.accumulate(np.where(anchor, t, T)[::-1], axis=0)[::-1]
+    return la, fa
+
+
+def _shift(a, k):
+    """a[t + k] along axis 0, False outside."""
+    out = np.zeros_like(a)
+    if k > 0:
+        out[:-k or None] = a[k:]
+    elif k < 0:
+        out[-k:] = a[:k]
+    else:
+        out[:] = a
+    return out
+
+
+def centres(run):
+    return _shift(run, -1) & run & _shift(run, 1)
+
+
+def active_frames(anchor, max_gap):
+    """(active, centre) [T, J] bool."""
+    anchor = np.asarray(anchor, bool)
+    T = anchor.shape[0]
+    if T == 0:
+        return anchor.copy(), anchor.copy()
+    la, fa = _neighbours(anchor)
+    run = anchor | ((la >= 0) & (fa < T) & (fa - la - 1 <= max_gap))
+    c = centres(run)
+    return run & (_shift(c, -1) | c | _shift(c, 1)), c
+
+
+def segments_loop(anchor, max_gap):
+    """The segment rule by a walk along one chain: [(first, last)] of the segments of at least three frames."""
+    at = [int(t) for t in np.nonzero(anchor)[0]]
+    out, start = [], None
+    for k, t in enumerate(at):
+        if start is None:
+            start = t
+        if k + 1 == len(at) or at[k + 1] - t - 1 > max_gap:
+            if t - start + 1 >= 3:
+                out.append((start, t))
+            start = None
+    return out
+
+
+def start_points(X0, anchor, active, dtype=np.float64):
+    X0 = np.asarray(X0, np.float64)
+    T = X0.shape[0]
+    X = X0.astype(dtype)
+    tt, jj = np.nonzero(active & ~anchor)
+    if tt.size:
+        la, fa = _neighbours(anchor)
+        a, b = la[tt, jj], fa[tt, jj]
+        A, B = X[a, jj], X[b, jj]
+        w = (tt - a).astype(dtype) / (b - a).astype(dtype)
+        X[tt, jj] = A + (B - A) * w[:, None]
+    return X
+
+
+def linearize(P, px, X, delta, dtype=np.float64):
+    """(H [T, J, 6], g [T, J, 3], weight [ncam, T, J], err [ncam, T, J], cost [T, J]) at X [T, J, 3]."""
+    P, px, X = np.asarray(P, dtype), np.asarray(px, dtype), np.asarray(X, dtype)
+    ncam, T, J, _ = px.shape
+    delta = dtype(delta)
+    H, g, cost = np.zeros((T, J, 6), dtype), np.zeros((T, J, 3), dtype), np.zeros((T, J), dtype)
+    weight, err = np.zeros((ncam, T, J), dtype), np.zeros((ncam, T, J), dtype)
+    vw = views(px)
+    x0, x1, x2 = X[..., 0], X[..., 1], X[..., 2]
+    with np.errstate(all="ignore"):
+        for c in range(ncam):
+            Pc = P[c]
+            u = Pc[0, 0] * x0 + Pc[0, 1] * x1 + Pc[0, 2] * x2 + Pc[0, 3]
+            v = Pc[1, 0] * x0 + Pc[1, 1] * x1 + Pc[1, 2] * x2 + Pc[1, 3]
+            w = Pc[2, 0] * x0 + Pc[2, 1] * x1 + Pc[2, 2] * x2 + Pc[2, 3]
+            pu, pv = u / w, v / w
+            du, dv = pu - px[c, ..., 1], pv - px[c, ..., 0]
+            q = du * du + dv * dv
+            e = np.sqrt(q)
+            valid = vw[c] & (w > 0.0) & np.isfinite(e)
+            inl = e <= delta
+            wt = np.where(inl, dtype(1.0), delta / e)
+            rho = np.where(inl, q, dtype(2.0) * delta * e - delta * delta)
+            Ju = [(Pc[0, k] - pu * Pc[2, k]) / w for k in range(3)]
+            Jv = [(Pc[1, k] - pv * Pc[2, k]) / w for k in range(3)]
+            n = 0
+            for a in range(3):
+                for b in range(a, 3):
+                    H[..., n] = np.where(valid, H[..., n] + wt * (Ju[a] * Ju[b] + Jv[a] * Jv[b]), H[..., n])
+                    n += 1
+                g[..., a] = np.where(valid, g[..., a] + wt * (Ju[a] * du + Jv[a] * dv), g[..., a])
+            cost = np.where(valid, cost + rho, cost)
+            weight[c] = np.where(valid, wt, 0.0)
+            err[c] = np.where(vw[c], np.where(valid, e, np.inf), 0.0)
+    return H, g, weight, err, cost
+
+
+def chain_sum(f):
+    """[J] of f [T, J] in the model's fixed order."""
+    f = np.asarray(f)
+    T, J = f.shape
+    part = np.zeros((LANES, J), f.dtype)
+    for r in range(0, T, LANES):
+        rows = f[r : r + LANES]
+        part[: len(rows)] = part[: len(rows)] + rows
+    h = LANES // 2
+    while h:
+        part[:h] = part[:h] + part[h : 2 * h]
+        h //= 2
+    return part[0].copy()
+
+
+def smoothness(X, c):
+    """(s [T, J, 3] (0 where c is false), KX [T, J, 3])."""
+    T = X.shape[0]
+    s = np.zeros_like(X)
+    if T >= 3:
+        s[1:-1] = (X[:-2] - X.dtype.type(2.0) * X[1:-1]) + X[2:]
+    s = np.where(c[..., None], s, 0.0)          # -> an absent term adds 0.0, which changes no bit of a sum that starts at 0.0
+    before, after = np.zeros_like(s), np.zeros_like(s)
+    before[1:], after[:-1] = s[:-1], s[1:]
+    kx = (before + X.dtype.type(-2.0) * s) + after
+    return s, kx
+
+
+def frame_cost(view_cost, s, c, lam, active):
+    sm = np.where(c, lam[None, :] * (s[..., 0] * s[..., 0] + s[..., 1] * s[..., 1] + s[..., 2] * s[..., 2]), 0.0)
+    return np.where(active, view_cost + sm, 0.0)
+
+
+def system(H, rhs_grad, c, active, lam, mu):
+    """(AB [J, 3 T, 9] the upper band of A, b [J, 3 T]) of H [T, J, 6] and the whole gradient rhs_grad [T, J, 3]; lam, mu [J]."""
+    T, J, _ = H.shape
+    dt = H.dtype
+    cf = c.astype(dt)
+    cb, ca = np.zeros_like(cf), np.zeros_like(cf)
+    cb[1:], ca[:-1] = cf[:-1], cf[1:]
+    kd = cb + 4.0 * cf + ca
+    k1 = -2.0 * (cf + ca)
+    k2 = ca
+    AB = np.zeros((J, T, 3, 9), dt)
+    for a, (d, o1, o2) in enumerate(((0, 1, 2), (3, 4, None), (5, None, None))):
+        AB[:, :, a, 0] = np.where(active, (H[..., d] + lam[None] * kd) + mu[None], 1.0).T
+        if o1 is not None:
+            AB[:, :, a, 1] = np.where(active, H[..., o1], 0.0).T
+        if o2 is not None:
+            AB[:, :, a, 2] = np.where(active, H[..., o2], 0.0).T
+        AB[:, :, a, 3] = (lam[None] * k1).T
+        AB[:, :, a, 6] = (lam[None] * k2).T
+    b = np.where(active[..., None], -rhs_grad, 0.0).transpose(1, 0, 2).reshape(J, 3 * T)
+    return AB.reshape(J, 3 * T, 9), b
+
+
+def dense(AB):
+    """[J, n, n] symmetric from the upper band."""
+    J, n, w = AB.shape
+    A = np.zeros((J, n, n), AB.dtype)
+    for m in range(w):
+        idx = np.arange(n - m)
+        A[:, idx, idx + m] = AB[:, : n - m, m]
+        A[:, idx + m, idx] = AB[:, : n - m, m]
+    return A
+
+
+_PAIRS = [(m, q) for m in range(1, 9) for q in range(m, 9)]
+_PAIR_M, _PAIR_Q = np.array([m for m, _ in _PAIRS]), np.array([q for _, q in _PAIRS])
+_PAIR_AT = 8 * _PAIR_M + _PAIR_Q          # entry (q - m) of row i + m lies 8 m + q doubles behind the start of row i
+
+
+def banded_solve(AB, b):
+    """(x [J, n], ok [J]): A x = b by the banded L D L^T in ascending order, every chain at once; ok: every pivot > 0.  Row i + m loses
+    (U[i, m] / U[i, 0]) U[i, q] from its entry q - m, 1 <= m <= q <= 8, and the right-hand side likewise; eight identity rows are
+    appended so that the last rows need no special case."""
+    J, n, w = AB.shape
+    assert w == 9
+    U = np.zeros((J, n + 8, 9), AB.dtype)
+    U[:, :n], U[:, n:, 0] = AB, 1.0
+    z = np.zeros((J, n + 8), AB.dtype)
+    z[:, :n] = b
+    F = U.reshape(J, -1)
+    ok = np.ones(J, bool)
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            u = U[:, i].copy()
+            ok &= u[:, 0] > 0.0
+            l = u / u[:, :1]
+            F[:, 9 * i + _PAIR_AT] -= l[:, _PAIR_M] * u[:, _PAIR_Q]
+            z[:, i + 1 : i + 9] -= l[:, 1:] * z[:, i : i + 1]
+        x = np.zeros_like(z)
+        for i in range(n - 1, -1, -1):
+            x[:, i] = (z[:, i] - (U[:, i, 1:] * x[:, i + 1 : i + 9]).sum(axis=1)) / U[:, i, 0]
+    return x[:, :n], ok
+
+
+def backward_error(AB, b, x, other=None):
+    """max |A x - b| / (|A|_inf |x|_inf + |b|_inf) per chain, in numpy.longdouble.  With `other`: max |A (x - other)| over the same
+    denominator: how far two answers to the same system are apart, in the backward error's own measure."""
+    U, x, b = AB.astype(np.longdouble), x.astype(np.longdouble), b.astype(np.longdouble)
+    if other is not None:
+        return _difference(U, b, x, other.astype(np.longdouble))
+    Ax, rows = _band_times(U, x)
+    r = np.abs(Ax - b).max(axis=1)
+    return (r / (rows.max(axis=1) * np.abs(x).max(axis=1) + np.abs(b).max(axis=1))).astype(np.float64)
+
+
+def _band_times(U, x):
+    n, w = U.shape[1], U.shape[2]
+    Ax, rows = U[:, :, 0] * x, np.abs(U[:, :, 0])
+    for m in range(1, min(w, n)):
+        Ax[:, : n - m] += U[:, : n - m, m] * x[:, m:]
+        Ax[:, m:] += U[:, : n - m, m] * x[:, : n - m]
+        rows[:, : n - m] += np.abs(U[:, : n - m, m])
+        rows[:, m:] += np.abs(U[:, : n - m, m])
+    return Ax, rows
+
+
+def _difference(U, b, x, y):
+    Ad, rows = _band_times(U, x - y)
+    return (np.abs(Ad).max(axis=1) / (rows.max(axis=1) * np.abs(x).max(axis=1) + np.abs(b).max(axis=1))).astype(np.float64)
+
+
+def total_cost(P, px, X, c, active, lam, delta, dtype):
+    view_cost = linearize(P, px, X, delta, dtype)[4]
+    return chain_sum(frame_cost(view_cost, smoothness(X, c)[0], c, lam, active))
+
+
+def fit(P, px, X0, lam, delta, max_gap, dtype=np.float64, max_iter=None):
+    """The whole model: a dict of X, status, weight, error, iterations, cost, counts, and `fit_status` [J] (CONVERGED, ...)."""
+    px = np.asarray(px, np.float64)
+    ncam, T, J, _ = px.shape
+    lam = np.broadcast_to(np.asarray(lam, dtype), (J,)).astype(dtype)
+    max_iter = config.TRAJECTORY_MAX_ITER if max_iter is None else max_iter
+    anchor = anchors(px, X0)
+    active, c = active_frames(anchor, max_gap)
+    X = start_points(X0, anchor, active, dtype)
+    vw = views(px)
+    nviews = vw.sum(axis=0)
+    E = total_cost(P, px, X, c, active, lam, delta, dtype) if T else np.zeros(J, dtype)
+    E0 = E.copy()
+    mu = np.full(J, config.TRAJECTORY_MU_INIT, dtype)
+    state = np.where(active.any(axis=0), RUNNING, CONVERGED).astype(np.int64) if T else np.zeros(J, np.int64)
+    iterations, trials = np.zeros(J, np.int32), 0
+    while (state == RUNNING).any():
+        k = np.nonzero(state == RUNNING)[0]            # the chains still running: every chain is independent of the others
+        pk, Xk, ck, ak, lk = px[:, :, k], X[:, k], c[:, k], active[:, k], lam[k]
+        H, g, _, _, _ = linearize(P, pk, Xk, delta, dtype)
+        AB, b = system(H, g + lk[None, :, None] * smoothness(Xk, ck)[1], ck, ak, lk, mu[k])
+        d, ok = banded_solve(AB, b)
+        d = d.reshape(len(k), T, 3).transpose(1, 0, 2)
+        trials += 1
+        with np.errstate(all="ignore"):
+            small = (np.abs(d) < config.TRAJECTORY_STEP_TOL).all(axis=(0, 2))   # (a NaN is not small)
+            Xn = Xk + d
+            En = total_cost(P, pk, Xn, ck, ak, lk, delta, dtype)
+            accept = ok & (small | (En <= E[k] * dtype(1.0 + config.TRAJECTORY_SLACK)))
+        X[:, k[accept]] = Xn[:, accept]
+        E[k[accept]] = En[accept]
+        iterations[k[accept]] += 1
+        mu[k] = np.where(accept, np.maximum(mu[k] / dtype(10.0), dtype(config.TRAJECTORY_MU_MIN)), dtype(10.0) * mu[k])
+        state[k[accept & small]] = CONVERGED
+        state[k[~accept & (mu[k] > config.TRAJECTORY_MU_MAX)]] = STALLED
+        if trials == max_iter:
+            state[state == RUNNING] = OUT_OF_ITERATIONS
+    _, _, weight, err, _ = linearize(P, px, X, delta, dtype)
+    weight, err = np.where(active[None], weight, 0.0), np.where(active[None], err, 0.0)
+    status = np.where(active, np.where(anchor, 1, np.where(nviews >= 1, 2, 3)), 0)
+    status = np.where(active & (state != CONVERGED)[None], 4, status).astype(np.int8)
+    counts = np.stack([(status == k).sum(axis=0) for k in range(5)], axis=1).astype(np.int64).reshape(J, 5)
+    return dict(X=X, status=status, weight=weight, error=err, iterations=iterations, cost=np.stack([E0, E], axis=1), counts=counts,
+                fit_status=state, active=active, centre=c, anchor=anchor)
