@@ -104,32 +104,7 @@ def test_banded_solve_meets_the_backward_error_bar(native_lib, cuda, J, lam):
 
 
 # ---------------------------------------------------------------------------------------------------------------------- the fit
-def _reference(P, px, X0):
-    """The oracle in float64 and in numpy.longdouble from the device's own start, how far rounding alone moves it, and the bar on X."""
-    lam = config.TRAJECTORY_LAMBDA[: px.shape[2]]
-    r64 = to.fit(P, px, X0, lam, config.TRAJECTORY_HUBER, config.REPAIR_MAX_GAP)
-    r80 = to.fit(P, px, X0, lam, config.TRAJECTORY_HUBER, config.REPAIR_MAX_GAP, dtype=np.longdouble)
-    moved = float(np.abs(r64["X"] - r80["X"].astype(np.float64)).max())
-    return r64, r80, moved, max(16.0 * moved, config.TRAJECTORY_STEP_TOL)
-
-
-def _error_and_cost_bars(P, px, r64, lam, delta, bar):
-    """What a point within `bar` (mm, per coordinate) of the oracle's may change, derived and not measured:
-    a view's error e = |proj(X) - px| moves by at most |J_c|_2 |dX|_2 <= L sqrt(3) bar, L^2 = the largest trace of a frame's sum of
-    J^T J at the oracle's point (it bounds every view's |J_c|_2^2 there; doubled for J's own change over `bar`), plus 16 eps e for the
-    rounding of the projection; a view's Huber term has slope at most 2 delta, a triple's |s|^2 moves by at most 2 |s|_2 |ds|_2 +
-    |ds|_2^2 with |ds|_2 <= 4 sqrt(3) bar; the chain sum of at most T ncam + T terms rounds within 1e-12 of the cost.
-    Returns (error bar [ncam, T, J], cost bar [J])."""
-    H = to.linearize(P, px, r64["X"], np.inf)[0]
-    L = float(np.sqrt(np.nanmax(H[..., 0] + H[..., 3] + H[..., 5])))
-    moved = 2.0 * np.sqrt(3.0) * L * bar
-    with np.errstate(invalid="ignore"):
-        error_bar = moved + 16.0 * EPS * np.where(np.isfinite(r64["error"]), r64["error"], 0.0)
-    views = (to.views(px) & r64["active"][None]).sum(axis=(0, 1))
-    s = np.linalg.norm(to.smoothness(r64["X"], r64["centre"])[0], axis=-1)
-    ds = 4.0 * np.sqrt(3.0) * bar
-    cost_bar = 2.0 * delta * views * moved + lam * (2.0 * s * ds + ds * ds).sum(axis=0) + 1e-12 * r64["cost"][:, 1]
-    return error_bar, cost_bar
+_reference, _error_and_cost_bars = tc.reference, tc.error_and_cost_bars   # shared with tests/test_gpu_trajectory_sweep.py
 
 
 def _same_bits(a, b):

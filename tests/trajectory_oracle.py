@@ -281,8 +281,12 @@ def total_cost(P, px, X, c, active, lam, delta, dtype):
     return chain_sum(frame_cost(view_cost, smoothness(X, c)[0], c, lam, active))
 
 
-def fit(P, px, X0, lam, delta, max_gap, dtype=np.float64, max_iter=None):
-    """The whole model: a dict of X, status, weight, error, iterations, cost, counts, and `fit_status` [J] (CONVERGED, ...)."""
+def fit(P, px, X0, lam, delta, max_gap, dtype=np.float64, max_iter=None, solve=None, trace=None):
+    """The whole model: a dict of X, status, weight, error, iterations, cost, counts, and `fit_status` [J] (CONVERGED, ...).
+    `solve` (AB, b) -> (x, ok) replaces banded_solve; `trace`, a list, receives one dict per trial: the chains that ran it (`chains`),
+    and of each `ok`, `small`, `accept`, the cost before (`E`) and of the trial (`En`) and the step's largest |d| (`step`).  Neither
+    changes anything when absent."""
+    solve = banded_solve if solve is None else solve
     px = np.asarray(px, np.float64)
     ncam, T, J, _ = px.shape
     lam = np.broadcast_to(np.asarray(lam, dtype), (J,)).astype(dtype)
@@ -302,7 +306,7 @@ def fit(P, px, X0, lam, delta, max_gap, dtype=np.float64, max_iter=None):
         pk, Xk, ck, ak, lk = px[:, :, k], X[:, k], c[:, k], active[:, k], lam[k]
         H, g, _, _, _ = linearize(P, pk, Xk, delta, dtype)
         AB, b = system(H, g + lk[None, :, None] * smoothness(Xk, ck)[1], ck, ak, lk, mu[k])
-        d, ok = banded_solve(AB, b)
+        d, ok = solve(AB, b)
         d = d.reshape(len(k), T, 3).transpose(1, 0, 2)
         trials += 1
         with np.errstate(all="ignore"):
@@ -310,6 +314,8 @@ def fit(P, px, X0, lam, delta, max_gap, dtype=np.float64, max_iter=None):
             Xn = Xk + d
             En = total_cost(P, pk, Xn, ck, ak, lk, delta, dtype)
             accept = ok & (small | (En <= E[k] * dtype(1.0 + config.TRAJECTORY_SLACK)))
+            if trace is not None:
+                trace.append(dict(chains=k, ok=ok.copy(), small=small, accept=accept, E=E[k].copy(), En=En, step=np.abs(d).max(axis=(0, 2))))
         X[:, k[accept]] = Xn[:, accept]
         E[k[accept]] = En[accept]
         iterations[k[accept]] += 1
