@@ -1,11 +1,17 @@
 """Thin host wrappers over the C ABI for the non-network kernels: arg-max and peaks, re-layout, triangulation, Procrustes and the
-video pose, and what DESIGN.md sections 9-19 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
+video pose, and what DESIGN.md sections 9-24 add -- pictorial structures, reprojection errors, 2-D smoothing, the heat-map
 overlay, joint angles, the leg fit, wavelet spectrograms, behaviour maps, their segmentation, the gait analysis, the pose repair,
-the treadmill ball (section 21), the tracking of the detections through time (section 22), the consensus triangulation over camera
-subsets (section 23) and the trajectory triangulation (section 24).
+the treadmill ball, the tracking of the detections through time, the consensus triangulation over camera subsets and the trajectory
+triangulation.
 
 Inputs/outputs are torch CUDA tensors (device memory + stream plumbing only); every computation is a
 libdf3d_hip.so kernel.  No CPU fallback: a missing library or GPU raises `_native.NativeLibraryError`.
+
+Every rule that more than one family applies to its arguments is written once, in the block below the imports: the tensor checks
+(`_need`, strict, and `_need_tensor`, which returns the contiguous tensor that the caller then uses), the camera matrices, the
+inputs of the triangulations, the `body_frame` argument, the workspace query, the integer / number / per-joint parameters, and
+`_call`, the call path that turns the library's DF3D_EINVAL into a ValueError.  A new family takes its checks from there and keeps
+only its own refusal texts.
 """
 import collections
 import ctypes
@@ -40,6 +46,122 @@ def _on_tensor_device(fn):
 def _need(t, dtype, name):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
         raise ValueError(f"{name} must be a contiguous {dtype} CUDA tensor")
+
+
+def _need_tensor(t, dtype, tail, name):
+    """`t`, contiguous: a `dtype` CUDA tensor of shape [T, *tail] and any strides.  The caller goes on with what this returns."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 1 + len(tail) and tuple(t.shape[1:]) == tuple(tail)):
+        raise ValueError(f"{name} must be a {dtype} CUDA tensor of shape [{', '.join(['T', *(str(n) for n in tail)])}]")
+    return t.contiguous()
+
+
+def _camera_matrices(P, ncam):
+    """P [ncam, 3, 4] (numpy or tensor) as a contiguous float64 host array."""
+    Ph = np.ascontiguousarray(P.detach().cpu().numpy() if isinstance(P, torch.Tensor) else P, dtype=np.float64)
+    if Ph.shape != (ncam, 3, 4):
+        raise ValueError("P must be [ncam, 3, 4]")
+    return Ph
+
+
+def _need_points2d_px(points2d_px, bounded=False):
+    """(ncam, T, J) of points2d_px [ncam, T, J, 2], contiguous float64 cuda; `bounded`: within the 8 cameras and 64 joints of the consensus and trajectory kernels."""
+    _need(points2d_px, torch.float64, "points2d_px")
+    if points2d_px.dim() != 4 or points2d_px.shape[3] != 2:
+        raise ValueError("points2d_px must be [ncam, T, J, 2]")
+    ncam, T, J, _ = points2d_px.shape
+    if bounded and not (1 <= ncam <= 8 and 1 <= J <= 64):
+        raise ValueError("points2d_px must hold 1 to 8 cameras and 1 to 64 joints")
+    return ncam, T, J
+
+
+def _need_X(X, points2d_px):
+    """An explicit X [T, J, 3], contiguous float64, on the frames, joints and device of points2d_px [ncam, T, J, 2]."""
+    _need(X, torch.float64, "X")
+    if tuple(X.shape) != (*points2d_px.shape[1:3], 3) or X.device != points2d_px.device:
+        raise ValueError("X must be [T, J, 3] on the device of points2d_px")
+
+
+_BODY_FRAME_TEXT = ('body_frame must be "recording", "per_frame" or a [3, 3] / [T, 3, 3] array',
+                    "an explicit body_frame must be [3, 3] or [T, 3, 3] with T = {T}")
+
+
+def _body_frames(value, T, dev, per_frame_allowed=True, text=_BODY_FRAME_TEXT):
+    """The `body_frame` argument of a family: None for "recording" and, where allowed, "per_frame" -- `_fill_body_frames` computes
+    those once the caller knows that there are frames --, else the explicit [3, 3] or, where allowed, [T, 3, 3] array or tensor as
+    contiguous float64 frames [1 or T, 3, 3] on `dev`.  `text`: the refusals of the string and of the shape."""
+    if isinstance(value, str):
+        if value != "recording" and not (per_frame_allowed and value == "per_frame"):
+            raise ValueError(text[0])
+        return None
+    frames = value if isinstance(value, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(value, dtype=np.float64))
+    if tuple(frames.shape) not in ((3, 3), (1, 3, 3)) + (((T, 3, 3),) if per_frame_allowed else ()):
+        raise ValueError(text[1].format(T=T))
+    return frames.to(device=dev, dtype=torch.float64).reshape(-1, 3, 3).contiguous()
+
+
+def _fill_body_frames(frames, value, points3d):
+    """`frames` of _body_frames, with None replaced by the frames that `value` names, of points3d [T >= 1, 38, 3]."""
+    if frames is not None:
+        return frames
+    return recording_frame(points3d) if value == "recording" else body_frame(points3d)
+
+
+def _workspace(entry_name, *dims, device, refusal=None, least=0):
+    """(work, need): the `need` bytes that the library's `entry_name`(*dims) asks for, as a uint8 tensor of at least `least` bytes on
+    `device` (None: no tensor, the size alone).  A size <= 0 is the entry's refusal of `dims`: ValueError with
+    `refusal`.format(*dims), by default the library's own message."""
+    lib = _native.load()
+    need = getattr(lib, entry_name)(*dims)
+    if need <= 0:
+        raise ValueError(lib.df3d_last_error().decode() if refusal is None else refusal.format(*dims))
+    return (None if device is None else torch.empty((max(need, least),), dtype=torch.uint8, device=device)), need
+
+
+def _integer(v, lo, hi, name):
+    """int(v) of a Python or numpy integer (no bool, no float) in [lo, hi]."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (it is {v!r})")
+    return int(v)
+
+
+def _number(v, name, positive=False):
+    """float(v) of a Python or numpy real number (no bool, no string); `positive`: a finite one > 0."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or (positive and not (np.isfinite(v) and v > 0)):
+        raise ValueError(f"{name} must be {'a finite number > 0' if positive else 'a number'} (it is {v!r})")
+    return float(v)
+
+
+def _per_joint(value, default, name, finite=False):
+    """A float64 array of one value or of one per joint from `value` (a number or a sequence of numbers; None: `default`), every
+    one >= 0 and not NaN -- `finite`: nor +inf.  `_broadcast_per_joint` fits it to the J of the data."""
+    if value is None:
+        a = np.array(default, dtype=np.float64)
+    else:
+        if isinstance(value, (bool, str)) or (isinstance(value, (list, tuple, np.ndarray)) and np.asarray(value).dtype.kind not in "fiu"):
+            raise ValueError(f"{name} must be a number or one number per joint (it is {value!r})")
+        try:
+            a = np.array(value, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number or one number per joint (it is {value!r})") from None
+    if a.size == 0 or not bool(np.all((a >= 0.0) & np.isfinite(a) if finite else a >= 0.0)):
+        raise ValueError(f"{name} must be >= 0 and " + ("finite" if finite else "not NaN (+inf is accepted)"))
+    return a
+
+
+def _broadcast_per_joint(a, J, name, config_name=None):
+    """[J] contiguous float64 of `a` [1] or [J]; `config_name`: the constant of config that `a` is, when it is the default."""
+    if a.shape not in ((1,), (J,)):
+        raise ValueError(f"{name} must hold one value, or one per joint ({J})" + (f" (config.{config_name} is for 38)" if config_name else ""))
+    return np.ascontiguousarray(np.broadcast_to(a, (J,)))
+
+
+def _call(name, *args):
+    """One entry of the library; its DF3D_EINVAL is the caller's mistake and becomes a ValueError with the library's message."""
+    lib = _native.load()
+    rc = getattr(lib, name)(*args)
+    if rc == _native.DF3D_EINVAL:
+        raise ValueError(lib.df3d_last_error().decode())
+    _native.check(rc, name)
 
 
 @_on_tensor_device
@@ -84,13 +206,8 @@ def triangulate(P, points2d_px):
     """P [ncam, 3, 4] float64 (numpy or tensor), points2d_px [ncam, T, J, 2] float64 cuda (row_px, col_px)
     -> X [T, J, 3] float64 cuda; zeros where fewer than two cameras see the joint."""
     lib = _native.load()
-    _need(points2d_px, torch.float64, "points2d_px")
-    ncam, T, J, two = points2d_px.shape
-    if two != 2:
-        raise ValueError("points2d_px must be [ncam, T, J, 2]")
-    Ph = np.ascontiguousarray(P.detach().cpu().numpy() if isinstance(P, torch.Tensor) else P, dtype=np.float64)
-    if Ph.shape != (ncam, 3, 4):
-        raise ValueError("P must be [ncam, 3, 4]")
+    ncam, T, J = _need_points2d_px(points2d_px)
+    Ph = _camera_matrices(P, ncam)
     X = torch.empty((T, J, 3), dtype=torch.float64, device=points2d_px.device)
     _native.check(
         lib.df3d_triangulate(Ph.ctypes.data_as(ctypes.c_void_p), points2d_px.data_ptr(), ncam, T, J, X.data_ptr(), _stream(points2d_px)),
@@ -198,12 +315,7 @@ def _pictorial_inputs(P, camera_ordering, points2d, peak_count, peak_pts, peak_v
     if any(t.device != points2d.device for t in (peak_count, peak_pts) + ((peak_val,) if peak_val is not None else ())):
         raise ValueError("points2d and the peaks must be on one device")
     order = (ctypes.c_int * 7)(*[int(c) for c in camera_ordering])
-    Ph = None
-    if P is not None:
-        Ph = np.ascontiguousarray(P.detach().cpu().numpy() if isinstance(P, torch.Tensor) else P, dtype=np.float64)
-        if Ph.shape != (7, 3, 4):
-            raise ValueError("P must be [7, 3, 4]")
-    return T, k, order, Ph
+    return T, k, order, None if P is None else _camera_matrices(P, 7)
 
 
 @_on_tensor_device
@@ -269,8 +381,8 @@ def arg_max_points3d(P, points2d, image_shape):
     CameraNetwork.triangulate sees them) -- the correction's proposal 0, bit for bit what the uncorrected run triangulates."""
     lib = _native.load()
     _need(points2d, torch.float64, "points2d")
-    Ph = np.ascontiguousarray(P.detach().cpu().numpy() if isinstance(P, torch.Tensor) else P, dtype=np.float64)
     ncam, T, J, _ = points2d.shape
+    Ph = _camera_matrices(P, ncam)
     X = torch.empty((T, J, 3), dtype=torch.float64, device=points2d.device)
     _native.check(lib.df3d_triangulate_scaled(Ph.ctypes.data_as(ctypes.c_void_p), points2d.data_ptr(), float(image_shape[1]), float(image_shape[0]), ncam, T, J,
                                               X.data_ptr(), _stream(points2d)), "df3d_triangulate_scaled")
@@ -307,27 +419,19 @@ def pictorial_correct(P, camera_ordering, points2d, peak_count, peak_pts, peak_v
 def reprojection_errors(P, points2d_px, X=None, thresholds=None, frames=None):
     """Per-joint reprojection errors and suspect-joint masks, df3d_reproj_errors.  P [ncam, 3, 4] float64
     (numpy or tensor, pixels); points2d_px [ncam, T, J, 2] float64 cuda (row_px, col_px); X [T, J, 3] float64 cuda on the same
-    frames, triangulate() of the selected detections when None; thresholds [J] pixels (default config.REPROJ_THR, J = 38);
+    frames, triangulate() of the selected detections when None; thresholds [J] or [1] pixels (default config.REPROJ_THR, J = 38);
     frames: optional frame ids, gathered on the device from points2d_px (and X), the outputs in their order.
     Returns (err [ncam, nf, J], jmax [nf, J] float64, mask [nf] int64: bit j set when jmax > thresholds[j]) on the device."""
     from .config import REPROJ_THR
 
     lib = _native.load()
-    _need(points2d_px, torch.float64, "points2d_px")
-    if points2d_px.dim() != 4 or points2d_px.shape[3] != 2:
-        raise ValueError("points2d_px must be [ncam, T, J, 2]")
-    ncam, T, J, _ = points2d_px.shape
+    ncam, T, J = _need_points2d_px(points2d_px)
     dev = points2d_px.device
-    Ph = np.ascontiguousarray(P.detach().cpu().numpy() if isinstance(P, torch.Tensor) else P, dtype=np.float64)
-    if Ph.shape != (ncam, 3, 4):
-        raise ValueError("P must be [ncam, 3, 4]")
+    Ph = _camera_matrices(P, ncam)
     thr = np.ascontiguousarray(REPROJ_THR if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
-    if thr.shape != (J,):
-        raise ValueError(f"thresholds must hold one value per joint ({J})" + (" (config.REPROJ_THR is for 38)" if thresholds is None else ""))
+    thr = _broadcast_per_joint(thr, J, "thresholds", "REPROJ_THR" if thresholds is None else None)
     if X is not None:
-        _need(X, torch.float64, "X")
-        if tuple(X.shape) != (T, J, 3) or X.device != dev:
-            raise ValueError("X must be [T, J, 3] on the device of points2d_px")
+        _need_X(X, points2d_px)
     px = points2d_px
     if frames is not None:
         idx = torch.as_tensor(np.asarray(frames, dtype=np.int64).reshape(-1), device=dev)
@@ -351,25 +455,16 @@ def reprojection_errors(P, points2d_px, X=None, thresholds=None, frames=None):
     return err, jmax, mask
 
 
-def _need_pose(points3d):
-    _need(points3d, torch.float64, "points3d")
-    if points3d.dim() != 3 or tuple(points3d.shape[1:]) != (38, 3):
-        raise ValueError("points3d must be [T, 38, 3]")
-
-
 @_on_tensor_device
 def body_frame(points3d):
     """points3d [n, 38, 3] float64 cuda -> [n, 3, 3]: rows ex, ey, ez of every pose's own body frame from its six body-coxa
     joints (df3d_body_frame); all NaN where one of them is missing or the six are degenerate."""
     lib = _native.load()
-    _need_pose(points3d)
+    points3d = _need_tensor(points3d, torch.float64, (38, 3), "points3d")
     n = points3d.shape[0]
     out = torch.empty((n, 3, 3), dtype=torch.float64, device=points3d.device)
     _native.check(lib.df3d_body_frame(points3d.data_ptr(), n, out.data_ptr(), _stream(points3d)), "df3d_body_frame")
     return out
-
-
-_pose_frames = body_frame   # joint_angles' `body_frame` argument hides the function there
 
 
 def _coxa_medians(points3d):
@@ -377,7 +472,7 @@ def _coxa_medians(points3d):
     points3d [T >= 1, 38, 3] as they stand)."""
     from .config import leg_joints
 
-    _need_pose(points3d)
+    points3d = _need_tensor(points3d, torch.float64, (38, 3), "points3d")
     coxae = torch.tensor([leg_joints(leg)[0] for leg in range(6)], device=points3d.device)
     cols = points3d.index_select(1, coxae).reshape(points3d.shape[0], 18).t().contiguous()   # the median wants contiguous columns
     return coxae, column_median(cols).reshape(6, 3)
@@ -400,23 +495,14 @@ def joint_angles(points3d, body_frame="recording"):
     used as given.  Returns (angles [T, 6, 8] radians in the order of config.LEG_ANGLE_NAMES, lengths [T, 6, 4]) on the device;
     NaN where a joint is missing or a direction is undefined."""
     lib = _native.load()
-    _need_pose(points3d)
+    points3d = _need_tensor(points3d, torch.float64, (38, 3), "points3d")
     T, dev = points3d.shape[0], points3d.device
     angles = torch.empty((T, 6, 8), dtype=torch.float64, device=dev)
     lengths = torch.empty((T, 6, 4), dtype=torch.float64, device=dev)
-    if isinstance(body_frame, str):
-        if body_frame not in ("recording", "per_frame"):
-            raise ValueError('body_frame must be "recording", "per_frame" or a [3, 3] / [T, 3, 3] array')
-        frames = None
-    else:
-        frames = body_frame if isinstance(body_frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(body_frame, dtype=np.float64))
-        if tuple(frames.shape) not in ((3, 3), (1, 3, 3), (T, 3, 3)):
-            raise ValueError(f"an explicit body_frame must be [3, 3] or [T, 3, 3] with T = {T}")
-        frames = frames.to(device=dev, dtype=torch.float64).reshape(-1, 3, 3).contiguous()
+    frames = _body_frames(body_frame, T, dev)
     if T == 0:   # no medians to take, nothing to launch
         return angles, lengths
-    if frames is None:
-        frames = recording_frame(points3d) if body_frame == "recording" else _pose_frames(points3d)
+    frames = _fill_body_frames(frames, body_frame, points3d)
     _native.check(lib.df3d_joint_angles(points3d.data_ptr(), T, frames.data_ptr(), frames.shape[0], angles.data_ptr(), lengths.data_ptr(),
                                         _stream(points3d)), "df3d_joint_angles")
     return angles, lengths
@@ -430,7 +516,7 @@ def segment_length_medians(points3d):
     column_median over the column's finite entries.  A segment without a finite length in any frame raises ValueError."""
     from .config import LEG_NAMES
 
-    _need_pose(points3d)
+    points3d = _need_tensor(points3d, torch.float64, (38, 3), "points3d")
     T, dev = points3d.shape[0], points3d.device
     names = ("coxa", "femur", "tibia", "tarsus")
     if T == 0:
@@ -487,7 +573,7 @@ def fit_legs(points3d, lengths="recording", anchor="per_frame", max_iter=None):
     table = None if isinstance(lengths, str) else _leg_table(lengths, (6, 4), "lengths")
     origin = None if isinstance(anchor, str) else _leg_table(anchor, (6, 3), "anchor")
     lib = _native.load()
-    _need_pose(points3d)
+    points3d = _need_tensor(points3d, torch.float64, (38, 3), "points3d")
     T, dev = points3d.shape[0], points3d.device
     if table is None:
         table = np.ascontiguousarray(segment_length_medians(points3d).cpu().numpy())
@@ -546,10 +632,7 @@ def _wavelet_bank(fps, freqs, omega0, radius):
     if freqs.ndim != 1 or freqs.dtype.kind not in "fiu":
         raise ValueError("freqs must be a numeric [F] array")
     freqs = np.ascontiguousarray(freqs, dtype=np.float64)
-    lib = _native.load()
-    need = lib.df3d_spectrogram_work_bytes(freqs.ctypes.data_as(ctypes.c_void_p), freqs.shape[0], fps, omega0, radius)
-    if need <= 0:
-        raise ValueError(lib.df3d_last_error().decode())
+    need = _workspace("df3d_spectrogram_work_bytes", freqs.ctypes.data_as(ctypes.c_void_p), freqs.shape[0], fps, omega0, radius, device=None)[1]
     return fps, freqs, omega0, radius, need
 
 
@@ -620,15 +703,6 @@ def unwrap_phase(series, channels=None):
 BehaviourMapResult = collections.namedtuple("BehaviourMapResult", "embedding train_index beta info kl perplexity")
 
 
-def _bmap_call(name, *args):
-    """One a13 entry; its DF3D_EINVAL is the caller's mistake and becomes a ValueError with the library's message."""
-    lib = _native.load()
-    rc = getattr(lib, name)(*args)
-    if rc == _native.DF3D_EINVAL:
-        raise ValueError(lib.df3d_last_error().decode())
-    _native.check(rc, name)
-
-
 def _need_f64(t, dims, name):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() in dims):
         raise ValueError(f"{name} must be a torch.float64 CUDA tensor of {' or '.join(str(d) for d in dims)} dimensions")
@@ -676,8 +750,8 @@ def _distributions(S):
     p, logp = torch.empty_like(S2), torch.empty_like(S2)
     e = torch.empty((T,), dtype=torch.float64, device=S.device)
     valid = torch.empty((T,), dtype=torch.int32, device=S.device)
-    _bmap_call("df3d_bmap_prepare", S2.data_ptr(), T, D, config.BEHAVIOUR_FLOOR, p.data_ptr(), logp.data_ptr(), e.data_ptr(), valid.data_ptr(),
-               _stream(S))
+    _call("df3d_bmap_prepare", S2.data_ptr(), T, D, config.BEHAVIOUR_FLOOR, p.data_ptr(), logp.data_ptr(), e.data_ptr(), valid.data_ptr(),
+          _stream(S))
     return p, logp, e, valid
 
 
@@ -697,14 +771,14 @@ def _divergence(pa, ea, lb):
     step = 65535 * 128   # the most rows one call takes
     for m0 in range(0, M, step):
         m1 = min(M, m0 + step)
-        _bmap_call("df3d_bmap_divergence", pa[m0:m1].data_ptr(), ea[m0:m1].data_ptr(), m1 - m0, lb.data_ptr(), N, D, K[m0:m1].data_ptr(), _stream(pa))
+        _call("df3d_bmap_divergence", pa[m0:m1].data_ptr(), ea[m0:m1].data_ptr(), m1 - m0, lb.data_ptr(), N, D, K[m0:m1].data_ptr(), _stream(pa))
     return K
 
 
 def _logs(p):
     logp = torch.empty_like(p)
     e = torch.empty((p.shape[0],), dtype=torch.float64, device=p.device)
-    _bmap_call("df3d_bmap_logs", p.data_ptr(), p.shape[0], p.shape[1], logp.data_ptr(), e.data_ptr(), _stream(p))
+    _call("df3d_bmap_logs", p.data_ptr(), p.shape[0], p.shape[1], logp.data_ptr(), e.data_ptr(), _stream(p))
     return logp, e
 
 
@@ -743,8 +817,8 @@ def perplexity_calibrate(K, perplexity=None, exclude=None):
     cond = torch.empty_like(K)
     beta = torch.empty((M,), dtype=torch.float64, device=K.device)
     info = torch.empty((M,), dtype=torch.int32, device=K.device)
-    _bmap_call("df3d_bmap_calibrate", K.data_ptr(), M, N, u, config.BEHAVIOUR_ENTROPY_TOL, config.BEHAVIOUR_BETA_MAX,
-               None if exclude is None else exclude.data_ptr(), cond.data_ptr(), beta.data_ptr(), info.data_ptr(), _stream(K))
+    _call("df3d_bmap_calibrate", K.data_ptr(), M, N, u, config.BEHAVIOUR_ENTROPY_TOL, config.BEHAVIOUR_BETA_MAX,
+          None if exclude is None else exclude.data_ptr(), cond.data_ptr(), beta.data_ptr(), info.data_ptr(), _stream(K))
     return cond, beta, info
 
 
@@ -755,17 +829,11 @@ def joint_probabilities(cond):
     if cond.shape[0] != cond.shape[1]:
         raise ValueError("cond must be square")
     P = torch.empty_like(cond)
-    _bmap_call("df3d_bmap_joint", cond.data_ptr(), cond.shape[0], P.data_ptr(), _stream(cond))
+    _call("df3d_bmap_joint", cond.data_ptr(), cond.shape[0], P.data_ptr(), _stream(cond))
     return P
 
 
-def _tsne_work(N, device):
-    need = _native.load().df3d_bmap_work_bytes(N)
-    if need <= 0:
-        from . import config
-
-        raise ValueError(f"N must be in [1, {config.BEHAVIOUR_POINTS_CAP}] (it is {N})")
-    return torch.empty((need,), dtype=torch.uint8, device=device), need
+_TSNE_REFUSAL = "N must be in [1, {}] (it is {{}})"   # df3d_bmap_work_bytes': the cap is config.BEHAVIOUR_POINTS_CAP, then N
 
 
 @_on_tensor_device
@@ -789,9 +857,9 @@ def tsne(P, init, n_iter=None, first_iter=0, state=None):
             raise ValueError("state must be (V [N, 2], G [N, 2])")
     if N == 0:
         return Y, V, G
-    work, need = _tsne_work(N, P.device)
-    _bmap_call("df3d_tsne_run", P.data_ptr(), N, Y.data_ptr(), V.data_ptr(), G.data_ptr(), int(first_iter), n_iter, max(N / 48.0, 50.0),
-               work.data_ptr(), need, _stream(P))
+    work, need = _workspace("df3d_bmap_work_bytes", N, device=P.device, refusal=_TSNE_REFUSAL.format(config.BEHAVIOUR_POINTS_CAP))
+    _call("df3d_tsne_run", P.data_ptr(), N, Y.data_ptr(), V.data_ptr(), G.data_ptr(), int(first_iter), n_iter, max(N / 48.0, 50.0),
+          work.data_ptr(), need, _stream(P))
     return Y, V, G
 
 
@@ -799,13 +867,15 @@ def tsne(P, init, n_iter=None, first_iter=0, state=None):
 def tsne_cost(P, Y):
     """The Kullback-Leibler cost sum_{P_ij > 0} P_ij log(P_ij Z / w_ij) of the positions Y [N, 2] under the joint table P [N, N]:
     a float64 tensor of one element on the device (nothing is read back)."""
+    from . import config
+
     P, Y = _need_f64(P, (2,), "P"), _need_f64(Y, (2,), "Y")
     N = P.shape[0]
     if P.shape != (N, N) or Y.shape != (N, 2) or Y.device != P.device:
         raise ValueError("P must be [N, N] and Y [N, 2] on its device")
-    work, need = _tsne_work(N, P.device)
+    work, need = _workspace("df3d_bmap_work_bytes", N, device=P.device, refusal=_TSNE_REFUSAL.format(config.BEHAVIOUR_POINTS_CAP))
     cost = torch.empty((1,), dtype=torch.float64, device=P.device)
-    _bmap_call("df3d_bmap_cost", P.data_ptr(), N, Y.data_ptr(), cost.data_ptr(), work.data_ptr(), need, _stream(P))
+    _call("df3d_bmap_cost", P.data_ptr(), N, Y.data_ptr(), cost.data_ptr(), work.data_ptr(), need, _stream(P))
     return cost[0]
 
 
@@ -853,7 +923,7 @@ def behaviour_map(S, perplexity=None, n_iter=None, max_points=None, seed=0):
         sel = rest[r0 : r0 + chunk]
         c, b, i = perplexity_calibrate(_divergence(p[sel], e[sel], lt), u)
         out = torch.empty((sel.numel(), 2), dtype=torch.float64, device=dev)
-        _bmap_call("df3d_bmap_place", c.data_ptr(), sel.numel(), N, Y.data_ptr(), out.data_ptr(), _stream(S))
+        _call("df3d_bmap_place", c.data_ptr(), sel.numel(), N, Y.data_ptr(), out.data_ptr(), _stream(S))
         embedding[sel], beta[sel], info[sel] = out, b, i
     return BehaviourMapResult(embedding, train, beta, info, float(kl.item()), u)
 
@@ -863,27 +933,13 @@ BehaviourSegmentsResult = collections.namedtuple("BehaviourSegmentsResult",
                                                  "density origin sigma regions region_peaks labels bouts occupancy transitions")
 
 
-def _bseg_work(T, G, device):
-    need = _native.load().df3d_bseg_work_bytes(int(T), int(G))
-    if need <= 0:
-        raise ValueError(f"no workspace for T = {T} frames on a grid of {G}: grid must be in [2, 1024] and T at most 65 535 * 2 048")
-    return torch.empty((need,), dtype=torch.uint8, device=device), need
-
-
-def _need_map(Y):
-    if not (isinstance(Y, torch.Tensor) and Y.is_cuda and Y.dtype == torch.float64 and Y.dim() == 2 and Y.shape[1] == 2):
-        raise ValueError("Y must be a torch.float64 CUDA tensor of shape [T, 2]")
-    return Y.contiguous()
+_BSEG_REFUSAL = "no workspace for T = {} frames on a grid of {}: grid must be in [2, 1024] and T at most 65 535 * 2 048"   # df3d_bseg_work_bytes'
 
 
 def _need_grid(grid):
     from . import config
 
-    lo, hi = config.BEHAVIOUR_GRID_RANGE
-    G = config.BEHAVIOUR_GRID if grid is None else grid
-    if isinstance(G, bool) or not isinstance(G, (int, np.integer)) or not lo <= G <= hi:
-        raise ValueError(f"grid must be an integer in [{lo}, {hi}] (it is {G!r})")
-    return int(G)
+    return _integer(config.BEHAVIOUR_GRID if grid is None else grid, *config.BEHAVIOUR_GRID_RANGE, "grid")
 
 
 def density_grid(lo, hi, grid=None, sigma=None):
@@ -918,18 +974,18 @@ def map_density(Y, grid=None, sigma=None):
     entry is not valid and contributes nothing) on the grid density_grid() lays over its valid rows: rho[r, q] = (M 2 pi sigma^2)^-1
     sum_t exp(-|g_rq - Y[t]|^2 / (2 sigma^2)) with g_rq = (x0 + (q + 0.5) h, y0 + (r + 0.5) h), the exact sum over all M valid frames.
     `grid`: G, default config.BEHAVIOUR_GRID.  The five bounds are read back.  ValueError: no valid row, and density_grid's."""
-    Y = _need_map(Y)
+    Y = _need_tensor(Y, torch.float64, (2,), "Y")
     G = _need_grid(grid)
     T = Y.shape[0]
     bounds = torch.zeros((5,), dtype=torch.float64, device=Y.device)
-    _bmap_call("df3d_bseg_bounds", Y.data_ptr(), T, bounds.data_ptr(), _stream(Y))
+    _call("df3d_bseg_bounds", Y.data_ptr(), T, bounds.data_ptr(), _stream(Y))
     b = bounds.cpu().tolist()
     if T == 0 or b[4] < 1.0:
         raise ValueError(f"the map holds no valid frame ({T} rows, each with a non-finite entry): there is nothing to take a density of")
     origin, sigma = density_grid((b[0], b[2]), (b[1], b[3]), G, sigma)
     rho = torch.empty((G, G), dtype=torch.float64, device=Y.device)
-    work, need = _bseg_work(T, G, Y.device)
-    _bmap_call("df3d_bseg_density", Y.data_ptr(), T, origin[0], origin[1], origin[2], G, sigma, rho.data_ptr(), work.data_ptr(), need, _stream(Y))
+    work, need = _workspace("df3d_bseg_work_bytes", T, G, device=Y.device, refusal=_BSEG_REFUSAL)
+    _call("df3d_bseg_density", Y.data_ptr(), T, origin[0], origin[1], origin[2], G, sigma, rho.data_ptr(), work.data_ptr(), need, _stream(Y))
     return rho, origin, sigma
 
 
@@ -953,9 +1009,9 @@ def watershed(rho, min_peak=None):
     regions = torch.empty((G, G), dtype=torch.int32, device=rho.device)
     roots = torch.empty((G * G,), dtype=torch.int32, device=rho.device)
     count = torch.empty((1,), dtype=torch.int32, device=rho.device)
-    work, need = _bseg_work(0, G, rho.device)
-    _bmap_call("df3d_bseg_watershed", rho.data_ptr(), G, min_peak, regions.data_ptr(), count.data_ptr(), roots.data_ptr(), work.data_ptr(), need,
-               _stream(rho))
+    work, need = _workspace("df3d_bseg_work_bytes", 0, G, device=rho.device, refusal=_BSEG_REFUSAL)
+    _call("df3d_bseg_watershed", rho.data_ptr(), G, min_peak, regions.data_ptr(), count.data_ptr(), roots.data_ptr(), work.data_ptr(), need,
+          _stream(rho))
     return regions, roots[: int(count.item())].clone()
 
 
@@ -963,7 +1019,7 @@ def watershed(rho, min_peak=None):
 def map_labels(Y, regions, origin):
     """labels [T] int32: -1 for a row of Y [T, 2] with a non-finite entry, else regions[r, q] of the cell the frame lies in,
     q = clamp(floor((Y[t, 0] - x0) / h), 0, G - 1) and r likewise from Y[t, 1] and y0; origin = (x0, y0, h)."""
-    Y = _need_map(Y)
+    Y = _need_tensor(Y, torch.float64, (2,), "Y")
     if not (isinstance(regions, torch.Tensor) and regions.is_cuda and regions.dtype == torch.int32 and regions.dim() == 2
             and regions.shape[0] == regions.shape[1] and regions.device == Y.device):
         raise ValueError("regions must be a torch.int32 CUDA tensor of shape [G, G] on the device of Y")
@@ -971,7 +1027,7 @@ def map_labels(Y, regions, origin):
     x0, y0, h = (float(v) for v in origin)
     regions = regions.contiguous()
     labels = torch.empty((Y.shape[0],), dtype=torch.int32, device=Y.device)
-    _bmap_call("df3d_bseg_labels", Y.data_ptr(), Y.shape[0], x0, y0, h, G, regions.data_ptr(), labels.data_ptr(), _stream(Y))
+    _call("df3d_bseg_labels", Y.data_ptr(), Y.shape[0], x0, y0, h, G, regions.data_ptr(), labels.data_ptr(), _stream(Y))
     return labels
 
 
@@ -981,12 +1037,10 @@ def ethogram(labels, num_regions):
     num_regions): the maximal runs of equal labels as rows (label, start, length) -- runs of -1 and of 0 among them, their lengths
     sum to T --, the frames of each label 0 .. R, and the counts of pairs (t, t + 1) whose labels are both >= 0 and differ.  B is
     read back."""
-    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.int32 and labels.dim() == 1):
-        raise ValueError("labels must be a torch.int32 CUDA tensor of shape [T]")
+    labels = _need_tensor(labels, torch.int32, (), "labels")
     R = int(num_regions)
     if not 0 <= R <= 32767:
         raise ValueError(f"num_regions must be in [0, 32767] (it is {R})")
-    labels = labels.contiguous()
     T, dev = labels.shape[0], labels.device
     occupancy = torch.zeros((R + 1,), dtype=torch.int64, device=dev)
     transitions = torch.zeros((R + 1, R + 1), dtype=torch.int64, device=dev)
@@ -994,9 +1048,9 @@ def ethogram(labels, num_regions):
         return torch.zeros((0, 3), dtype=torch.int64, device=dev), occupancy, transitions
     bouts = torch.empty((T, 3), dtype=torch.int64, device=dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev)
-    work, need = _bseg_work(T, 2, dev)
-    _bmap_call("df3d_bseg_bouts", labels.data_ptr(), T, R, bouts.data_ptr(), count.data_ptr(), occupancy.data_ptr(), transitions.data_ptr(),
-               work.data_ptr(), need, _stream(labels))
+    work, need = _workspace("df3d_bseg_work_bytes", T, 2, device=dev, refusal=_BSEG_REFUSAL)
+    _call("df3d_bseg_bouts", labels.data_ptr(), T, R, bouts.data_ptr(), count.data_ptr(), occupancy.data_ptr(), transitions.data_ptr(),
+          work.data_ptr(), need, _stream(labels))
     return bouts[: int(count.item())].clone(), occupancy, transitions
 
 
@@ -1038,23 +1092,11 @@ class GaitResult:
     fps: float
 
 
-def _gait_work(T, device):
-    need = _native.load().df3d_gait_work_bytes(int(T))
-    if need <= 0:
-        raise ValueError(f"no workspace for T = {T} frames: T must be at most (2^31 - 1) / 6")
-    return torch.empty((need,), dtype=torch.uint8, device=device), need
-
-
-def _need_gait(t, dtype, tail, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 1 + len(tail) and tuple(t.shape[1:]) == tail):
-        raise ValueError(f"{name} must be a {dtype} CUDA tensor of shape [T, {', '.join(str(n) for n in tail)}]")
-    return t.contiguous()
+_LEGS_REFUSAL = "no workspace for T = {} frames: T must be at most (2^31 - 1) / 6"   # df3d_gait_work_bytes' and df3d_ball_work_bytes'
 
 
 def _gait_fps(fps):
-    if isinstance(fps, bool) or not isinstance(fps, (int, float, np.integer, np.floating)) or not (np.isfinite(fps) and fps > 0):
-        raise ValueError(f"fps must be a finite number > 0 (it is {fps!r})")
-    return float(fps)
+    return _number(fps, "fps", positive=True)
 
 
 def gait_thresholds(on=None, off=None, half_window=None):
@@ -1068,11 +1110,7 @@ def gait_thresholds(on=None, off=None, half_window=None):
         raise ValueError(f"on and off must be finite (they are {on:g} and {off:g})")
     if not on > off:
         raise ValueError(f"on must be above off (they are {on:g} and {off:g})")
-    lo, hi = config.GAIT_DIFF_HALF_RANGE
-    w = config.GAIT_DIFF_HALF if half_window is None else half_window
-    if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not lo <= w <= hi:
-        raise ValueError(f"half_window must be an integer in [{lo}, {hi}] (it is {w!r})")
-    return on, off, int(w)
+    return on, off, _integer(config.GAIT_DIFF_HALF if half_window is None else half_window, *config.GAIT_DIFF_HALF_RANGE, "half_window")
 
 
 @_on_tensor_device
@@ -1082,29 +1120,17 @@ def tip_kinematics(points3d, fps, body_frame="recording", half_window=None):
     the window a = max(t - half_window, 0), b = min(t + half_window, T - 1), in the leg coordinates of joint_angles (x anterior,
     side-1 legs mirrored in y) and pose units (per second).  `body_frame` as in joint_angles.  NaN where an end joint is missing
     (the velocity: P4 at a or at b), where the window is empty (T = 1) or where the frame holds a non-finite number."""
-    if not (isinstance(points3d, torch.Tensor) and points3d.is_cuda and points3d.dtype == torch.float64 and points3d.dim() == 3
-            and tuple(points3d.shape[1:]) == (38, 3)):
-        raise ValueError("points3d must be a torch.float64 CUDA tensor of shape [T, 38, 3]")
-    points3d = points3d.contiguous()
+    points3d = _need_tensor(points3d, torch.float64, (38, 3), "points3d")
     fps, w = _gait_fps(fps), gait_thresholds(half_window=half_window)[2]
     T, dev = points3d.shape[0], points3d.device
     tip = torch.empty((T, 6, 3), dtype=torch.float64, device=dev)
     vel = torch.empty((T, 6, 3), dtype=torch.float64, device=dev)
-    if isinstance(body_frame, str):
-        if body_frame not in ("recording", "per_frame"):
-            raise ValueError('body_frame must be "recording", "per_frame" or a [3, 3] / [T, 3, 3] array')
-        frames = None
-    else:
-        frames = body_frame if isinstance(body_frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(body_frame, dtype=np.float64))
-        if tuple(frames.shape) not in ((3, 3), (1, 3, 3), (T, 3, 3)):
-            raise ValueError(f"an explicit body_frame must be [3, 3] or [T, 3, 3] with T = {T}")
-        frames = frames.to(device=dev, dtype=torch.float64).reshape(-1, 3, 3).contiguous()
+    frames = _body_frames(body_frame, T, dev)
     if T == 0:
         return tip, vel
-    if frames is None:
-        frames = recording_frame(points3d) if body_frame == "recording" else _pose_frames(points3d)
-    _bmap_call("df3d_gait_velocity", points3d.data_ptr(), T, frames.data_ptr(), frames.shape[0], fps, w, tip.data_ptr(), vel.data_ptr(),
-               _stream(points3d))
+    frames = _fill_body_frames(frames, body_frame, points3d)
+    _call("df3d_gait_velocity", points3d.data_ptr(), T, frames.data_ptr(), frames.shape[0], fps, w, tip.data_ptr(), vel.data_ptr(),
+          _stream(points3d))
     return tip, vel
 
 
@@ -1114,18 +1140,14 @@ def gait_states(vel, on=None, off=None):
     u = vel[..., 0].  A sample is unknown where u is NaN, swing where u > on, stance where u < off (defaults config.GAIT_SWING_ON and
     GAIT_SWING_OFF, a guess nobody has measured on a recording) and keeps the state otherwise; the state is that of the last
     deciding sample at or before t: -1 unknown, 0 stance, 1 swing, and -1 before the first."""
-    vel = _need_gait(vel, torch.float64, (6, 3), "vel")
+    vel = _need_tensor(vel, torch.float64, (6, 3), "vel")
     on, off, _ = gait_thresholds(on, off)
     T = vel.shape[0]
     states = torch.empty((T, 6), dtype=torch.int32, device=vel.device)
     if T:
-        work, need = _gait_work(T, vel.device)
-        _bmap_call("df3d_gait_states", vel.data_ptr(), T, on, off, states.data_ptr(), work.data_ptr(), need, _stream(vel))
+        work, need = _workspace("df3d_gait_work_bytes", T, device=vel.device, refusal=_LEGS_REFUSAL)
+        _call("df3d_gait_states", vel.data_ptr(), T, on, off, states.data_ptr(), work.data_ptr(), need, _stream(vel))
     return states
-
-
-def _need_states(states):
-    return _need_gait(states, torch.int32, (6,), "states")
 
 
 @_on_tensor_device
@@ -1135,8 +1157,8 @@ def gait_steps(states, tip, fps):
     state in [t0, t2], and t1 the one touch-down between them.  Rows (leg, t0, t1, t2) ordered by (leg, t0); metrics: swing duration
     (t1 - t0) / fps, stance duration (t2 - t1) / fps, stride tip[t1, leg, 0] - tip[t0, leg, 0] (NaN where either tip is).  S is
     read back."""
-    states = _need_states(states)
-    tip = _need_gait(tip, torch.float64, (6, 3), "tip")
+    states = _need_tensor(states, torch.int32, (6,), "states")
+    tip = _need_tensor(tip, torch.float64, (6, 3), "tip")
     fps = _gait_fps(fps)
     T, dev = states.shape[0], states.device
     if tip.shape[0] != T or tip.device != dev:
@@ -1146,9 +1168,9 @@ def gait_steps(states, tip, fps):
     steps = torch.empty((3 * T, 4), dtype=torch.int64, device=dev)
     metrics = torch.empty((3 * T, 3), dtype=torch.float64, device=dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev)
-    work, need = _gait_work(T, dev)
-    _bmap_call("df3d_gait_steps", states.data_ptr(), tip.data_ptr(), T, fps, steps.data_ptr(), metrics.data_ptr(), count.data_ptr(),
-               work.data_ptr(), need, _stream(states))
+    work, need = _workspace("df3d_gait_work_bytes", T, device=dev, refusal=_LEGS_REFUSAL)
+    _call("df3d_gait_steps", states.data_ptr(), tip.data_ptr(), T, fps, steps.data_ptr(), metrics.data_ptr(), count.data_ptr(),
+          work.data_ptr(), need, _stream(states))
     S = int(count.item())
     return steps[:S].clone(), metrics[:S].clone()
 
@@ -1157,12 +1179,12 @@ def gait_steps(states, tip, fps):
 def gait_phase(states):
     """phase [T, 6] float64 of states [T, 6] (int32 cuda): (t - t0) / (t2 - t0) for the step of the leg with t0 <= t < t2
     (gait_steps), NaN outside every step."""
-    states = _need_states(states)
+    states = _need_tensor(states, torch.int32, (6,), "states")
     T = states.shape[0]
     phase = torch.empty((T, 6), dtype=torch.float64, device=states.device)
     if T:
-        work, need = _gait_work(T, states.device)
-        _bmap_call("df3d_gait_phase", states.data_ptr(), T, phase.data_ptr(), work.data_ptr(), need, _stream(states))
+        work, need = _workspace("df3d_gait_work_bytes", T, device=states.device, refusal=_LEGS_REFUSAL)
+        _call("df3d_gait_phase", states.data_ptr(), T, phase.data_ptr(), work.data_ptr(), need, _stream(states))
     return phase
 
 
@@ -1171,13 +1193,13 @@ def gait_coupling(phase):
     """(mean [6, 6, 2] float64, count [6, 6] int64) of phase [T, 6] (float64 cuda): for every ordered pair of legs the mean of
     (cos, sin)(2 pi (phase_i - phase_j)) over the count[i, j] frames where both phases are finite, NaN where there is none.  The
     resultant length is numpy.hypot of the two components and the mean angle their arctan2."""
-    phase = _need_gait(phase, torch.float64, (6,), "phase")
+    phase = _need_tensor(phase, torch.float64, (6,), "phase")
     T, dev = phase.shape[0], phase.device
     mean = torch.full((6, 6, 2), float("nan"), dtype=torch.float64, device=dev)
     count = torch.zeros((6, 6), dtype=torch.int64, device=dev)
     if T:
-        work, need = _gait_work(T, dev)
-        _bmap_call("df3d_gait_coupling", phase.data_ptr(), T, mean.data_ptr(), count.data_ptr(), work.data_ptr(), need, _stream(phase))
+        work, need = _workspace("df3d_gait_work_bytes", T, device=dev, refusal=_LEGS_REFUSAL)
+        _call("df3d_gait_coupling", phase.data_ptr(), T, mean.data_ptr(), count.data_ptr(), work.data_ptr(), need, _stream(phase))
     return mean, count
 
 
@@ -1186,13 +1208,13 @@ def gait_patterns(states):
     """(pattern [T] int32, histogram [64] int64, state_counts [6, 3] int64) of states [T, 6] (int32 cuda): every frame's mask of
     the legs in swing (bit L = leg L; config.GAIT_TRIPODS are the two tripods), -1 where a leg is unknown; the frames of every
     mask; every leg's unknown, stance and swing frames."""
-    states = _need_states(states)
+    states = _need_tensor(states, torch.int32, (6,), "states")
     T, dev = states.shape[0], states.device
     pattern = torch.empty((T,), dtype=torch.int32, device=dev)
     histogram = torch.zeros((64,), dtype=torch.int64, device=dev)
     counts = torch.zeros((6, 3), dtype=torch.int64, device=dev)
     if T:
-        _bmap_call("df3d_gait_patterns", states.data_ptr(), T, pattern.data_ptr(), histogram.data_ptr(), counts.data_ptr(), _stream(states))
+        _call("df3d_gait_patterns", states.data_ptr(), T, pattern.data_ptr(), histogram.data_ptr(), counts.data_ptr(), _stream(states))
     return pattern, histogram, counts
 
 
@@ -1255,24 +1277,10 @@ def treadmill_params(radius=None, min_legs=None, iterations=None):
     from . import config
 
     if radius is not None:
-        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or not (np.isfinite(radius) and radius > 0):
-            raise ValueError(f"radius must be a finite number > 0 (it is {radius!r})")
-        radius = float(radius)
-    out = []
-    for v, default, (lo, hi), name in ((min_legs, config.BALL_MIN_LEGS, config.BALL_MIN_LEGS_RANGE, "min_legs"),
-                                       (iterations, config.BALL_FIT_ITERATIONS, config.BALL_FIT_ITERATIONS_RANGE, "iterations")):
-        v = default if v is None else v
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-            raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (it is {v!r})")
-        out.append(int(v))
-    return (radius, *out)
-
-
-def _ball_work(T, device):
-    need = _native.load().df3d_ball_work_bytes(int(T))
-    if need <= 0:
-        raise ValueError(f"no workspace for T = {T} frames: T must be at most (2^31 - 1) / 6")
-    return torch.empty((need,), dtype=torch.uint8, device=device), need
+        radius = _number(radius, "radius", positive=True)
+    min_legs = _integer(config.BALL_MIN_LEGS if min_legs is None else min_legs, *config.BALL_MIN_LEGS_RANGE, "min_legs")
+    iterations = _integer(config.BALL_FIT_ITERATIONS if iterations is None else iterations, *config.BALL_FIT_ITERATIONS_RANGE, "iterations")
+    return radius, min_legs, iterations
 
 
 def _same_frames(t, T, dev, name):
@@ -1287,27 +1295,20 @@ def body_tips(points3d, fps, body_frame="recording", half_window=None):
     mirrored nor relative to the coxa, unlike tip_kinematics -- and its velocity F (P4[b] - P4[a]) fps / (b - a) over gait's window.
     `body_frame`: "recording" or an explicit [3, 3] array or tensor (rows ex, ey, ez).  NaN where the tip is missing (the velocity: at
     a or at b), where the window is empty (T = 1) or where the frame or o holds a non-finite number."""
-    points3d = _need_pose(points3d)
+    points3d = _need_tensor(points3d, torch.float64, (38, 3), "points3d")
     fps, w = _gait_fps(fps), gait_thresholds(half_window=half_window)[2]
     T, dev = points3d.shape[0], points3d.device
-    if isinstance(body_frame, str):
-        if body_frame != "recording":
-            raise ValueError('body_frame must be "recording" or a [3, 3] array: the ball is one object in one frame')
-        frame = None
-    else:
-        frame = body_frame if isinstance(body_frame, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(body_frame, dtype=np.float64))
-        if tuple(frame.shape) not in ((3, 3), (1, 3, 3)):
-            raise ValueError("an explicit body_frame must be [3, 3]: the ball is one object in one frame")
-        frame = frame.to(device=dev, dtype=torch.float64).reshape(3, 3).contiguous()
+    frame = _body_frames(body_frame, T, dev, per_frame_allowed=False,
+                         text=('body_frame must be "recording" or a [3, 3] array: the ball is one object in one frame',
+                               "an explicit body_frame must be [3, 3]: the ball is one object in one frame"))
     tips = torch.empty((T, 6, 3), dtype=torch.float64, device=dev)
     vel = torch.empty((T, 6, 3), dtype=torch.float64, device=dev)
     if T == 0:
         return tips, vel
     coxa = _coxa_medians(points3d)[1].contiguous()
-    if frame is None:
-        frame = recording_frame(points3d).reshape(3, 3).contiguous()
-    _bmap_call("df3d_ball_tips", points3d.data_ptr(), T, frame.data_ptr(), coxa.data_ptr(), fps, w, tips.data_ptr(), vel.data_ptr(),
-               _stream(points3d))
+    frame = _fill_body_frames(frame, body_frame, points3d)   # [1, 3, 3]: the nine numbers df3d_ball_tips reads
+    _call("df3d_ball_tips", points3d.data_ptr(), T, frame.data_ptr(), coxa.data_ptr(), fps, w, tips.data_ptr(), vel.data_ptr(),
+          _stream(points3d))
     return tips, vel
 
 
@@ -1321,8 +1322,8 @@ def fit_ball(tips, states, radius=None, iterations=None):
     diagonal entry.  Nothing is read back."""
     from . import config
 
-    tips = _need_gait(tips, torch.float64, (6, 3), "tips")
-    states = _need_states(states)
+    tips = _need_tensor(tips, torch.float64, (6, 3), "tips")
+    states = _need_tensor(states, torch.int32, (6,), "states")
     radius, _, iterations = treadmill_params(radius, None, iterations)
     T, dev = tips.shape[0], tips.device
     _same_frames(states, T, dev, "states")
@@ -1331,10 +1332,10 @@ def fit_ball(tips, states, radius=None, iterations=None):
     info = torch.tensor([0, 1], dtype=torch.int64, device=dev)   # no frames: no samples, a refused fit
     sums = torch.zeros((17,), dtype=torch.float64, device=dev)
     if T:
-        work, need = _ball_work(T, dev)
-        _bmap_call("df3d_ball_fit", tips.data_ptr(), states.data_ptr(), T, 0 if radius is None else 1, 0.0 if radius is None else radius,
-                   iterations, float(config.BALL_PIVOT_MIN), ball.data_ptr(), info.data_ptr(), sums.data_ptr(), work.data_ptr(), need,
-                   _stream(tips))
+        work, need = _workspace("df3d_ball_work_bytes", T, device=dev, refusal=_LEGS_REFUSAL)
+        _call("df3d_ball_fit", tips.data_ptr(), states.data_ptr(), T, 0 if radius is None else 1, 0.0 if radius is None else radius,
+              iterations, float(config.BALL_PIVOT_MIN), ball.data_ptr(), info.data_ptr(), sums.data_ptr(), work.data_ptr(), need,
+              _stream(tips))
     return BallFit(ball, info, sums)
 
 
@@ -1348,9 +1349,9 @@ def ball_rotation(tips, vel, states, ball, min_legs=None):
     sideways speed (pose units per second) and yaw rate (rad/s)."""
     from . import config
 
-    tips = _need_gait(tips, torch.float64, (6, 3), "tips")
-    vel = _need_gait(vel, torch.float64, (6, 3), "vel")
-    states = _need_states(states)
+    tips = _need_tensor(tips, torch.float64, (6, 3), "tips")
+    vel = _need_tensor(vel, torch.float64, (6, 3), "vel")
+    states = _need_tensor(states, torch.int32, (6,), "states")
     min_legs = treadmill_params(None, min_legs)[1]
     T, dev = tips.shape[0], tips.device
     _same_frames(vel, T, dev, "vel")
@@ -1364,9 +1365,9 @@ def ball_rotation(tips, vel, states, ball, min_legs=None):
     residual = torch.empty((T,), dtype=torch.float64, device=dev)
     fictive = torch.empty((T, 3), dtype=torch.float64, device=dev)
     if T:
-        _bmap_call("df3d_ball_rotation", tips.data_ptr(), vel.data_ptr(), states.data_ptr(), T, ball.data_ptr(), min_legs,
-                   float(config.BALL_FRAME_PIVOT_MIN), rotation.data_ptr(), legs.data_ptr(), residual.data_ptr(), fictive.data_ptr(),
-                   _stream(tips))
+        _call("df3d_ball_rotation", tips.data_ptr(), vel.data_ptr(), states.data_ptr(), T, ball.data_ptr(), min_legs,
+              float(config.BALL_FRAME_PIVOT_MIN), rotation.data_ptr(), legs.data_ptr(), residual.data_ptr(), fictive.data_ptr(),
+              _stream(tips))
     return rotation, legs, residual, fictive
 
 
@@ -1375,14 +1376,14 @@ def fictive_path(fictive, fps):
     """(path [T, 3] float64 = (x, y, theta), skipped, a 0-dim int64 tensor) of fictive [T, 3] (float64 cuda, ball_rotation's) sampled at
     `fps`: theta_0 = 0, theta_{t+1} = theta_t + yaw_t / fps; (x, y)_0 = 0, (x, y)_{t+1} = (x, y)_t + Rot(theta_t)(forward_t,
     sideways_t) / fps.  A frame with a non-finite component moves nothing and is counted in `skipped`."""
-    fictive = _need_gait(fictive, torch.float64, (3,), "fictive")
+    fictive = _need_tensor(fictive, torch.float64, (3,), "fictive")
     fps = _gait_fps(fps)
     T, dev = fictive.shape[0], fictive.device
     path = torch.empty((T, 3), dtype=torch.float64, device=dev)
     skipped = torch.zeros((1,), dtype=torch.int64, device=dev)
     if T:
-        work, need = _ball_work(T, dev)
-        _bmap_call("df3d_ball_path", fictive.data_ptr(), T, fps, path.data_ptr(), skipped.data_ptr(), work.data_ptr(), need, _stream(fictive))
+        work, need = _workspace("df3d_ball_work_bytes", T, device=dev, refusal=_LEGS_REFUSAL)
+        _call("df3d_ball_path", fictive.data_ptr(), T, fps, path.data_ptr(), skipped.data_ptr(), work.data_ptr(), need, _stream(fictive))
     return path, skipped[0]
 
 
@@ -1402,7 +1403,7 @@ def treadmill(points3d, fps, body_frame="recording", states=None, radius=None, o
         states = gait_states(vel, thresholds[0], thresholds[1])   # the anterior velocity is tip_kinematics' own: F (P4[b] - P4[a]) . ex
         on, off = thresholds[:2]
     else:
-        states = _need_states(states)
+        states = _need_tensor(states, torch.int32, (6,), "states")
         _same_frames(states, tip.shape[0], tip.device, "states")
         on = off = float("nan")
     ball = fit_ball(tip, states, radius, iterations)
@@ -1433,33 +1434,16 @@ def repair_params(half_window=None, threshold=None, floor=None, max_gap=None, mi
     max_gap that is no integer in config.REPAIR_MAX_GAP_RANGE, a min_count that is no integer in [1, 2 half_window + 1]."""
     from . import config
 
-    def integer(v, lo, hi, name):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-            raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (it is {v!r})")
-        return int(v)
-
-    def number(v, name):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError(f"{name} must be a number (it is {v!r})")
-        return float(v)
-
-    h = integer(config.REPAIR_HALF_WINDOW if half_window is None else half_window, *config.REPAIR_HALF_WINDOW_RANGE, "half_window")
-    k = number(config.REPAIR_THRESHOLD if threshold is None else threshold, "threshold")
+    h = _integer(config.REPAIR_HALF_WINDOW if half_window is None else half_window, *config.REPAIR_HALF_WINDOW_RANGE, "half_window")
+    k = _number(config.REPAIR_THRESHOLD if threshold is None else threshold, "threshold")
     if not (np.isfinite(k) and k > 0.0):
         raise ValueError(f"threshold must be finite and > 0 (it is {k:g})")
-    fl = number(config.REPAIR_FLOOR if floor is None else floor, "floor")
+    fl = _number(config.REPAIR_FLOOR if floor is None else floor, "floor")
     if not (np.isfinite(fl) and fl >= 0.0):
         raise ValueError(f"floor must be finite and >= 0 (it is {fl:g})")
-    gap = integer(config.REPAIR_MAX_GAP if max_gap is None else max_gap, *config.REPAIR_MAX_GAP_RANGE, "max_gap")
-    n_min = integer(config.REPAIR_MIN_COUNT if min_count is None else min_count, 1, 2 * h + 1, "min_count")
+    gap = _integer(config.REPAIR_MAX_GAP if max_gap is None else max_gap, *config.REPAIR_MAX_GAP_RANGE, "max_gap")
+    n_min = _integer(config.REPAIR_MIN_COUNT if min_count is None else min_count, 1, 2 * h + 1, "min_count")
     return h, k, fl, gap, n_min
-
-
-def _need_pose(points3d):
-    if not (isinstance(points3d, torch.Tensor) and points3d.is_cuda and points3d.dtype == torch.float64 and points3d.dim() == 3
-            and tuple(points3d.shape[1:]) == (38, 3)):
-        raise ValueError("points3d must be a torch.float64 CUDA tensor of shape [T, 38, 3]")
-    return points3d.contiguous()
 
 
 @_on_tensor_device
@@ -1471,14 +1455,14 @@ def pose_outliers(points3d, half_window=None, threshold=None, floor=None, min_co
     score: the largest deviation / bound over the coordinates, NaN for a missing or untested joint.  Defaults: repair_params."""
     from . import config
 
-    points3d = _need_pose(points3d)
+    points3d = _need_tensor(points3d, torch.float64, (38, 3), "points3d")
     h, k, fl, _, n_min = repair_params(half_window, threshold, floor, None, min_count)
     T, dev = points3d.shape[0], points3d.device
     flags = torch.empty((T, 38), dtype=torch.uint8, device=dev)
     score = torch.empty((T, 38), dtype=torch.float64, device=dev)
     if T:
-        _bmap_call("df3d_repair_outliers", points3d.data_ptr(), T, h, k * config.REPAIR_MAD_TO_SIGMA, fl, n_min, flags.data_ptr(),
-                   score.data_ptr(), _stream(points3d))
+        _call("df3d_repair_outliers", points3d.data_ptr(), T, h, k * config.REPAIR_MAD_TO_SIGMA, fl, n_min, flags.data_ptr(),
+              score.data_ptr(), _stream(points3d))
     return flags, score
 
 
@@ -1489,7 +1473,7 @@ def fill_gaps(points3d, flags, max_gap=None):
     first good frame after, where both exist and at most max_gap frames lie between them, and set to 0 -- missing -- otherwise.  Good
     joints keep their bits; nothing is extrapolated.  status: 0 kept, 1 missing and filled, 2 outlier and filled, 3 missing and left,
     4 outlier and removed; counts: the frames per joint and code."""
-    points3d = _need_pose(points3d)
+    points3d = _need_tensor(points3d, torch.float64, (38, 3), "points3d")
     T, dev = points3d.shape[0], points3d.device
     if not (isinstance(flags, torch.Tensor) and flags.dtype == torch.uint8 and flags.device == dev and tuple(flags.shape) == (T, 38)):
         raise ValueError(f"flags must be a torch.uint8 tensor of shape [{T}, 38] on the device of points3d")
@@ -1499,12 +1483,9 @@ def fill_gaps(points3d, flags, max_gap=None):
     status = torch.empty((T, 38), dtype=torch.int8, device=dev)
     counts = torch.zeros((38, 5), dtype=torch.int64, device=dev)
     if T:
-        need = _native.load().df3d_repair_work_bytes(T)
-        if need <= 0:
-            raise ValueError(f"no workspace for T = {T} frames: T must be at most (2^31 - 1) / 38")
-        work = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _bmap_call("df3d_repair_fill", points3d.data_ptr(), flags.data_ptr(), T, gap, points.data_ptr(), status.data_ptr(), counts.data_ptr(),
-                   work.data_ptr(), need, _stream(points3d))
+        work, need = _workspace("df3d_repair_work_bytes", T, device=dev, refusal="no workspace for T = {} frames: T must be at most (2^31 - 1) / 38")
+        _call("df3d_repair_fill", points3d.data_ptr(), flags.data_ptr(), T, gap, points.data_ptr(), status.data_ptr(), counts.data_ptr(),
+              work.data_ptr(), need, _stream(points3d))
     return points, status, counts
 
 
@@ -1538,26 +1519,18 @@ def track_params(tau=None, w_motion=None, w_value=None, block_frames=None):
     config.TRACK_WEIGHT_MAX], a block_frames that is no integer in config.TRACK_BLOCK_FRAMES_RANGE."""
     from . import config
 
-    def number(v, name):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError(f"{name} must be a number (it is {v!r})")
-        return float(v)
-
     d = config.TRACK_DEFAULTS
-    t = number(d["tau"] if tau is None else tau, "tau")
+    t = _number(d["tau"] if tau is None else tau, "tau")
     if not (np.isfinite(t) and t > 0.0):
         raise ValueError(f"tau must be finite and > 0 (it is {t:g})")
     weights = []
     for name, v in (("w_motion", w_motion), ("w_value", w_value)):
-        w = number(d[name] if v is None else v, name)
+        w = _number(d[name] if v is None else v, name)
         if not (np.isfinite(w) and 0.0 <= w <= config.TRACK_WEIGHT_MAX):
             raise ValueError(f"{name} must be finite and in [0, {config.TRACK_WEIGHT_MAX:g}] (it is {w:g})")
         weights.append(w)
-    b = d["block_frames"] if block_frames is None else block_frames
-    lo, hi = config.TRACK_BLOCK_FRAMES_RANGE
-    if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not lo <= b <= hi:
-        raise ValueError(f"block_frames must be an integer in [{lo}, {hi}] (it is {b!r})")
-    return t, weights[0], weights[1], int(b)
+    b = _integer(d["block_frames"] if block_frames is None else block_frames, *config.TRACK_BLOCK_FRAMES_RANGE, "block_frames")
+    return t, weights[0], weights[1], b
 
 
 def _need_peaks(peak_count, peak_pts, peak_val):
@@ -1595,12 +1568,10 @@ def track_peaks(peak_count, peak_pts, peak_val, image_shape, tau=None, w_motion=
     choice = torch.empty((C, T, J), dtype=torch.int32, device=dev)
     cost = torch.zeros((C, J), dtype=torch.int64, device=dev)
     if T:
-        need = _native.load().df3d_track_work_bytes(C * J, T, K, b)
-        if need <= 0:
-            raise ValueError(f"no workspace for {C * J} chains of {T} frames: C J must be at most 2^20, T at most 2^31 - 1 and C J T at most 2^36")
-        work = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _bmap_call("df3d_track_peaks", peak_count.data_ptr(), peak_pts.data_ptr(), peak_val.data_ptr(), C, T, J, K, H, W, t, wm, wv, b,
-                   choice.data_ptr(), cost.data_ptr(), work.data_ptr(), need, _stream(peak_count))
+        work, need = _workspace("df3d_track_work_bytes", C * J, T, K, b, device=dev,
+                                refusal="no workspace for {} chains of {} frames: C J must be at most 2^20, T at most 2^31 - 1 and C J T at most 2^36")
+        _call("df3d_track_peaks", peak_count.data_ptr(), peak_pts.data_ptr(), peak_val.data_ptr(), C, T, J, K, H, W, t, wm, wv, b,
+              choice.data_ptr(), cost.data_ptr(), work.data_ptr(), need, _stream(peak_count))
     return TrackResult(choice, cost, (t, wm, wv, b))
 
 
@@ -1652,41 +1623,18 @@ def consensus_params(tau=None, min_views=None):
     in config.ROBUST_MIN_VIEWS_RANGE."""
     from . import config
 
-    if tau is None:
-        t = np.array(config.ROBUST_TAU, dtype=np.float64)
-    else:
-        if isinstance(tau, (bool, str)) or (isinstance(tau, (list, tuple, np.ndarray)) and np.asarray(tau).dtype.kind not in "fiu"):
-            raise ValueError(f"tau must be a number or one number per joint (it is {tau!r})")
-        try:
-            t = np.array(tau, dtype=np.float64).reshape(-1)
-        except (TypeError, ValueError):
-            raise ValueError(f"tau must be a number or one number per joint (it is {tau!r})") from None
-    if t.size == 0 or not bool(np.all(t >= 0.0)):
-        raise ValueError("tau must be >= 0 and not NaN (+inf accepts every finite error)")
-    m = config.ROBUST_MIN_VIEWS if min_views is None else min_views
-    lo, hi = config.ROBUST_MIN_VIEWS_RANGE
-    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not lo <= m <= hi:
-        raise ValueError(f"min_views must be an integer in [{lo}, {hi}] (it is {m!r})")
-    return t, int(m)
+    t = _per_joint(tau, config.ROBUST_TAU, "tau")
+    return t, _integer(config.ROBUST_MIN_VIEWS if min_views is None else min_views, *config.ROBUST_MIN_VIEWS_RANGE, "min_views")
 
 
 def _consensus_inputs(P, points2d_px, X):
-    """(Ph, X, ncam, T, J): the checks consensus_candidates and triangulate_consensus share; X = triangulate() when None."""
-    _need(points2d_px, torch.float64, "points2d_px")
-    if points2d_px.dim() != 4 or points2d_px.shape[3] != 2:
-        raise ValueError("points2d_px must be [ncam, T, J, 2]")
-    ncam, T, J, _ = points2d_px.shape
-    if not (1 <= ncam <= 8 and 1 <= J <= 64):
-        raise ValueError("points2d_px must hold 1 to 8 cameras and 1 to 64 joints")
-    Ph = np.ascontiguousarray(P.detach().cpu().numpy() if isinstance(P, torch.Tensor) else P, dtype=np.float64)
-    if Ph.shape != (ncam, 3, 4):
-        raise ValueError("P must be [ncam, 3, 4]")
+    """(Ph, X, ncam, T, J): the checks the consensus and the trajectory entries share; X = triangulate() when None."""
+    ncam, T, J = _need_points2d_px(points2d_px, bounded=True)
+    Ph = _camera_matrices(P, ncam)
     if X is None:
         X = triangulate(Ph, points2d_px)
     else:
-        _need(X, torch.float64, "X")
-        if tuple(X.shape) != (T, J, 3) or X.device != points2d_px.device:
-            raise ValueError("X must be [T, J, 3] on the device of points2d_px")
+        _need_X(X, points2d_px)
     return Ph, X, ncam, T, J
 
 
@@ -1701,8 +1649,8 @@ def consensus_candidates(P, points2d_px, X=None):
     cand_X = torch.zeros((T, J, 1 << ncam, 3), dtype=torch.float64, device=dev)
     cand_q = torch.zeros((T, J, 1 << ncam, ncam), dtype=torch.float64, device=dev)
     if T:
-        _bmap_call("df3d_consensus_candidates", Ph.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), points2d_px.data_ptr(), X.data_ptr(), ncam, T, J,
-                   cand_X.data_ptr(), cand_q.data_ptr(), _stream(points2d_px))
+        _call("df3d_consensus_candidates", Ph.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), points2d_px.data_ptr(), X.data_ptr(), ncam, T, J,
+              cand_X.data_ptr(), cand_q.data_ptr(), _stream(points2d_px))
     return cand_X, cand_q
 
 
@@ -1717,20 +1665,17 @@ def triangulate_consensus(P, points2d_px, X=None, tau=None, min_views=None):
     detection lies near an epipolar line.  Defaults and refusals: consensus_params."""
     t, m = consensus_params(tau, min_views)   # refused before any device work
     Ph, X, ncam, T, J = _consensus_inputs(P, points2d_px, X)
-    if t.shape not in ((1,), (J,)):
-        raise ValueError(f"tau must hold one value, or one per joint ({J})" + (" (config.ROBUST_TAU is for 38)" if tau is None else ""))
-    t = np.ascontiguousarray(np.broadcast_to(t, (J,)))
+    t = _broadcast_per_joint(t, J, "tau", "ROBUST_TAU" if tau is None else None)
     dev = points2d_px.device
     out = ConsensusResult(torch.empty((T, J, 3), dtype=torch.float64, device=dev), torch.empty((T, J), dtype=torch.int32, device=dev),
                           torch.empty((T, J), dtype=torch.int8, device=dev), torch.empty((ncam, T, J), dtype=torch.float64, device=dev),
                           torch.empty((ncam, T, J, 2), dtype=torch.float64, device=dev), torch.zeros((J, 4), dtype=torch.int64, device=dev), (t, m))
     if T:
-        need = _native.load().df3d_consensus_work_bytes(ncam, T, J)
-        work = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+        work, need = _workspace("df3d_consensus_work_bytes", ncam, T, J, device=dev, least=8)
         dp = ctypes.POINTER(ctypes.c_double)
-        _bmap_call("df3d_triangulate_consensus", Ph.ctypes.data_as(dp), points2d_px.data_ptr(), X.data_ptr(), ncam, T, J, t.ctypes.data_as(dp), m,
-                   out.points3d.data_ptr(), out.cameras.data_ptr(), out.status.data_ptr(), out.error.data_ptr(), out.fixed_px.data_ptr(),
-                   out.counts.data_ptr(), work.data_ptr(), need, _stream(points2d_px))
+        _call("df3d_triangulate_consensus", Ph.ctypes.data_as(dp), points2d_px.data_ptr(), X.data_ptr(), ncam, T, J, t.ctypes.data_as(dp), m,
+              out.points3d.data_ptr(), out.cameras.data_ptr(), out.status.data_ptr(), out.error.data_ptr(), out.fixed_px.data_ptr(),
+              out.counts.data_ptr(), work.data_ptr(), need, _stream(points2d_px))
     return out
 
 
@@ -1761,37 +1706,17 @@ def trajectory_params(lam=None, huber=None, max_gap=None, block_frames=None):
     config.TRAJECTORY_BLOCK_FRAMES_RANGE."""
     from . import config
 
-    if lam is None:
-        l = np.array(config.TRAJECTORY_LAMBDA, dtype=np.float64)
-    else:
-        if isinstance(lam, (bool, str)) or (isinstance(lam, (list, tuple, np.ndarray)) and np.asarray(lam).dtype.kind not in "fiu"):
-            raise ValueError(f"lam must be a number or one number per joint (it is {lam!r})")
-        try:
-            l = np.array(lam, dtype=np.float64).reshape(-1)
-        except (TypeError, ValueError):
-            raise ValueError(f"lam must be a number or one number per joint (it is {lam!r})") from None
-    if l.size == 0 or not bool(np.all((l >= 0.0) & np.isfinite(l))):
-        raise ValueError("lam must be >= 0 and finite")
-    h = config.TRAJECTORY_HUBER if huber is None else huber
-    if isinstance(h, (bool, str)) or not isinstance(h, (int, float, np.integer, np.floating)):
-        raise ValueError(f"huber must be a number (it is {h!r})")
-    if not float(h) >= 0.0:
+    l = _per_joint(lam, config.TRAJECTORY_LAMBDA, "lam", finite=True)
+    h = _number(config.TRAJECTORY_HUBER if huber is None else huber, "huber")
+    if not h >= 0.0:
         raise ValueError("huber must be >= 0 and not NaN (+inf is plain least squares)")
-
-    def integer(v, lo, hi, name):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-            raise ValueError(f"{name} must be an integer in [{lo}, {hi}] (it is {v!r})")
-        return int(v)
-
-    gap = integer(config.REPAIR_MAX_GAP if max_gap is None else max_gap, *config.REPAIR_MAX_GAP_RANGE, "max_gap")
-    b = None if block_frames is None else integer(block_frames, *config.TRAJECTORY_BLOCK_FRAMES_RANGE, "block_frames")
-    return l, float(h), gap, b
+    gap = _integer(config.REPAIR_MAX_GAP if max_gap is None else max_gap, *config.REPAIR_MAX_GAP_RANGE, "max_gap")
+    b = None if block_frames is None else _integer(block_frames, *config.TRAJECTORY_BLOCK_FRAMES_RANGE, "block_frames")
+    return l, h, gap, b
 
 
 def _trajectory_lambda(l, J, default):
-    if l.shape not in ((1,), (J,)):
-        raise ValueError(f"lam must hold one value, or one per joint ({J})" + (" (config.TRAJECTORY_LAMBDA is for 38)" if default else ""))
-    return np.ascontiguousarray(np.broadcast_to(l, (J,)))
+    return _broadcast_per_joint(l, J, "lam", "TRAJECTORY_LAMBDA" if default else None)
 
 
 def _trajectory_work(ncam, T, J, b, dev):
@@ -1799,10 +1724,8 @@ def _trajectory_work(ncam, T, J, b, dev):
     from . import config
 
     b = config.trajectory_block_frames(T) if b is None else b
-    need = _native.load().df3d_trajectory_work_bytes(ncam, T, J, b)
-    if need <= 0:
-        raise ValueError(f"no workspace for {T} frames: T must be at most {config.TRAJECTORY_MAX_FRAMES}")
-    return torch.empty((need,), dtype=torch.uint8, device=dev), need, b
+    refusal = f"no workspace for {{1}} frames: T must be at most {config.TRAJECTORY_MAX_FRAMES}"
+    return (*_workspace("df3d_trajectory_work_bytes", ncam, T, J, b, device=dev, refusal=refusal), b)
 
 
 @_on_tensor_device
@@ -1818,8 +1741,8 @@ def trajectory_linearize(P, points2d_px, X, huber=None):
            torch.zeros((J,), dtype=torch.float64, device=dev))
     if T:
         work = torch.empty((T * J,), dtype=torch.float64, device=dev)
-        _bmap_call("df3d_trajectory_linearize", Ph.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), points2d_px.data_ptr(), X.data_ptr(), ncam, T, J,
-                   h, *(o.data_ptr() for o in out), work.data_ptr(), T * J * 8, _stream(points2d_px))
+        _call("df3d_trajectory_linearize", Ph.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), points2d_px.data_ptr(), X.data_ptr(), ncam, T, J,
+              h, *(o.data_ptr() for o in out), work.data_ptr(), T * J * 8, _stream(points2d_px))
     return out
 
 
@@ -1843,8 +1766,8 @@ def trajectory_solve(H, g, segment, lam, mu, block_frames=None):
     ok = torch.ones((J,), dtype=torch.int32, device=dev)
     if T:
         work, need, b = _trajectory_work(1, T, J, b, dev)
-        _bmap_call("df3d_trajectory_solve", H.contiguous().data_ptr(), g.contiguous().data_ptr(), segment.contiguous().data_ptr(), T, J,
-                   l.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(mu), b, d.data_ptr(), ok.data_ptr(), None, work.data_ptr(), need, _stream(H))
+        _call("df3d_trajectory_solve", H.contiguous().data_ptr(), g.contiguous().data_ptr(), segment.contiguous().data_ptr(), T, J,
+              l.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(mu), b, d.data_ptr(), ok.data_ptr(), None, work.data_ptr(), need, _stream(H))
     return d, ok
 
 
@@ -1870,9 +1793,9 @@ def triangulate_trajectory(P, points2d_px, X=None, lam=None, huber=None, max_gap
         work, need, b = _trajectory_work(ncam, T, J, b, dev)
         out.params = (l, h, gap, b)
         dp = ctypes.POINTER(ctypes.c_double)
-        _bmap_call("df3d_triangulate_trajectory", Ph.ctypes.data_as(dp), points2d_px.contiguous().data_ptr(), X.contiguous().data_ptr(), ncam, T, J,
-                   l.ctypes.data_as(dp), h, gap, b, out.points3d.data_ptr(), out.status.data_ptr(), out.weight.data_ptr(), out.error.data_ptr(),
-                   out.iterations.data_ptr(), out.cost.data_ptr(), out.counts.data_ptr(), work.data_ptr(), need, _stream(points2d_px))
+        _call("df3d_triangulate_trajectory", Ph.ctypes.data_as(dp), points2d_px.contiguous().data_ptr(), X.contiguous().data_ptr(), ncam, T, J,
+              l.ctypes.data_as(dp), h, gap, b, out.points3d.data_ptr(), out.status.data_ptr(), out.weight.data_ptr(), out.error.data_ptr(),
+              out.iterations.data_ptr(), out.cost.data_ptr(), out.counts.data_ptr(), work.data_ptr(), need, _stream(points2d_px))
     return out
 
 

@@ -237,14 +237,14 @@ def test_chunked_placement_gives_the_same_bits(native_lib, cuda, monkeypatch):
     full = bo.planted_spectra()[0]
     c = bo.PLANTED
     calls = []
-    real = ops._bmap_call
+    real = ops._call
 
     def counting(name, *args):
         if name == "df3d_bmap_place":
             calls.append(int(args[1]))
         return real(name, *args)
 
-    monkeypatch.setattr(ops, "_bmap_call", counting)
+    monkeypatch.setattr(ops, "_call", counting)
     whole = ops.behaviour_map(_dev(full, cuda), c["perplexity"], 50, c["max_points"], seed=0)
     assert calls == [60]
     del calls[:]

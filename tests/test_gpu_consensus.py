@@ -204,9 +204,9 @@ def _native_overlap(ops, P, d):
     need = lib.df3d_consensus_work_bytes(ncam, T, J)
     work = torch.empty(need, dtype=torch.uint8, device=d.device)
     dp = ctypes.POINTER(ctypes.c_double)
-    ops._bmap_call("df3d_triangulate_consensus", np.ascontiguousarray(P).ctypes.data_as(dp), d.data_ptr(), full.data_ptr(), ncam, T, J,
-                   t.ctypes.data_as(dp), 2, full.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), None, None, work.data_ptr(),
-                   need, ops._stream(d))
+    ops._call("df3d_triangulate_consensus", np.ascontiguousarray(P).ctypes.data_as(dp), d.data_ptr(), full.data_ptr(), ncam, T, J,
+              t.ctypes.data_as(dp), 2, full.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), None, None, work.data_ptr(),
+              need, ops._stream(d))
 
 
 # ------------------------------------------------------------------------------------------------------------------ Core

@@ -295,6 +295,38 @@ def test_segment_length_medians(native_lib, cuda, sets, tiled):
     assert tuple(fit.points.shape) == (0, 38, 3) and tuple(fit.cost.shape) == (0, 6) and tuple(fit.status.shape) == (0, 6)
 
 
+# ------------------------------------------------------------------------------------------------------------------ strided poses
+def test_a_strided_pose_gives_what_its_contiguous_copy_gives(native_lib, cuda, tiled):
+    """Every wrapper that takes a pose [T, 38, 3] accepts any strides and works on the contiguous tensor: V = X[::2] gives the bytes
+    of V.contiguous(), output by output (the outputs hold NaN), and V is not changed.  A wrapper that checked V and then handed
+    V.data_ptr() and T = 5 to its kernel would read X[0:5], which the jitter of `tiled` makes another recording."""
+    from deepfly3d_amd import ops
+
+    X = tiled[:10].copy()
+    X[4, lo.leg_joints(2)[3]] = 0.0      # a missing joint in a frame the view keeps
+    X[3, lo.leg_joints(4)[1]] = np.nan   # and one in a frame it skips
+    V = _dev(cuda, X)[::2]
+    C = V.contiguous()
+    assert tuple(V.shape) == (5, 38, 3) and not V.is_contiguous() and not np.array_equal(X[::2][1:], X[1:5], equal_nan=True)
+    before = V.cpu().numpy().tobytes()
+
+    def fit(points3d):
+        r = ops.fit_legs(points3d, max_iter=2)
+        return r.points, r.cost, r.status, r.iters
+
+    calls = {"body_frame": ops.body_frame, "joint_angles per_frame": lambda p: ops.joint_angles(p, "per_frame"),
+             "joint_angles recording": lambda p: ops.joint_angles(p, "recording"), "segment_length_medians": ops.segment_length_medians,
+             "fit_legs": fit, "tip_kinematics": lambda p: ops.tip_kinematics(p, fps=100.0), "pose_outliers": ops.pose_outliers}
+    for name, call in calls.items():
+        got, want = call(V), call(C)
+        got, want = ((got,), (want,)) if isinstance(got, torch.Tensor) else (got, want)
+        assert len(got) == len(want) and len(got) >= 1, name
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert g.shape == w.shape and g.dtype == w.dtype and g.shape[0] in (5, 6), (name, i)
+            assert g.cpu().numpy().tobytes() == w.cpu().numpy().tobytes(), (name, i)
+        assert V.cpu().numpy().tobytes() == before and not V.is_contiguous(), name
+
+
 # ------------------------------------------------------------------------------------------------------------------ Core and the CLI
 def _recording(tmp_path, golden_dir):
     """(folder, result pickle): 15 frames (links to the sample's frame 0) and an earlier result holding the golden detections and cameras."""
