@@ -146,6 +146,12 @@ PROTOTYPES = {
                                       c_void_p, c_longlong, c_void_p]),
     "df3d_triangulate_trajectory": (c_int, [POINTER(c_double), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_double, c_int, c_int,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p]),
+    "df3d_heatmap3d_window_doubles": (c_int, []),
+    "df3d_heatmap3d_scores": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_double), POINTER(ctypes.c_ubyte), POINTER(c_int), c_int,
+                                      c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_void_p]),
+    "df3d_triangulate_heatmaps": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_double), POINTER(ctypes.c_ubyte), POINTER(c_int),
+                                          c_int, c_void_p, c_double, c_int, c_double, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_eval": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_colsq": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_matvec": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

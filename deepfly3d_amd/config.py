@@ -99,6 +99,19 @@ def trajectory_block_frames(frames):
     return int(min(max(lo, int(np.ceil(np.sqrt(max(int(frames), 0))))), hi))
 
 
+# ---- heat-map triangulation: the 3-D point of a joint is where the product of its views' heat-maps, sampled at
+# the point's projection, is largest.  The search starts at the plain triangulation and scores HEATMAP3D_GRID^3 points of a cube of
+# half width HEATMAP3D_HALF (mm) around it, then of the cube around the best point with the step as its half width, HEATMAP3D_LEVELS
+# times: the last step is 2 half / 8 / 4^(levels - 1), 0.0016 mm at the defaults.  A heat-map cell at or below HEATMAP3D_FLOOR (or not
+# finite) counts as the floor: a view says "no information" there, it does not veto.  The three defaults come from planted blobs on
+# the golden calibration (section 25 holds the table) and are guesses: nobody has measured them on a recording.
+HEATMAP3D_GRID = 8          # a compile-time constant of csrc/heatmap3d.hip
+HEATMAP3D_HALF = 0.4
+HEATMAP3D_LEVELS = 4
+HEATMAP3D_LEVELS_RANGE = (1, 6)
+HEATMAP3D_FLOOR = 1e-3
+
+
 # ---- leg joint angles.  Leg L = 3 side + l (l = 0, 1, 2: front, mid, hind) owns the five joints
 # 19 side + 5 l + k; its eight angles come in this order: thorax-coxa yaw, pitch and roll, coxa-trochanter pitch and roll,
 # femur-tibia pitch and roll, tibia-tarsus pitch; its four segment lengths are coxa, femur, tibia, tarsus.

@@ -485,6 +485,84 @@ class Core:
         return ops.TrajectoryResult(*(v.cpu().numpy() for v in (r.points3d, r.status, r.weight, r.error, r.iterations, r.cost, r.counts)),
                                     r.params)
 
+    # -- heat-map triangulation: a rank-0 method on the images and the calibrated cameras ----------------------------
+    def _heatmap3d_on(self, what, params, X=None, batch=16):
+        """The heatmap3d.HeatmapTriangulation on the device of every frame of the camera network, with the refusals of _robust_on and
+        of the heat-map queries.  `params`: heatmap3d_params' values.  `X`: the start points [T, 38, 3], a float64 device tensor or a
+        numpy array (save()'s latest pose); None: the plain triangulation of the camera network's detections, computed here.  Batches of
+        `batch` frames go through the file bytes, the device JPEG decode and the hourglass exactly as video._heatmap_frames sends them,
+        one search launch per batch; the heat-maps of a batch (4.3 MB per frame) never reach the host and are dropped with it."""
+        from . import distributed as dd
+        from . import heatmap3d, jpeg
+        from .inference import PREPROCESS, get_engine
+
+        if dd.current()[0] != 0:
+            raise RuntimeError(f"{what} is a rank-0 method: the camera network lives on rank 0")
+        if self.camNet is None or not self.camNet.has_calibration():
+            raise RuntimeError(f"{what} needs calibrated cameras: run calibrate_calc() first")
+        if not self.has_heatmap:
+            raise FileNotFoundError(f"{what} searches the heat-maps the network computes from the camera images, and {self.input_folder} "
+                                    "holds none (deleted with --delete-images?): heat-maps are recomputed from the images, never stored")
+        _native.require_gpu()
+        dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
+        cameras, flip, plane = heatmap3d.view_table(self.camera_ordering)
+        P = np.stack([c.P for c in self.camNet.cam_list])
+        if X is None:
+            X = ops.triangulate(P, torch.from_numpy(np.ascontiguousarray(self.camNet.points2d, dtype=np.float64)).to(dev))
+        elif not isinstance(X, torch.Tensor):
+            X = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(dev)
+        T = int(X.shape[0])
+        W, H = self.image_shape
+        engine = get_engine(dtype=self.dtype, device=dev)
+        flip_dev = torch.from_numpy(flip).to(dev)
+        half, levels, floor = params
+
+        def forward(e, luma, f):
+            return e.forward_u8(luma, f, PREPROCESS["mean"], PREPROCESS["std"], resize=PREPROCESS["resize"])
+
+        parts = []
+        for t0 in range(0, T, batch):
+            ids = range(t0, min(t0 + batch, T))
+            blobs = []
+            for i in ids:
+                for cam in cameras:
+                    with open(image_path_for(self.input_folder, int(cam), i), "rb") as f:
+                        blobs.append(f.read())
+            luma = jpeg.decode_luma(blobs, W, H, device=dev)   # [V n, H, W], image-major
+            f = flip_dev.repeat(len(ids))
+            V = len(cameras)
+            if t0 == 0 and engine.dtype != "f32":   # a reduced-precision engine proves itself on the first image's views (HourglassEngine.canary)
+                engine.canary(get_engine(dtype="f32", device=dev), lambda e: forward(e, luma[:V], f[:V]), what=f"the first views of {self.input_folder}")
+            hm = forward(engine, luma, f)
+            hm = hm.reshape(len(ids), V, *hm.shape[1:])
+            parts.append(heatmap3d.triangulate_heatmaps(P[cameras], hm, flip, plane, X[t0:t0 + len(ids)].contiguous(), self.image_shape,
+                                                        half=half, levels=levels, floor=floor))
+            luma = hm = None
+        if not parts:
+            return heatmap3d.triangulate_heatmaps(P[cameras], torch.empty((0, len(cameras), config["num_predict"], 64, 128), dtype=torch.float32, device=dev),
+                                                  flip, plane, X.contiguous(), self.image_shape, half=half, levels=levels, floor=floor)
+        cat = lambda name: torch.cat([getattr(p, name) for p in parts])   # noqa: E731
+        return heatmap3d.HeatmapTriangulation(cat("points3d"), cat("score"), cat("status"), cat("views"), cat("shift"), cat("choice"),
+                                              torch.stack([p.counts for p in parts]).sum(dim=0), parts[0].params, cat("path"))
+
+    def heatmap_triangulation(self, half=None, levels=None, floor=None):
+        """The heat-map triangulation (heatmap3d.triangulate_heatmaps) of every frame, a
+        heatmap3d.HeatmapTriangulation of numpy arrays: points3d [T, 38, 3] (in the layout of points3d_wo_procrustes), score [T, 38]
+        (NaN where nothing was searched), status [T, 38] int8 (0 fewer than two views or no start point: the plain triangulation's
+        point, 1 searched, 2 no evidence within the cube: the plain triangulation's point, 3 searched, and the best point of the first
+        level lay on a face of the cube), views [T, 38] int32 (bit v: the v-th camera that has planes, in ascending camera id), shift
+        [T, 38] mm, choice [T, 38, levels], counts [38, 4] and params (half, levels, floor, grid).  The search starts at the plain
+        triangulation of the camera network's detections and reads the heat-maps the network computes from the images, on the run's
+        own path (Core.heatmaps); they are never stored, so the images must be present.  `half` (mm), `levels` and `floor` default to
+        config.HEATMAP3D_*, guesses nobody has measured on a recording.  A rank-0 method with the refusals of the reprojection-error
+        queries."""
+        from . import heatmap3d
+
+        params = heatmap3d.heatmap3d_params(half, levels, floor)   # refused before any work
+        r = self._heatmap3d_on("heatmap_triangulation", params)
+        return heatmap3d.HeatmapTriangulation(*(v.cpu().numpy() for v in (r.points3d, r.score, r.status, r.views, r.shift, r.choice, r.counts)),
+                                              r.params, r.path.cpu().numpy())
+
     # -- the kinematic chain (DESIGN.md sections 14-17): one kinematics.PoseChain per call, never kept ----------------------------------
     def _measured_pose(self, what, fps=None, repair=None, pose=None):
         """The PoseChain of camNet.points3d on the device (triangulating first when there is none), with the refusals of the rank-0
@@ -837,6 +915,7 @@ class Core:
     def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False, behaviour_perplexity=None,
              behaviour_segments=False, behaviour_sigma=None, behaviour_grid=None, gait=False, gait_on=None, gait_off=None, repair_pose=False,
              repair_window=None, repair_threshold=None, repair_floor=None, repair_max_gap=None, treadmill=False, ball_radius=None,
+             heatmap_triangulation=False, heatmap_half=None, heatmap_levels=None, heatmap_floor=None,
              trajectory_triangulation=False, trajectory_lambda=None, trajectory_huber=None, trajectory_max_gap=None,
              robust_triangulation=False, robust_tau=None, robust_min_views=None):
         """Write df3d_result_*.pkl with the reference's schema and key order (reference :349-369).  `joint_angles=True` appends the
@@ -888,8 +967,16 @@ class Core:
         "trajectory_params" (the 38 values of lambda, then huber, then max_gap).  The stages run in the order robust, trajectory,
         repair: together with robust_triangulation the fit starts from the robust points and sees only the views the consensus kept;
         every other opt-in key of the same save is computed from the trajectory pose (repaired afterwards with repair_pose), which is
-        computed once."""
+        computed once.
+        `heatmap_triangulation=True` appends, after every other key (after the trajectory keys), the heat-map triangulation of every
+        frame (Core.heatmap_triangulation() with `heatmap_half`, mm, `heatmap_levels` and `heatmap_floor`; the defaults are guesses
+        nobody has measured on a recording; the images must be present): "points3d_heatmap" [T, 38, 3] in the layout of
+        points3d_wo_procrustes, "heatmap3d_status" [T, 38] int8, "heatmap3d_score" [T, 38], "heatmap3d_views" [T, 38] int32,
+        "heatmap3d_shift" [T, 38], "heatmap3d_counts" [38, 4] and "heatmap3d_params" (half, levels, floor, grid).  The stages run in the
+        order robust, trajectory, heat-map, repair: the search starts from the latest pose of the save, and every other opt-in key
+        of the same save is computed from the heat-map pose (repaired afterwards with repair_pose), which is computed once."""
         from . import distributed as dd
+        from . import heatmap3d
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
         # triangulates every frame itself -- every rank knows that it ran (the flag is set on all of them) and takes this branch
@@ -921,6 +1008,9 @@ class Core:
                       if trajectory_triangulation else None)   # refused before any work
         if trajectory is not None and trajectory[0].shape not in ((1,), (config["num_joints"],)):
             raise ValueError(f"trajectory_lambda must hold one value, or one per joint ({config['num_joints']})")
+        if not heatmap_triangulation and any(v is not None for v in (heatmap_half, heatmap_levels, heatmap_floor)):
+            raise ValueError("heatmap_half, heatmap_levels and heatmap_floor belong to heatmap_triangulation: they need heatmap_triangulation=True")
+        heatmap = heatmap3d.heatmap3d_params(heatmap_half, heatmap_levels, heatmap_floor) if heatmap_triangulation else None   # refused before any work
         segments = (behaviour_sigma, behaviour_grid) if behaviour_segments else None
         if segments is not None:   # refused before any work
             if behaviour_grid is not None:
@@ -930,13 +1020,14 @@ class Core:
         if self.is_primary:
             try:
                 self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
-                                   repair, treadmill, robust, trajectory)
+                                   repair, treadmill, robust, trajectory, heatmap)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
     def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False,
-                      behaviour_perplexity=None, segments=None, gait=None, repair=None, treadmill=None, robust=None, trajectory=None):
+                      behaviour_perplexity=None, segments=None, gait=None, repair=None, treadmill=None, robust=None, trajectory=None,
+                      heatmap=None):
         if behaviour_map and getattr(self, "num_images", None) is not None:   # too short for the perplexity: refused before any work
             ops.behaviour_map_points(self.num_images, behaviour_perplexity)
         result = {"points2d": np.copy(self.points2d)}
@@ -962,9 +1053,9 @@ class Core:
             result["subpixel"] = True
         # opt-in, like the two keys above: else the reference's schema
         if (joint_angles or rigid_legs or angle_spectrogram or behaviour_map or gait or repair or treadmill or robust is not None
-                or trajectory is not None):
+                or trajectory is not None or heatmap is not None):
             result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
-                                               repair, treadmill, robust, trajectory))
+                                               repair, treadmill, robust, trajectory, heatmap))
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")
@@ -980,19 +1071,24 @@ class Core:
     _ROBUST_KEYS = ("points3d_robust", "robust_cameras", "robust_status", "robust_error", "robust_counts", "points2d_robust", "robust_params")
     _TRAJECTORY_KEYS = ("points3d_trajectory", "trajectory_status", "trajectory_weight", "trajectory_error", "trajectory_iterations",
                         "trajectory_cost", "trajectory_counts", "trajectory_params")
+    _HEATMAP3D_KEYS = ("points3d_heatmap", "heatmap3d_status", "heatmap3d_score", "heatmap3d_views", "heatmap3d_shift", "heatmap3d_counts",
+                       "heatmap3d_params")
 
     def _kinematic_keys(self, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, perplexity, segments=None, gait=None, repair=None,
-                        treadmill=None, robust=None, trajectory=None):
+                        treadmill=None, robust=None, trajectory=None, heatmap=None):
         """The keys save()'s flags append, in the result's order, all read from one PoseChain of this save's triangulation.
         `segments`: None, or (sigma, grid) of the segmentation of every map.  `gait`: None, or the thresholds of the gait analysis.
         `repair`: None, or the parameters of the pose repair; the one chain is then that of the repaired pose, repaired once.
         `treadmill`: None, or the parameters of the treadmill analysis; with `gait` it takes the measured pose's states from that.
         `robust`: None, or (tau, min_views) of the consensus triangulation; the one chain is then that of the robust pose (repaired
         afterwards when `repair` is set), computed once.  `trajectory`: None, or ops.trajectory_params' values of the trajectory
-        triangulation, which runs after the consensus and before the repair; the one chain is then that of the trajectory pose."""
+        triangulation, which runs after the consensus and before the repair; the one chain is then that of the trajectory pose.
+        `heatmap`: None, or heatmap3d_params' values of the heat-map triangulation, which runs after the trajectory and before the
+        repair from the latest pose; the one chain is then that of the heat-map pose."""
         what = ("joint_angles" if joint_angles else "rigid_legs" if rigid_legs else "angle_spectrogram" if angle_spectrogram
                 else "behaviour_map" if behaviour_map else "gait" if gait is not None else "treadmill" if treadmill is not None
-                else "repair_pose" if repair is not None else "robust_triangulation" if robust is not None else "trajectory_triangulation")
+                else "repair_pose" if repair is not None else "robust_triangulation" if robust is not None else "trajectory_triangulation" if trajectory is not None
+                else "heatmap_triangulation")
         spectra = angle_spectrogram or behaviour_map
         fps, bank = self._wavelet_bank(what, None, {}) if spectra else (None, {})   # save()'s fps and frequencies are the method's defaults
         if (gait is not None or treadmill is not None) and fps is None:
@@ -1013,6 +1109,12 @@ class Core:
                                                                host(r.cost), host(r.counts),
                                                                np.append(r.params[0], [float(r.params[1]), float(r.params[2])]))))
             pose, r, kept = r.points3d, None, None
+        heatmap_keys = {}
+        if heatmap is not None:
+            r = self._heatmap3d_on(what, heatmap, X=self.camNet.points3d if pose is None else pose)
+            heatmap_keys = dict(zip(self._HEATMAP3D_KEYS, (host(r.points3d), host(r.status), host(r.score), host(r.views), host(r.shift),
+                                                           host(r.counts), np.array(r.params, dtype=np.float64))))
+            pose, r = r.points3d, None
         chains = [self._measured_pose(what, fps, repair, pose)]
         pose = None
         repair_keys = {}
@@ -1064,7 +1166,8 @@ class Core:
             S = m = None   # released before the other variant's is computed: one float64 spectrogram at a time
         if angle_spectrogram:
             keys["spectrogram_freqs"], keys["spectrogram_fps"] = bank["freqs"], fps
-        return {**{k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}, **gait_keys, **repair_keys, **robust_keys, **trajectory_keys}
+        return {**{k: keys[k] for k in self._KINEMATIC_KEYS if k in keys}, **gait_keys, **repair_keys, **robust_keys, **trajectory_keys,
+                **heatmap_keys}
 
     # -- helpers --------------------------------------------------------------------------------------
     def _correction_for(self, corrections, cam_id, img_id):

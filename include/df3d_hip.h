@@ -640,6 +640,40 @@ int df3d_triangulate_trajectory(const double* P_host, const double* pts_px_dev, 
                                 long long* counts_dev, void* work_dev, long long work_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a21 heat-map triangulation (the model is this project's own specification, stated in float64 numpy by
+ *     tests/heatmap3d_oracle.py, whose header lists every operation).  hm_dev [n, V, C, H, W] float32: the heat-maps of n frames and V
+ *     views as the network saw them; P_host [V, 3, 4] HOST float64 (pixels); flip_host [V] HOST bytes (non-zero: the network saw the
+ *     view mirrored); plane_host [V, J] HOST int32: the plane of joint j in view v, or -1.  cell_rows, cell_cols: the pixels of one
+ *     heat-map cell (image rows / H, image columns / W); log_floor = log(floor), taken by the caller: a cell is log(h) where that lies
+ *     above log_floor and h is finite, else log_floor.  The score of a 3-D point is the sum over the joint's views, ascending, of
+ *     max(Catmull-Rom sample of the cells at the point's projection, log_floor) where w > 0 and the projection lies inside the plane
+ *     (0 <= row <= H - 1, 0 <= column <= W - 1 in cells), else of log_floor.
+ * df3d_heatmap3d_scores: out_dev [n, J, M] = the score of pts_dev [n, J, M, 3].  For tests: the sampler alone.
+ * df3d_triangulate_heatmaps: from X0_dev [n, J, 3], `levels` levels of 8 x 8 x 8 points centre + (i - 3.5) step, step = 2 half / 8,
+ *     index (ix 8 + iy) 8 + iz; the best is the largest score, ties to the lowest index, and the next level searches centre = that
+ *     point, half = step.  X_dev [n, J, 3]; score_dev [n, J] (the last level's best; NaN for status 0); status_dev [n, J] int8: 0 fewer
+ *     than two views, X0 not finite or X0 = (0, 0, 0): the bits of X0; 1 searched; 2 no point of level 0 scored above the all-floor
+ *     score: X0; 3 searched, and the best point of level 0 lay on a face of its cube; views_dev [n, J] int32 (bit v: view v has a
+ *     plane); shift_dev [n, J] = |X - X0|; choice_dev [n, J, levels] int32 (the index chosen at every level, -1 where none was);
+ *     counts_dev [J, 4] int64; path_dev [n, J] int8 (may be NULL): 0 not searched, 1 the windows were staged in LDS, 2 they were not.
+ *     One workgroup per (frame, joint) stages the logarithms of the cells its search can reach in LDS when they are at most `budget`
+ *     doubles (0 <= budget <= df3d_heatmap3d_window_doubles(); 0 stages nothing); otherwise every tap reads the plane and takes the
+ *     logarithm itself.  Both routes give the same bits.
+ * 0 <= n <= 1048576 (n = 0 launches nothing and returns DF3D_OK), 1 <= V <= 8, 1 <= C <= 1024, 4 <= H, W <= 1024, 1 <= J <= 64,
+ *     0 <= M <= 1048576, 1 <= levels <= 6, half finite and > 0, log_floor finite and < 0, plane indices in [-1, C).  DF3D_EINVAL before
+ *     the device is touched, with a message, for a value outside those ranges, a null, misaligned (8 bytes for float64 / int64, 4
+ *     for float32 / int32) or overlapping buffer.  No atomics: two calls on the same input give the same bits.  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------------------------------- */
+int df3d_heatmap3d_window_doubles(void);
+int df3d_heatmap3d_scores(const float* hm_dev, int n, int V, int C, int H, int W, const double* P_host, const unsigned char* flip_host,
+                          const int* plane_host, int J, const double* pts_dev, int M, double cell_rows, double cell_cols, double log_floor,
+                          double* out_dev, void* stream);
+int df3d_triangulate_heatmaps(const float* hm_dev, int n, int V, int C, int H, int W, const double* P_host, const unsigned char* flip_host,
+                              const int* plane_host, int J, const double* X0_dev, double half, int levels, double cell_rows,
+                              double cell_cols, double log_floor, int budget, double* X_dev, double* score_dev, signed char* status_dev,
+                              int* views_dev, double* shift_dev, int* choice_dev, long long* counts_dev, signed char* path_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
