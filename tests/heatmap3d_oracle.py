@@ -5,8 +5,10 @@ projection; the point is where the sum of the logarithms (the product of the hea
 float64 operation of the kernel, in the kernel's order (the file is built with -ffp-contract=off):
 
   cell value   l = log(h) where h > floor and h is finite, else log_floor = log(floor): NaN, +-inf and negatives go to the floor.
-               (The kernel never sees `floor`: it compares log(h) > log_floor, the same decision for every float32 h, because two
-               different float32 values lie 6e-8 apart relatively and their logarithms 6e-8 absolutely.)
+               (The kernel never sees `floor`: it compares log(h) > log_floor, the same decision for every float32 h != floor, because
+               two different float32 values lie 6e-8 apart relatively and their logarithms 6e-8 absolutely.  Where `floor` is itself a
+               float32 and h equals it, the decision rests on the device's logarithm and numpy's giving the same double for that
+               one value: tests/heatmap3d_cases.py's "floor" case runs it at 2^-10, and they do.)
   projection   u = P00 x + P01 y + P02 z + P03 (left to right), v and w alike; col_px = u / w, row_px = v / w
   cells        r = row_px / cell_rows, c = col_px / cell_cols, for a flipped view c = W - col_px / cell_cols
   weights      Catmull-Rom at f = r - floor(r):  ((-f + 2) f - 1) f / 2,  ((3 f - 5) f f + 2) / 2,  ((-3 f + 4) f + 1) f / 2,
@@ -134,7 +136,9 @@ def _grid_points(centre, step):
 
 def triangulate(hm, P, flip, plane, X0, image_shape, half, levels, floor):
     """dict of points [n, J, 3], score, status (int8), views (int32), shift, choice [n, J, levels] (int32), counts [J, 4] (int64) and
-    gap [n, J, levels]: the best score minus the second best of every level searched (+inf elsewhere)."""
+    gap [n, J, levels]: the best score minus the second best of every level searched (+inf elsewhere); ties [n, J, levels] (int32): how
+    many of the level's 512 scores equal the best (0 elsewhere); gap_next: the best score minus the largest score strictly below it
+    (+inf elsewhere, and where all 512 are equal)."""
     n, V, C, H, W = hm.shape
     J = plane.shape[1]
     cell, logs = cell_size(image_shape, H, W), Logs(hm, floor)
@@ -146,6 +150,8 @@ def triangulate(hm, P, flip, plane, X0, image_shape, half, levels, floor):
     shift = np.zeros((n, J), dtype=np.float64)
     choice = np.full((n, J, levels), -1, dtype=np.int32)
     gap = np.full((n, J, levels), np.inf)
+    gap_next = np.full((n, J, levels), np.inf)
+    ties = np.zeros((n, J, levels), dtype=np.int32)
     for t in range(n):
         for j in range(J):
             vs = [v for v in range(V) if plane[v, j] >= 0]
@@ -172,6 +178,10 @@ def triangulate(hm, P, flip, plane, X0, image_shape, half, levels, floor):
                     status[t, j] = 3 if ((i == 0) | (i == GRID - 1)).any() else 1
                 top = np.sort(s)[-2:]
                 gap[t, j, level] = top[1] - top[0]
+                ties[t, j, level] = (s == s[best]).sum()
+                below = s[s < s[best]]
+                if below.size:
+                    gap_next[t, j, level] = s[best] - below.max()
                 choice[t, j, level] = best
                 centre, h, score[t, j] = pts[best].copy(), step, s[best]
             if status[t, j] != 2:
@@ -179,7 +189,64 @@ def triangulate(hm, P, flip, plane, X0, image_shape, half, levels, floor):
                 d = centre - x0
                 shift[t, j] = np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
     counts = np.stack([(status == k).sum(axis=0) for k in range(4)], axis=1).astype(np.int64)
-    return dict(points=X, score=score, status=status, views=views, shift=shift, choice=choice, counts=counts, gap=gap)
+    return dict(points=X, score=score, status=status, views=views, shift=shift, choice=choice, counts=counts, gap=gap, ties=ties,
+                gap_next=gap_next)
+
+
+REACH = 1.25   # the cube a search can reach, in half widths of its first level
+
+
+def windows(P, flip, plane, X0, image_shape, H, W, half):
+    """(used [n, J] int64, win [n, J, V, 4] int64) of the window rule: per view of a searched (frame, joint) the cells (r0, r1, c0, c1)
+    the kernel would stage -- the bounding box of the 8 corners X0 +- 1.25 half in cells, floor(min) - 1 .. floor(max) + 2, clamped to the
+    plane; the whole plane where some but not all corners have w <= 0 or a corner's w, r or c is not finite; (0, -1, 0, -1), no window,
+    where all 8 have w <= 0, and for a view without a plane -- and the number of cells of the joint's windows together, 0 for a
+    (frame, joint) that is not searched."""
+    n, J = X0.shape[:2]
+    V = len(P)
+    cell = cell_size(image_shape, H, W)
+    used = np.zeros((n, J), dtype=np.int64)
+    win = np.tile(np.array([0, -1, 0, -1], dtype=np.int64), (n, J, V, 1))
+    e = float(half) * REACH
+    sign = np.array([[1.0 if k & 4 else -1.0, 1.0 if k & 2 else -1.0, 1.0 if k & 1 else -1.0] for k in range(8)])
+    for t in range(n):
+        for j in range(J):
+            vs = [v for v in range(V) if plane[v, j] >= 0]
+            x0 = X0[t, j]
+            if len(vs) < 2 or not np.isfinite(x0).all() or not x0.any():
+                continue
+            corners = x0[None, :] + sign * e
+            for v in vs:
+                row_px, col_px, w = project(P[v], corners)
+                r, c = to_cells(row_px, col_px, bool(flip[v]), cell, W)
+                finite = np.isfinite(w) & np.isfinite(r) & np.isfinite(c)
+                behind = int((finite & ~(w > 0.0)).sum())
+                if finite.all() and behind == 8:
+                    continue
+                if not finite.all() or behind > 0:
+                    box = (0, H - 1, 0, W - 1)
+                else:
+                    box = (int(min(max(np.floor(r.min()) - 1.0, 0.0), H - 1.0)), int(min(max(np.floor(r.max()) + 2.0, 0.0), H - 1.0)),
+                           int(min(max(np.floor(c.min()) - 1.0, 0.0), W - 1.0)), int(min(max(np.floor(c.max()) + 2.0, 0.0), W - 1.0)))
+                win[t, j, v] = box
+                used[t, j] += (box[1] - box[0] + 1) * (box[3] - box[2] + 1)
+    return used, win
+
+
+def taps(hm_plane, P, flip, X, cell):
+    """What the sampler reads for the points X [M, 3] in one view: (ok [M] bool: the view informs, f [M, 2]: the fractions
+    (r - floor(r), c - floor(c)), cells [M, 16] float32: the plane's values at the 16 taps, rows outside, in the sampler's order)."""
+    H, W = hm_plane.shape
+    row_px, col_px, w = project(P, X)
+    r, c = to_cells(row_px, col_px, flip, cell, W)
+    with np.errstate(invalid="ignore"):
+        ok = (w > 0.0) & (r >= 0.0) & (r <= H - 1.0) & (c >= 0.0) & (c <= W - 1.0)
+    r, c = np.where(ok, r, 0.0), np.where(ok, c, 0.0)
+    fr, fc = np.floor(r), np.floor(c)
+    ir, ic = fr.astype(np.int64), fc.astype(np.int64)
+    rows = np.clip(ir[:, None] - 1 + np.arange(4)[None, :], 0, H - 1)
+    cols = np.clip(ic[:, None] - 1 + np.arange(4)[None, :], 0, W - 1)
+    return ok, np.stack([r - fr, c - fc], axis=1), hm_plane[rows[:, :, None], cols[:, None, :]].reshape(len(X), 16)
 
 
 # ---- planted inputs -----------------------------------------------------------------------------------------------------------------

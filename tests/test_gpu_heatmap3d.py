@@ -39,7 +39,7 @@ def _same_bits(a, b):
     return torch.equal(a.view(torch.int64), b.view(torch.int64)) if a.dtype == torch.float64 else torch.equal(a, b)
 
 
-FIELDS = ("points3d", "score", "status", "views", "shift", "choice", "counts")
+FIELDS = hc.FIELDS
 
 
 # ---------------------------------------------------------------------------------------------------------------------- the sampler
@@ -80,30 +80,7 @@ CASES = {"fly": ("fly", (2,), {}), "fly, noise 0.02": ("fly", (2, 0.02), {}), "s
 
 def _compare(name, r, ref, case):
     got = {f: getattr(r, f).cpu().numpy() for f in FIELDS}
-    searched = ref["status"] % 2 == 1
-    ok = hc.comparable(ref)
-    skipped = int((searched & ~ok).sum())
-    print(f"{name}: {int(searched.sum())} searched, {skipped} under the gap of {hc.GAP:g} (smallest gap {ref['gap'].min():.2e}), statuses "
-          f"{np.bincount(ref['status'].ravel(), minlength=4).tolist()}, |score| {np.nanmax(np.abs(got['score'] - ref['score'])):.2e}")
-    assert skipped <= hc.MAX_SKIPPED * ref["status"].size
-    assert got["status"].dtype == np.int8 and got["views"].dtype == np.int32 and got["choice"].dtype == np.int32 and got["counts"].dtype == np.int64
-    assert np.array_equal(got["views"], ref["views"])
-    assert np.array_equal(got["status"][ok], ref["status"][ok]) and np.array_equal(got["choice"][ok], ref["choice"][ok])
-    assert np.array_equal(got["counts"], np.stack([(got["status"] == k).sum(axis=0) for k in range(4)], axis=1))
-    if not skipped:
-        assert np.array_equal(got["counts"], ref["counts"])
-    moved = ok & searched
-    assert np.abs(got["points3d"][moved] - ref["points"][moved]).max(initial=0.0) <= POINT_BAR
-    assert np.abs(got["shift"][moved] - ref["shift"][moved]).max(initial=0.0) <= POINT_BAR
-    assert np.abs(got["score"][moved] - ref["score"][moved]).max(initial=0.0) <= SCORE_BAR
-    kept = ~searched
-    assert got["points3d"][kept].tobytes() == case["X0"][kept].tobytes() and not got["shift"][kept].any()
-    assert np.array_equal(np.isnan(got["score"]), ref["status"] == 0)
-    two = ref["status"] == 2
-    assert np.abs(got["score"][two] - ref["score"][two]).max(initial=0.0) <= SCORE_BAR and (got["choice"][kept] == -1).all()
-    path = r.path.cpu().numpy()
-    assert np.array_equal(path == 0, ref["status"] == 0) and np.isin(path, (0, 1, 2)).all()
-    return path
+    return hc.compare(name, got, r.path.cpu().numpy(), ref, case["X0"], hc.comparable(ref), POINT_BAR, SCORE_BAR, what=f"under the gap of {hc.GAP:g}")
 
 
 @pytest.mark.parametrize("name", list(CASES))
