@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("DF3D_LIB") or os.path.join(_HERE, "libdf3d_hip.so")  
 
 ABI_VERSION = 610  # DF3D_ABI_VERSION of include/df3d_hip.h: the revision these prototypes were written against
 LSMR_AUTO, LSMR_BARRIERS, LSMR_LAUNCHES, LSMR_LOCAL, LSMR_ELEVEN = 0, 1, 2, 3, 11   # DF3D_LSMR_* of include/df3d_hip.h
+BA_LOSSES = ("linear", "soft_l1", "huber", "cauchy", "arctan")   # DF3D_BA_LOSS_* of include/df3d_hip.h = the index here
 DF3D_EINVAL = -1  # include/df3d_hip.h
 DF3D_ENOSPC = -5
 DF3D_EIO = -6
@@ -187,6 +188,18 @@ PROTOTYPES = {
     "df3d_ba_trf_linearize": (
         c_int,
         [POINTER(BAProblem), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    ),
+    "df3d_ba_eval_robust": (c_int, [POINTER(BAProblem), c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_ba_robust_cost": (c_int, [c_void_p, c_size_t, c_int, c_double, POINTER(c_double), c_void_p, c_void_p]),
+    "df3d_ba_trf_linearize_robust": (
+        c_int,
+        [POINTER(BAProblem), c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+         c_void_p, c_void_p],
+    ),
+    "df3d_ba_trf_trial_robust": (
+        c_int,
+        [POINTER(BAProblem), c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_double), c_void_p],
     ),
     "df3d_hg_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),
     "df3d_hg_destroy": (None, [c_void_p]),

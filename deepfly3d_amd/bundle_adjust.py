@@ -176,6 +176,19 @@ class _Dev:
             "df3d_ba_eval",
         )
 
+    def eval_robust(self, x, loss, f_scale, f, Jc=None, Jp=None, f_true=None, w=None):
+        """df3d_ba_eval under a robust loss (`loss`: the code, _native.BA_LOSSES' index): f <- f w / s, the Jacobian rows times s; optionally the
+        unscaled residuals and the weights."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        _native.check(self.lib.df3d_ba_eval_robust(ctypes.byref(self.p.c), x.data_ptr(), loss, f_scale, ptr(f_true), f.data_ptr(), ptr(Jc), ptr(Jp), ptr(w),
+                                                   self.stream()), "df3d_ba_eval_robust")
+
+    def robust_cost(self, f, loss, f_scale):
+        """1/2 C^2 sum rho((f / C)^2) over the unscaled residuals f, in dot's summation order."""
+        _native.check(self.lib.df3d_ba_robust_cost(f.data_ptr(), f.numel(), loss, f_scale, ctypes.byref(self._res), self.scratch.data_ptr(), self.stream()),
+                      "df3d_ba_robust_cost")
+        return self._res.value
+
     def colsq(self, Jc, Jp, out):
         _native.check(self.lib.df3d_ba_colsq(ctypes.byref(self.p.c), Jc.data_ptr(), Jp.data_ptr(), out.data_ptr(), self.scratch.data_ptr(), self.stream()), "df3d_ba_colsq")
         return out
@@ -220,9 +233,12 @@ class _HostScalars:
     """solve_trf's back end whose scalars come back to the host in groups: every step is one of _Dev's vector calls, seven read-backs per
     outer iteration and one per trial step."""
 
-    def __init__(self, dv, prob, lsmr_form):
-        self.dv, self.prob, self.form = dv, prob, lsmr_form
+    def __init__(self, dv, prob, lsmr_form, loss=0, f_scale=1.0):
+        """loss: the code of a robust loss (_native.BA_LOSSES' index), 0 = the plain sum of squares -- which takes the calls it always took
+        and allocates nothing for the others."""
+        self.dv, self.prob, self.form, self.loss, self.f_scale = dv, prob, lsmr_form, loss, f_scale
         m, n, nobs = prob.m, prob.n, prob.nobs
+        self.w = dv.new(m) if loss else None     # rho' of the residuals at the last linearisation
         self.f, self.f_new, self.Js0, self.Js1, self.tmp_m = (dv.new(m) for _ in range(5))
         self.Jc, self.Jp = dv.new(12 * nobs), dv.new(6 * nobs)
         self.g, self.g_h, self.gn_h, self.scale, self.scale_inv, self.tmp_n, self.step, self.s0, self.s1, self.step_h, self.x_new = (dv.new(n) for _ in range(11))
@@ -231,7 +247,13 @@ class _HostScalars:
     def linearize(self, x, f, first):
         """J, g = J^T f and the column scaling at x (and f, on the first call, which returns |f|^2 and |x / scale|^2)."""
         dv, Jc, Jp = self.dv, self.Jc, self.Jp
-        if first:
+        if self.loss:
+            # robust: f <- f w / s and J's rows times s, whatever f held (after an accepted step: the unscaled trial residuals); the first
+            # call returns the robust cost of the unscaled residuals in place of |f|^2
+            dv.eval_robust(x, self.loss, self.f_scale, f, Jc, Jp, f_true=self.f_new if first else None, w=self.w)
+            if first:
+                ff = dv.robust_cost(self.f_new, self.loss, self.f_scale)
+        elif first:
             dv.eval(x, f, Jc, Jp)
             ff = dv.dot(f, f)
         else:
@@ -280,13 +302,17 @@ class _HostScalars:
         return g_norm, np.array([[b00, b01], [b01, b11]]), np.array([gs0, gs1]), info
 
     def trial(self, p_S, x, x_new, f_new):
-        """x_new = x + D (p0 s0 + p1 s1), f_new = f(x_new); returns |J_h step|^2, step_h . g_h, |step_h|^2, |f_new|^2, |step|^2, |x|^2."""
+        """x_new = x + D (p0 s0 + p1 s1), f_new = f(x_new); returns |J_h step|^2, step_h . g_h, |step_h|^2, |f_new|^2, |step|^2, |x|^2
+        (robust: the cost of the unscaled f_new in place of |f_new|^2)."""
         dv, step_h, tmp_m, step = self.dv, self.step_h, self.tmp_m, self.step
         dv.axpby(float(p_S[0]), self.s0, float(p_S[1]), self.s1, step_h)
         dv.axpby(float(p_S[0]), self.Js0, float(p_S[1]), self.Js1, tmp_m)   # J_h step = p0 J_h s0 + p1 J_h s1
         dv.mul(self.scale, step_h, step)
         dv.axpby(1.0, x, 1.0, step, x_new)
         dv.eval(x_new, f_new, None, None)
+        if self.loss:
+            jp2, sg, sh2, st2, xx = dv.dots((tmp_m, tmp_m), (step_h, self.g_h), (step_h, step_h), (step, step), (x, x))
+            return [jp2, sg, sh2, dv.robust_cost(f_new, self.loss, self.f_scale), st2, xx]
         return dv.dots((tmp_m, tmp_m), (step_h, self.g_h), (step_h, step_h), (f_new, f_new), (step, step), (x, x))
 
 
@@ -294,14 +320,24 @@ class _DeviceScalars(_HostScalars):
     """solve_trf's back end whose scalars stay on the device (df3d_ba_trf_* of include/df3d_hip.h): one read-back per outer iteration and
     one per trial step; the LSMR damping is read from device memory.  Same buffers, same arithmetic."""
 
-    def __init__(self, dv, prob, lsmr_form):
-        super().__init__(dv, prob, lsmr_form)
+    def __init__(self, dv, prob, lsmr_form, loss=0, f_scale=1.0):
+        super().__init__(dv, prob, lsmr_form, loss, f_scale)
         self.P = ctypes.byref(prob.c)
         self.sub = (ctypes.c_double * 19)()
         self.tri = (ctypes.c_double * 6)()
 
     def linearize(self, x, f, first):
         dv = self.dv
+        if self.loss:
+            _native.check(dv.lib.df3d_ba_trf_linearize_robust(self.P, x.data_ptr(), self.loss, self.f_scale, self.f_new.data_ptr() if first else None, f.data_ptr(),
+                                                              self.Jc.data_ptr(), self.Jp.data_ptr(), self.w.data_ptr(), self.g.data_ptr(), self.tmp_n.data_ptr(),
+                                                              self.scale_inv.data_ptr(), self.scale.data_ptr(), 1 if first else 0, dv.scratch.data_ptr(), dv.stream()),
+                          "df3d_ba_trf_linearize_robust")
+            if first:
+                cost = dv.robust_cost(self.f_new, self.loss, self.f_scale)
+                dv.mul(x, self.scale_inv, self.tmp_n)
+                return cost, dv.dot(self.tmp_n, self.tmp_n)
+            return None
         _native.check(dv.lib.df3d_ba_trf_linearize(self.P, x.data_ptr(), f.data_ptr(), 1 if first else 0, self.Jc.data_ptr(), self.Jp.data_ptr(), self.g.data_ptr(),
                                                    self.tmp_n.data_ptr(), self.scale_inv.data_ptr(), self.scale.data_ptr(), 1 if first else 0, dv.scratch.data_ptr(),
                                                    dv.stream()), "df3d_ba_trf_linearize")
@@ -320,6 +356,12 @@ class _DeviceScalars(_HostScalars):
 
     def trial(self, p_S, x, x_new, f_new):
         dv = self.dv
+        if self.loss:
+            _native.check(dv.lib.df3d_ba_trf_trial_robust(self.P, self.loss, self.f_scale, float(p_S[0]), float(p_S[1]), self.s0.data_ptr(), self.s1.data_ptr(),
+                                                          self.Js0.data_ptr(), self.Js1.data_ptr(), self.scale.data_ptr(), x.data_ptr(), self.g_h.data_ptr(),
+                                                          self.step_h.data_ptr(), self.tmp_m.data_ptr(), self.step.data_ptr(), x_new.data_ptr(), f_new.data_ptr(),
+                                                          dv.scratch.data_ptr(), self.tri, dv.stream()), "df3d_ba_trf_trial_robust")
+            return list(self.tri)
         _native.check(dv.lib.df3d_ba_trf_trial(self.P, float(p_S[0]), float(p_S[1]), self.s0.data_ptr(), self.s1.data_ptr(), self.Js0.data_ptr(), self.Js1.data_ptr(),
                                                self.scale.data_ptr(), x.data_ptr(), self.g_h.data_ptr(), self.step_h.data_ptr(), self.tmp_m.data_ptr(),
                                                self.step.data_ptr(), x_new.data_ptr(), f_new.data_ptr(), dv.scratch.data_ptr(), self.tri, dv.stream()),
@@ -327,7 +369,17 @@ class _DeviceScalars(_HostScalars):
         return list(self.tri)
 
 
-def solve_trf(prob, x0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, lsmr_form=_native.LSMR_AUTO, device_scalars=None):
+def loss_code(loss, f_scale):
+    """(code, f_scale) of a loss name for the C ABI; raises ValueError for an unknown name or an f_scale that is not positive and finite."""
+    if loss not in _native.BA_LOSSES:
+        raise ValueError("loss must be one of %s, not %r" % (", ".join(_native.BA_LOSSES), loss))
+    f_scale = float(f_scale)
+    if not (f_scale > 0 and np.isfinite(f_scale)):
+        raise ValueError("f_scale must be positive and finite, not %r" % (f_scale,))
+    return _native.BA_LOSSES.index(loss), f_scale
+
+
+def solve_trf(prob, x0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, lsmr_form=_native.LSMR_AUTO, device_scalars=None, loss="linear", f_scale=1.0):
     """Trust-region-reflective least squares without bounds, LSMR subspace step, x_scale='jac'.
     x0: device float64 [n].  Returns dict(x=device tensor, cost, nfev, njev, status, lsmr_iters, optimality).
     lsmr_form: DF3D_LSMR_* of include/df3d_hip.h (AUTO: one persistent data-local kernel per inner solve; LAUNCHES when the adjustment
@@ -335,15 +387,21 @@ def solve_trf(prob, x0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, lsmr_for
     device_scalars (default True; DF3D_TRF_HOST_SCALARS=1 in the environment turns it off): the driver's scalars stay on the device -- one
     read-back per outer iteration and one per trial step (df3d_ba_trf_* of include/df3d_hip.h) instead of seven and one; the same
     arithmetic, the same iterates (tests/test_gpu_ba.py compares the two).  Either way the host keeps the trust radius, the 2x2
-    subproblem and the acceptance logic -- everything that decides what is enqueued next."""
+    subproblem and the acceptance logic -- everything that decides what is enqueued next.
+    loss, f_scale: scipy's least_squares(loss=, f_scale=) -- 'soft_l1' | 'huber' | 'cauchy' | 'arctan' applied per scalar residual
+    (soft_l1 is the one to use: huber and cauchy can stall at a perturbed start).  The evaluation then hands the driver
+    J's rows times s and f w / s, and the actual reduction compares the robust cost 1/2 C^2 sum rho of the unscaled trial residuals;
+    the result gains `loss`, `f_scale`, `weights` (device [nobs]: the smaller rho' of an observation's two components at the result) and
+    `cost` is the robust cost.  'linear' (the default) is the plain sum of squares: the calls, buffers and bits it always had."""
+    code, f_scale = loss_code(loss, f_scale)
     if device_scalars is None:
         device_scalars = os.environ.get("DF3D_TRF_HOST_SCALARS", "0") in ("", "0")
     dv = _Dev(prob)
-    be = (_DeviceScalars if device_scalars else _HostScalars)(dv, prob, lsmr_form)
+    be = (_DeviceScalars if device_scalars else _HostScalars)(dv, prob, lsmr_form, code, f_scale)
     x, x_new, f, f_new = x0.clone(), be.x_new, be.f, be.f_new
     ff0, d2 = be.linearize(x, f, True)
     nfev = njev = 1
-    cost = 0.5 * ff0
+    cost = ff0 if code else 0.5 * ff0        # (a robust back end returns the cost itself where the linear one returns |f|^2)
     Delta = float(np.sqrt(d2))
     if Delta == 0:
         Delta = 1.0
@@ -373,7 +431,7 @@ def solve_trf(prob, x0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, lsmr_for
             nfev += 1
             predicted_reduction = -(0.5 * jp2 + sg)
             step_h_norm = float(np.sqrt(sh2))
-            cost_new = 0.5 * ff
+            cost_new = ff if code else 0.5 * ff
             if not np.isfinite(cost_new):
                 Delta = 0.25 * step_h_norm
                 continue
@@ -409,7 +467,10 @@ def solve_trf(prob, x0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, lsmr_for
             njev += 1
     if status is None:
         status = 0
-    return dict(x=x, cost=cost, nfev=nfev, njev=njev, status=status, lsmr_iters=lsmr_iters, optimality=g_norm, lsmr_fallbacks=lsmr_fallbacks)
+    res = dict(x=x, cost=cost, nfev=nfev, njev=njev, status=status, lsmr_iters=lsmr_iters, optimality=g_norm, lsmr_fallbacks=lsmr_fallbacks)
+    if code:
+        res.update(loss=loss, f_scale=f_scale, weights=be.w.view(-1, 2).min(dim=1).values)
+    return res
 
 
 def reprojection_error(points2d_px, points3d, R, tvec, intr, device="cuda:0"):
@@ -441,8 +502,11 @@ def reprojection_error(points2d_px, points3d, R, tvec, intr, device="cuda:0"):
 _side_streams = {}
 
 
-def bundle_adjust(points2d_px, R, tvec, intr, device="cuda:0", return_info=False, concurrent=False):
+def bundle_adjust(points2d_px, R, tvec, intr, device="cuda:0", return_info=False, concurrent=False, loss="linear", f_scale=1.0):
     """See _bundle_adjust; runs with `device` as the current HIP device (kernels launch on the current device).
+    loss, f_scale: solve_trf's (a robust loss on the reprojection residuals, in pixels; 'linear' = the reference's sum of squares).  With a
+    robust loss the returned info also holds `obs_weight` [ncam, T, J] float64 on the host: the weight the adjustment gave each detection
+    (1 = believed in full, NaN = not part of the adjustment).
     concurrent=True: the adjustment shares the device with other work (a window's re-calibration beside the frame pipeline): its inner
     solves take the launch-based LSMR form, which needs no co-resident workgroups; the default -- the CLI's one adjustment per folder
     (reference df3d/core.py:249) -- takes one persistent kernel per solve.  When the
@@ -453,18 +517,18 @@ def bundle_adjust(points2d_px, R, tvec, intr, device="cuda:0", return_info=False
     with torch.cuda.device(dev):
         cur = torch.cuda.current_stream(dev)
         if cur.cuda_stream != 0:
-            return _bundle_adjust(points2d_px, R, tvec, intr, device, return_info, concurrent)
+            return _bundle_adjust(points2d_px, R, tvec, intr, device, return_info, concurrent, loss, f_scale)
         side = _side_streams.get(str(dev))
         if side is None:
             side = _side_streams[str(dev)] = torch.cuda.Stream(device=dev)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            out = _bundle_adjust(points2d_px, R, tvec, intr, device, return_info, concurrent)
+            out = _bundle_adjust(points2d_px, R, tvec, intr, device, return_info, concurrent, loss, f_scale)
         cur.wait_stream(side)
         return out
 
 
-def _bundle_adjust(points2d_px, R, tvec, intr, device, return_info, concurrent=False):
+def _bundle_adjust(points2d_px, R, tvec, intr, device, return_info, concurrent=False, loss="linear", f_scale=1.0):
     """points2d_px (ncam, T, J, 2) float64 (row_px, col_px); R (ncam,3,3), tvec (ncam,3), intr (ncam,3,3).
     Returns adjusted (R, tvec) as float64 numpy arrays (+ solver info)."""
     _native.require_gpu()
@@ -480,7 +544,14 @@ def _bundle_adjust(points2d_px, R, tvec, intr, device, return_info, concurrent=F
     X0 = ops.triangulate(P, px_dev)
     cams = np.concatenate([np.stack([_rotvec_from_matrix(R[c]) for c in range(ncam)]), tvec], axis=1).ravel()
     x0 = torch.cat([torch.from_numpy(cams).to(dev), X0.reshape(-1, 3)[prob.ok_dev].reshape(-1)])
-    res = solve_trf(prob, x0, lsmr_form=_native.LSMR_LAUNCHES if concurrent else _native.LSMR_AUTO)
+    res = solve_trf(prob, x0, lsmr_form=_native.LSMR_LAUNCHES if concurrent else _native.LSMR_AUTO, loss=loss, f_scale=f_scale)
+    if "weights" in res:
+        # the weights back on the detections' grid: observation i is (camera cam_idx[i], frame and joint of point pt_idx[i])
+        T, J = px_dev.shape[1:3]
+        grid = torch.full((ncam, T * J), float("nan"), dtype=torch.float64, device=dev)
+        tj = torch.nonzero(prob.ok_dev).reshape(-1)[prob.t["pt_idx"].long()]
+        grid[prob.t["cam_idx"].long(), tj] = res["weights"]
+        res["obs_weight"] = grid.reshape(ncam, T, J).cpu().numpy()
     cams_new = res["x"][: 6 * ncam].cpu().numpy().reshape(ncam, 6)
     R_new = np.stack([_matrix_from_rotvec(cams_new[c, :3]) for c in range(ncam)])
     t_new = cams_new[:, 3:].copy()

@@ -139,9 +139,11 @@ class CameraNetwork:
         self.points3d = ops.triangulate(P, px).cpu().numpy()
         return self.points3d
 
-    def bundle_adjust(self, update_intrinsic=False, update_distort=False):
+    def bundle_adjust(self, update_intrinsic=False, update_distort=False, loss="linear", f_scale=1.0):
         """Adjust camera extrinsics (+ internal 3-D points); intrinsics / distortion stay frozen -- the only
-        configuration the reference uses (core.py:249)."""
+        configuration the reference uses (core.py:249).  loss, f_scale: bundle_adjust.solve_trf's robust loss on the reprojection
+        residuals, in pixels; ba_info then also holds `obs_weight` [7, T', 38] (the weight of every detection of
+        the frames the adjustment used, NaN where it had none) and `frame_stride` (those frames are 0, stride, 2 stride, ...)."""
         if update_intrinsic or update_distort:
             raise NotImplementedError("only update_intrinsic=False, update_distort=False is supported (the reference's call)")
         R, t, K = self._stack()
@@ -150,10 +152,12 @@ class CameraNetwork:
         # golden vector, every 1 000-frame window -- use all frames.  Longer ones are cut to an evenly strided,
         # deterministic subset, which also bounds the Jacobian (12 * nobs doubles) instead of growing with T.
         pts = self._ba_subset()
-        R_new, t_new, info = _ba.bundle_adjust(pts, R, t, K, device=self._device(), return_info=True)
+        R_new, t_new, info = _ba.bundle_adjust(pts, R, t, K, device=self._device(), return_info=True, loss=loss, f_scale=f_scale)
+        if "obs_weight" in info:
+            info["frame_stride"] = 1 if pts is self._points2d else -(-self._points2d.shape[1] // int(config["ba_max_images"]))
         for c, cam in enumerate(self.cam_list):
             cam.R, cam.tvec = R_new[c], t_new[c]
-        self.ba_info = {k: v for k, v in info.items() if k != "x"}
+        self.ba_info = {k: v for k, v in info.items() if k not in ("x", "weights")}
         self.triangulate()
         return self.ba_info
 

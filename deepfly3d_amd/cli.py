@@ -172,6 +172,16 @@ def parse_cli_args(argv=None):
                         "(default 20, a guess)")
     p.add_argument("--robust-min-views", dest="robust_min_views", type=int, default=None, metavar="N",
                    help="With --robust-triangulation: the fewest cameras a subset may hold, 2 to 8 (default 2)")
+    p.add_argument("--ba-loss", dest="ba_loss", choices=("linear", "soft_l1", "huber", "cauchy", "arctan"), default=None,
+                   help="The loss of the calibration's bundle adjustment on the reprojection residuals, with the meaning of scipy's "
+                        "least_squares(loss=): linear (the default) is the plain sum of squares, which believes every detection; with the "
+                        "others a wrong detection stops pulling the cameras.  soft_l1 is the one to use: huber and cauchy can stall at the "
+                        "start.  Appends, after every other key, ba_weight [7, T, 38] (1: the detection counted in full, NaN: it was not "
+                        "in the adjustment), ba_counts [7, 3] and ba_params to the result.  On a joint that two cameras see, a wrong "
+                        "detection cannot be told from a wrong point: the loss only bounds its pull")
+    p.add_argument("--ba-f-scale", dest="ba_f_scale", type=float, default=None, metavar="PX",
+                   help="With --ba-loss: the residual, in pixels, up to which a detection counts in full (default 4: about two standard "
+                        "deviations of a 7.5 px heat-map cell's quantisation -- a guess that nobody has measured on a recording)")
     p.add_argument("--trajectory-triangulation", dest="trajectory_triangulation", action="store_true",
                    help="Fit every joint's 3-D trajectory to the 2-D detections of the whole recording: per joint the points minimise a Huber "
                         "loss (--trajectory-huber pixels) of every camera's reprojection error plus --trajectory-lambda times the squared "
@@ -241,6 +251,11 @@ def parse_cli_args(argv=None):
             ops.trajectory_params(args.trajectory_lambda, args.trajectory_huber, args.trajectory_max_gap)
         except ValueError as e:
             p.error(f"--trajectory-lambda, --trajectory-huber and --trajectory-max-gap: {e}")
+    if args.ba_f_scale is not None:
+        if args.ba_loss in (None, "linear"):
+            p.error("--ba-f-scale sets a parameter of --ba-loss: it needs --ba-loss with a loss other than linear")
+        if not (args.ba_f_scale > 0 and args.ba_f_scale != float("inf")):
+            p.error("--ba-f-scale must be positive and finite")
     for name in ("tau", "min_views"):
         if getattr(args, "robust_" + name) is not None and not args.robust_triangulation:
             p.error(f"--robust-{name.replace('_', '-')} sets a parameter of --robust-triangulation: it needs --robust-triangulation")
@@ -408,7 +423,7 @@ def run(args):
     # the heat-map video needs the images and the weights only: without an earlier result to reopen there is no pose to calibrate or save
     pose_free = args.skip_estimation and core.points2d is None and video_heatmap and not args.video_2d and not args.video_3d
     if not pose_free:
-        core.calibrate_calc(0, core.max_img_id)
+        core.calibrate_calc(0, core.max_img_id, loss=getattr(args, "ba_loss", None), f_scale=getattr(args, "ba_f_scale", None))
         if auto and getattr(args, "correct_only_flagged", False):
             core.auto_correct(flagged_only=True)
         elif auto:

@@ -70,6 +70,15 @@ ROBUST_TAU = np.full(38, 20.0, dtype=np.float64)
 ROBUST_MIN_VIEWS = 2
 ROBUST_MIN_VIEWS_RANGE = (2, 8)
 
+# ---- robust-loss bundle adjustment: calibrate_calc's loss on the reprojection residuals, with scipy's meaning of
+# least_squares(loss=, f_scale=).  'linear' is the reference's plain sum of squares; of the others 'soft_l1' is the one to use (huber and
+# cauchy can stall at a perturbed start).  BA_F_SCALE, pixels, is where a residual stops counting in full: 4 px is about two standard
+# deviations of the quantisation of a 7.5 px heat-map cell (7.5 / sqrt(12)) -- a guess that nobody has measured on a recording.  It is
+# used only when a robust loss is asked for.
+BA_LOSSES = ("linear", "soft_l1", "huber", "cauchy", "arctan")
+BA_LOSS = "linear"
+BA_F_SCALE = 4.0
+
 # ---- trajectory triangulation: per joint, the 3-D points of a whole recording minimise the Huber loss
 # (TRAJECTORY_HUBER pixels) of every view's reprojection error plus TRAJECTORY_LAMBDA[j] (px^2 / mm^2) times the squared second
 # differences of the trajectory.  The two defaults come from a sweep of tests/trajectory_oracle.py on planted trajectories (section 24

@@ -23,6 +23,8 @@ import numpy as np
 import torch
 
 from . import _native, logger, ops
+from . import bundle_adjust as _ba
+from . import config as config_mod
 from .camera_network import CameraNetwork
 from .config import IGNORE_JOINT_ID, SPECTROGRAM_FPS, camera_is_flipped, camera_see_joint, config, heatmap_planes, load_calibration, plane_color
 from .db import PoseDB
@@ -814,23 +816,67 @@ class Core:
             raise RuntimeError("smooth_points2d needs the camera network: run calibrate_calc() first")
         return self.camNet.smooth_points2d(refresh=refresh)[cam_id]
 
-    def calibrate_calc(self, min_img_id, max_img_id):
+    def calibrate_calc(self, min_img_id, max_img_id, loss=None, f_scale=None):
         """Bundle adjustment from the shipped initial calibration (reference :229-250; like the reference the
         image-id range is accepted and unused).  Multi-GPU: rank 0 solves, EVERY rank calls this and leaves it together --
-        a failure on rank 0 (the solver, the disk) is raised on all ranks (`distributed.agree`)."""
+        a failure on rank 0 (the solver, the disk) is raised on all ranks (`distributed.agree`).
+        `loss`, `f_scale` (defaults config.BA_LOSS = 'linear', config.BA_F_SCALE pixels): a robust loss on the reprojection residuals,
+        scipy's least_squares(loss=, f_scale=) per scalar residual -- 'soft_l1' is the one to use; a wrong
+        detection then stops pulling the cameras.  With a loss other than 'linear', save() appends, after every other key, "ba_weight"
+        [7, T, 38] float64 (the smaller rho' of the detection's two residuals: 1 where it took part at full weight, NaN where it was
+        not in the adjustment), "ba_counts" [7, 3] (per camera: observations, those with weight below 0.5, the mean weight) and
+        "ba_params" (loss, f_scale); calibration_outliers() lists the detections the calibration disbelieved.  'linear' changes
+        nothing: the reference's sum of squares, and the result's schema as it was."""
         from . import distributed as dd
 
+        loss = config_mod.BA_LOSS if loss is None else loss
+        f_scale = config_mod.BA_F_SCALE if f_scale is None else f_scale
+        _ba.loss_code(loss, f_scale)    # refused before any work, on every rank
         error = None
+        self._ba_robust = None
         if self.is_primary:
             try:
                 calib = load_calibration()
                 reordered = {int(cidx): calib[idx] for idx, cidx in enumerate(self.camera_ordering)}
                 self.camNet = CameraNetwork(self.points2d * self.image_shape[::-1], calib=reordered, image_path=self._image_path, device=self.device)
-                self.camNet.bundle_adjust(update_intrinsic=False, update_distort=False)
+                if loss == "linear":
+                    self.camNet.bundle_adjust(update_intrinsic=False, update_distort=False)
+                else:
+                    info = self.camNet.bundle_adjust(update_intrinsic=False, update_distort=False, loss=loss, f_scale=float(f_scale))
+                    self._ba_robust = self._ba_robust_keys(info, loss, float(f_scale))
                 print(f"Reprojection error is {self.camNet.reprojection_error()}")
             except Exception as e:  # noqa: BLE001  (re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "calibrate_calc")
+
+    def _ba_robust_keys(self, info, loss, f_scale):
+        """The result keys of a robust calibration, from the camera network's solver info."""
+        T, stride = self.camNet.points2d.shape[1], int(info["frame_stride"])
+        weight = np.full(self.camNet.points2d.shape[:3], np.nan, dtype=np.float64)
+        weight[:, ::stride][:, : info["obs_weight"].shape[1]] = info["obs_weight"]   # (a recording above ba_max_images: the strided frames)
+        seen = ~np.isnan(weight)
+        with np.errstate(invalid="ignore"):
+            low = seen & (weight < 0.5)
+        counts = np.zeros((weight.shape[0], 3), dtype=np.float64)
+        counts[:, 0], counts[:, 1] = seen.sum(axis=(1, 2)), low.sum(axis=(1, 2))
+        counts[:, 2] = np.where(counts[:, 0] > 0, np.nansum(weight, axis=(1, 2)) / np.maximum(counts[:, 0], 1), np.nan)
+        return {"ba_weight": weight, "ba_counts": counts, "ba_params": {"loss": loss, "f_scale": f_scale, "cost": float(info["cost"]), "nfev": int(info["nfev"]),
+                                                                          "status": int(info["status"]), "frame_stride": stride}}
+
+    def calibration_outliers(self, threshold=0.5):
+        """The detections the robust calibration disbelieved: a list of (camera id, image id, joint id) whose weight in the bundle
+        adjustment ("ba_weight") is below `threshold` -- the detections to look at first, as outlier_cameras() lists them for the
+        consensus.  Needs calibrate_calc() with a loss other than 'linear'; a rank-0 method."""
+        from . import distributed as dd
+
+        if dd.current()[0] != 0:
+            raise RuntimeError("calibration_outliers is a rank-0 method: the camera network lives on rank 0")
+        if getattr(self, "_ba_robust", None) is None:
+            raise RuntimeError("calibration_outliers needs a robust calibration: run calibrate_calc(loss='soft_l1') first")
+        if not (np.isfinite(threshold) and 0 < threshold <= 1):
+            raise ValueError(f"threshold must lie in (0, 1] (it is {threshold:g})")
+        with np.errstate(invalid="ignore"):
+            return [(int(c), int(t), int(j)) for c, t, j in np.argwhere(self._ba_robust["ba_weight"] < threshold)]
 
     def get_points3d(self):
         """Pose for the 3-D video: array[image_id][joint_id] = (x, y, z) after Procrustes, median-centring + axis swap
@@ -1056,6 +1102,8 @@ class Core:
                 or trajectory is not None or heatmap is not None):
             result.update(self._kinematic_keys(joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
                                                repair, treadmill, robust, trajectory, heatmap))
+        if getattr(self, "_ba_robust", None) is not None:   # only after a robust calibration: else the schema is what it was
+            result.update(self._ba_robust)
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")

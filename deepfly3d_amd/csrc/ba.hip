@@ -3,6 +3,8 @@
 //   * ba_eval_kernel     one thread per observation: pinhole residual + analytic 2x6 / 2x3 Jacobian blocks.
 //                        The <= 8 camera rotations R(rvec) and the Rodrigues derivative factor M are built
 //                        once per workgroup in LDS (oracle/trf_lsmr.py:rotation_and_dfactor).
+//   * ba_eval_robust_kernel  the same lanes under a robust loss (ba_robust_dev.h; the section at the end of this file): f w / s, the
+//                        Jacobian rows times s, the weights, in one pass.
 //   * matvec / rmatvec   J v and J^T u on the block form.  J^T u needs a reduction over all observations of a
 //                        camera: observations are pre-grouped by camera (cam_perm / cam_start), every
 //                        (camera, chunk) workgroup reduces its slice in a fixed order, a second kernel sums the
@@ -17,6 +19,7 @@
 
 #include "common.h"
 #include "ba_lsmr.h"
+#include "ba_robust_dev.h"
 
 namespace {
 
@@ -137,6 +140,91 @@ __global__ __launch_bounds__(256) void ba_eval_kernel(df3d_ba_problem p, const d
         Jc[(1 * 6 + 3) * n + i] = 0.0;
         Jc[(1 * 6 + 4) * n + i] = a11;
         Jc[(1 * 6 + 5) * n + i] = a12;
+    }
+}
+
+// what the robust evaluation adds to an observation's outputs: the loss, C = f_scale, and two optional planes
+struct RobustOut {
+    int loss;
+    double C;
+    double* f_true;   // [2 nobs] the unscaled residuals, or null
+    double* w;        // [2 nobs] the weights rho', or null
+};
+
+// ba_eval_kernel with the robust loss applied on the way out, in ONE pass: the scaled f = f w / s (r, required), the Jacobian entries times
+// their row's s (Jc / Jp, optional, together), and through `ro` the unscaled f and the weights (optional).  Same lanes, same camera staging,
+// same memory traffic + the weight plane.  The arithmetic in front of the scaling is ba_eval_kernel's, statement for statement; it is written
+// out a second time, not shared, because ba_eval_kernel has to keep its bits: which of two products the compiler fuses into their sum
+// follows the shape of the code around them, and routing that kernel through a shared body swapped the choice in its Jp.
+__global__ __launch_bounds__(256) void ba_eval_robust_kernel(df3d_ba_problem p, const double* __restrict__ x, RobustOut ro,
+                                                             double* __restrict__ r, double* __restrict__ Jc,
+                                                             double* __restrict__ Jp) {
+    __shared__ CamLds L;
+    cam_prep(x, p.intr4, p.ncam, L);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.nobs) return;
+    const int c = p.cam_idx[i];
+    const int q = p.pt_idx[i];
+    const double* Xp = x + 6 * p.ncam + 3 * (size_t)q;
+    const double X0 = Xp[0], X1 = Xp[1], X2 = Xp[2];
+    const double* R = L.R[c];
+    const double xc = R[0] * X0 + R[1] * X1 + R[2] * X2 + L.t[c][0];
+    const double yc = R[3] * X0 + R[4] * X1 + R[5] * X2 + L.t[c][1];
+    const double zc = R[6] * X0 + R[7] * X1 + R[8] * X2 + L.t[c][2];
+    const double fx = L.k[c][0], fy = L.k[c][1], cx = L.k[c][2], cy = L.k[c][3];
+    const double iz = 1.0 / zc;
+    const double2 o = *reinterpret_cast<const double2*>(p.obs_xy + 2 * (size_t)i);
+    double2 res;
+    res.x = fx * xc * iz + cx - o.x;
+    res.y = fy * yc * iz + cy - o.y;
+    const df3d_robust::Row r0 = df3d_robust::row(ro.loss, res.x, ro.C), r1 = df3d_robust::row(ro.loss, res.y, ro.C);
+    if (ro.f_true) *reinterpret_cast<double2*>(ro.f_true + 2 * (size_t)i) = res;
+    if (ro.w) {
+        double2 ww;
+        ww.x = r0.w;
+        ww.y = r1.w;
+        *reinterpret_cast<double2*>(ro.w + 2 * (size_t)i) = ww;
+    }
+    res.x = res.x * r0.w / r0.s;
+    res.y = res.y * r1.w / r1.s;
+    *reinterpret_cast<double2*>(r + 2 * (size_t)i) = res;
+    if (Jc && Jp) {
+        const double s0 = r0.s, s1 = r1.s;
+        // d pi / d Xc
+        const double a00 = fx * iz, a02 = -fx * xc * iz * iz;
+        const double a11 = fy * iz, a12 = -fy * yc * iz * iz;
+        // point block: dpi * R
+        const size_t n = (size_t)p.nobs;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            Jp[(0 * 3 + k) * n + i] = (a00 * R[0 + k] + a02 * R[6 + k]) * s0;
+            Jp[(1 * 3 + k) * n + i] = (a11 * R[3 + k] + a12 * R[6 + k]) * s1;
+        }
+        // rotation block: dpi * (-R [X]x M)
+        // G = [X]x M
+        const double* M = L.M[c];
+        double G[9];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            G[0 + k] = -X2 * M[3 + k] + X1 * M[6 + k];
+            G[3 + k] = X2 * M[0 + k] - X0 * M[6 + k];
+            G[6 + k] = -X1 * M[0 + k] + X0 * M[3 + k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double d0 = -(R[0] * G[0 + k] + R[1] * G[3 + k] + R[2] * G[6 + k]);
+            const double d1 = -(R[3] * G[0 + k] + R[4] * G[3 + k] + R[5] * G[6 + k]);
+            const double d2 = -(R[6] * G[0 + k] + R[7] * G[3 + k] + R[8] * G[6 + k]);
+            Jc[(0 * 6 + k) * n + i] = (a00 * d0 + a02 * d2) * s0;
+            Jc[(1 * 6 + k) * n + i] = (a11 * d1 + a12 * d2) * s1;
+        }
+        // translation block: dpi
+        Jc[(0 * 6 + 3) * n + i] = a00 * s0;
+        Jc[(0 * 6 + 4) * n + i] = 0.0;
+        Jc[(0 * 6 + 5) * n + i] = a02 * s0;
+        Jc[(1 * 6 + 3) * n + i] = 0.0;
+        Jc[(1 * 6 + 4) * n + i] = a11 * s1;
+        Jc[(1 * 6 + 5) * n + i] = a12 * s1;
     }
 }
 
@@ -1081,6 +1169,135 @@ int df3d_ba_trf_linearize(const df3d_ba_problem* p, const double* x_dev, double*
     if (int rc = df3d_ba_colsq(p, Jc, Jp, colsq_dev, scratch_dev, stream)) return rc;
     hipLaunchKernelGGL(update_scale_kernel, dim3(grid_for(n)), dim3(256), 0, s, colsq_dev, scale_inv_dev, scale_dev, n, first);
     DF3D_LAUNCH_CHECK();
+    return DF3D_OK;
+}
+
+}  // extern "C"
+
+// ---- robust losses: scipy's loss = soft_l1 | huber | cauchy | arctan inside the same trust-region driver ---------------
+// The robust evaluation hands the driver J's rows times s and f w / s (ba_robust_dev.h), so everything between two evaluations -- g,
+// x_scale='jac', the Cauchy damping, every LSMR form, the 2-D subspace, the predicted reduction -- runs unchanged on what it is given; the
+// actual reduction takes the robust cost 1/2 C^2 sum rho of the UNSCALED trial residuals in place of 1/2 |f_new|^2.
+namespace {
+
+// partial sums of rho over a residual vector: dot_kernel's grid and order
+__global__ __launch_bounds__(256) void robust_cost_kernel(const double* __restrict__ f, size_t n, int loss, double C, double* __restrict__ partial) {
+    __shared__ double lds4[4];
+    double acc = 0.0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) acc += df3d_robust::rho(loss, f[i], C);
+    const double tot = block_reduce_256(acc, lds4);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+// final_sum_kernel, times 1/2 C^2
+__global__ __launch_bounds__(256) void robust_cost_final_kernel(const double* __restrict__ partial, int count, double half_c2, double* __restrict__ result) {
+    __shared__ double lds4[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < count; i += 256) acc += partial[i];
+    const double tot = block_reduce_256(acc, lds4);
+    if (threadIdx.x == 0) result[0] = half_c2 * tot;
+}
+
+int check_loss(const char* who, int loss, double f_scale) {
+    if (loss != DF3D_BA_LOSS_LINEAR && loss != DF3D_BA_LOSS_SOFT_L1 && loss != DF3D_BA_LOSS_HUBER && loss != DF3D_BA_LOSS_CAUCHY && loss != DF3D_BA_LOSS_ARCTAN) {
+        df3d::set_error("%s: %s", who, "unknown loss");
+        return DF3D_EINVAL;
+    }
+    if (!(f_scale > 0) || !std::isfinite(f_scale)) {
+        df3d::set_error("%s: %s", who, "f_scale must be positive and finite");
+        return DF3D_EINVAL;
+    }
+    return DF3D_OK;
+}
+
+// 1/2 C^2 sum rho(f) into *result (device), partials in `partial` (RED_BLOCKS doubles)
+void enqueue_robust_cost(const double* f, size_t m, int loss, double C, double* partial, double* result, hipStream_t s) {
+    const int g = grid_for(m);
+    hipLaunchKernelGGL(robust_cost_kernel, dim3(g), dim3(256), 0, s, f, m, loss, C, partial);
+    hipLaunchKernelGGL(robust_cost_final_kernel, dim3(1), dim3(256), 0, s, partial, g, 0.5 * C * C, result);
+}
+
+void enqueue_eval_robust(const df3d_ba_problem* p, const double* x, int loss, double C, double* f_true, double* f, double* Jc, double* Jp, double* w, hipStream_t s) {
+    RobustOut ro;
+    ro.loss = loss;
+    ro.C = C;
+    ro.f_true = f_true;
+    ro.w = w;
+    hipLaunchKernelGGL(ba_eval_robust_kernel, dim3((p->nobs + 255) / 256), dim3(256), 0, s, *p, x, ro, f, Jc, Jp);
+}
+
+}  // namespace
+
+extern "C" {
+
+int df3d_ba_eval_robust(const df3d_ba_problem* p, const double* x_dev, int loss, double f_scale, double* f_true_dev, double* f_dev, double* Jc_dev,
+                        double* Jp_dev, double* w_dev, void* stream) {
+    if (int rc = check_problem(p)) return rc;
+    if (int rc = check_loss(__func__, loss, f_scale)) return rc;
+    DF3D_CHECK_ARG(x_dev != nullptr && f_dev != nullptr, "null x or f");
+    DF3D_CHECK_ARG((Jc_dev == nullptr) == (Jp_dev == nullptr), "Jc and Jp must be given together");
+    enqueue_eval_robust(p, x_dev, loss, f_scale, f_true_dev, f_dev, Jc_dev, Jp_dev, w_dev, df3d::as_stream(stream));
+    DF3D_LAUNCH_CHECK();
+    return DF3D_OK;
+}
+
+int df3d_ba_robust_cost(const double* f_dev, size_t m, int loss, double f_scale, double* result_host, double* scratch_dev, void* stream) {
+    if (int rc = check_loss(__func__, loss, f_scale)) return rc;
+    DF3D_CHECK_ARG(f_dev && result_host && scratch_dev, "null pointer");
+    hipStream_t s = df3d::as_stream(stream);
+    enqueue_robust_cost(f_dev, m, loss, f_scale, scratch_dev, scratch_dev + SCRATCH_RESULT, s);
+    DF3D_LAUNCH_CHECK();
+    return read_back(scratch_dev + SCRATCH_RESULT, result_host, s);
+}
+
+int df3d_ba_trf_linearize_robust(const df3d_ba_problem* p, const double* x_dev, int loss, double f_scale, double* f_true_dev, double* f_dev, double* Jc,
+                                 double* Jp, double* w_dev, double* g_dev, double* colsq_dev, double* scale_inv_dev, double* scale_dev, int first,
+                                 double* scratch_dev, void* stream) {
+    if (int rc = check_problem(p)) return rc;
+    if (int rc = check_loss(__func__, loss, f_scale)) return rc;
+    DF3D_CHECK_ARG(x_dev && f_dev && Jc && Jp && g_dev && colsq_dev && scale_inv_dev && scale_dev && scratch_dev, "null pointer");
+    hipStream_t s = df3d::as_stream(stream);
+    const size_t n = 6 * (size_t)p->ncam + 3 * (size_t)p->npts;
+    enqueue_eval_robust(p, x_dev, loss, f_scale, f_true_dev, f_dev, Jc, Jp, w_dev, s);
+    if (int rc = launch_rmatvec(p, Jc, Jp, nullptr, f_dev, g_dev, scratch_dev, s)) return rc;   // g = J^T f, both scaled
+    if (int rc = df3d_ba_colsq(p, Jc, Jp, colsq_dev, scratch_dev, stream)) return rc;
+    hipLaunchKernelGGL(update_scale_kernel, dim3(grid_for(n)), dim3(256), 0, s, colsq_dev, scale_inv_dev, scale_dev, n, first);
+    DF3D_LAUNCH_CHECK();
+    return DF3D_OK;
+}
+
+int df3d_ba_trf_trial_robust(const df3d_ba_problem* p, int loss, double f_scale, double p0, double p1, const double* s0, const double* s1, const double* Js0,
+                             const double* Js1, const double* scale_dev, const double* x_dev, const double* g_h, double* step_h, double* tmp_m, double* step,
+                             double* x_new, double* f_new, double* scratch_dev, double* out_host, void* stream) {
+    if (int rc = check_problem(p)) return rc;
+    if (int rc = check_loss(__func__, loss, f_scale)) return rc;
+    DF3D_CHECK_ARG(s0 && s1 && Js0 && Js1 && scale_dev && x_dev && g_h && step_h && tmp_m && step && x_new && f_new && scratch_dev && out_host, "null pointer");
+    hipStream_t s = df3d::as_stream(stream);
+    const size_t m = 2 * (size_t)p->nobs, n = 6 * (size_t)p->ncam + 3 * (size_t)p->npts;
+    const int gm = grid_for(m), gn = grid_for(n);
+    hipLaunchKernelGGL(axpby_kernel<false>, dim3(gn), dim3(256), 0, s, p0, s0, p1, s1, step_h, n, nullptr);
+    hipLaunchKernelGGL(axpby_kernel<false>, dim3(gm), dim3(256), 0, s, p0, Js0, p1, Js1, tmp_m, m, nullptr);   // J_h step = p0 J_h s0 + p1 J_h s1
+    hipLaunchKernelGGL(mul_kernel, dim3(gn), dim3(256), 0, s, scale_dev, step_h, step, n);
+    hipLaunchKernelGGL(axpby_kernel<false>, dim3(gn), dim3(256), 0, s, 1.0, x_dev, 1.0, step, x_new, n, nullptr);
+    hipLaunchKernelGGL(ba_eval_kernel, dim3((p->nobs + 255) / 256), dim3(256), 0, s, *p, x_new, f_new, nullptr, nullptr);   // the UNSCALED residuals
+    // df3d_ba_trf_trial's other five products in slots 0 .. 4 (a product's partials and sum are its slot's alone: the same bits in any slot),
+    // the robust cost in slot 5; out_host keeps df3d_ba_trf_trial's order, the cost where |f_new|^2 was
+    const double* a[5] = {tmp_m, step_h, step_h, step, x_dev};
+    const double* b[5] = {tmp_m, g_h, step_h, step, x_dev};
+    const size_t len[5] = {m, n, n, n, n};
+    double* const result = scratch_dev + SCRATCH_DOTS_RESULT;
+    if (int rc = enqueue_dots(5, a, b, len, scratch_dev, result, s)) return rc;
+    enqueue_robust_cost(f_new, m, loss, f_scale, scratch_dev + 5 * RED_BLOCKS, result + 5, s);
+    DF3D_LAUNCH_CHECK();
+    double host[6];
+    DF3D_HIP(hipMemcpyAsync(host, result, sizeof(host), hipMemcpyDeviceToHost, s));
+    DF3D_HIP(hipStreamSynchronize(s));
+    out_host[0] = host[0];
+    out_host[1] = host[1];
+    out_host[2] = host[2];
+    out_host[3] = host[5];
+    out_host[4] = host[3];
+    out_host[5] = host[4];
     return DF3D_OK;
 }
 

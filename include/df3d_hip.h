@@ -790,6 +790,35 @@ int df3d_ba_trf_trial(const df3d_ba_problem* p, double p0, double p1, const doub
 int df3d_ba_trf_linearize(const df3d_ba_problem* p, const double* x_dev, double* f_dev, int eval_f, double* Jc_dev, double* Jp_dev, double* g_dev,
                           double* colsq_dev, double* scale_inv_dev, double* scale_dev, int first, double* scratch_dev, void* stream);
 
+/* Robust losses for the adjustment, with the semantics of scipy.optimize.least_squares(method='trf', loss=..., f_scale=...) (an opt-in
+ * beside the reference's plain sum of squares, call site reference df3d/core.py:249).  With C = f_scale and z = (f / C)^2 PER SCALAR residual:
+ *   cost = 1/2 C^2 sum rho(z),   w = rho'(z),   s^2 = rho' + 2 z rho'' clamped below at 2^-52;   J's row times s, f <- f w / s.
+ *   soft_l1: rho = 2 (sqrt(1 + z) - 1)   huber: z (z <= 1), 2 sqrt(z) - 1   cauchy: log1p(z)   arctan: atan(z)   linear: z (w = s = 1)
+ * The scaled (J, f) go through every entry above unchanged (matvec, rmatvec, colsq, every LSMR form, df3d_ba_trf_subspace).
+ * Every entry refuses an unknown loss, an f_scale that is not positive and finite, and null pointers before it touches the device.
+ * df3d_ba_eval_robust: one pass, one lane per observation as df3d_ba_eval: the scaled f (f_dev[2 nobs], required), the scaled Jc / Jp rows
+ *   (NULL together to skip), and optionally the unscaled residuals (f_true_dev[2 nobs]) and the weights (w_dev[2 nobs]).
+ * df3d_ba_robust_cost: 1/2 C^2 sum rho over a vector of m UNSCALED residuals, summed in df3d_vec_dot's order (a residual that is not
+ *   finite gives NaN); synchronous.
+ * df3d_ba_trf_linearize_robust / df3d_ba_trf_trial_robust: df3d_ba_trf_linearize / df3d_ba_trf_trial for a robust loss.  linearize always
+ *   evaluates f (scaled into f_dev; f_true_dev and w_dev optional); trial leaves the UNSCALED residuals in f_new_dev and returns the robust
+ *   cost in out_host[3], where df3d_ba_trf_trial returns |f_new|^2. */
+#define DF3D_BA_LOSS_LINEAR 0
+#define DF3D_BA_LOSS_SOFT_L1 1
+#define DF3D_BA_LOSS_HUBER 2
+#define DF3D_BA_LOSS_CAUCHY 3
+#define DF3D_BA_LOSS_ARCTAN 4
+int df3d_ba_eval_robust(const df3d_ba_problem* p, const double* x_dev, int loss, double f_scale, double* f_true_dev, double* f_dev, double* Jc_dev,
+                        double* Jp_dev, double* w_dev, void* stream);
+int df3d_ba_robust_cost(const double* f_dev, size_t m, int loss, double f_scale, double* result_host, double* scratch_dev, void* stream);
+int df3d_ba_trf_linearize_robust(const df3d_ba_problem* p, const double* x_dev, int loss, double f_scale, double* f_true_dev, double* f_dev,
+                                 double* Jc_dev, double* Jp_dev, double* w_dev, double* g_dev, double* colsq_dev, double* scale_inv_dev,
+                                 double* scale_dev, int first, double* scratch_dev, void* stream);
+int df3d_ba_trf_trial_robust(const df3d_ba_problem* p, int loss, double f_scale, double p0, double p1, const double* s0_dev, const double* s1_dev,
+                             const double* Js0_dev, const double* Js1_dev, const double* scale_dev, const double* x_dev, const double* g_h_dev,
+                             double* step_h_dev, double* tmp_m_dev, double* step_dev, double* x_new_dev, double* f_new_dev, double* scratch_dev,
+                             double* out_host, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * a2  stacked-hourglass forward.   Replaces the network forward inside df2d's inference_folder
  *     (call site reference df3d/core.py:177-185; 2 stacks / 19 maps / 64x128 heat-maps:
