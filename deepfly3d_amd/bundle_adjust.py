@@ -211,6 +211,9 @@ class _Dev:
         return list(info)
 
 
+_S1_REORTH = 2.0**-20    # |s1| below this fraction of |gn_h|: the second Gram-Schmidt pass (csrc/ba.hip: S1_REORTH)
+
+
 def _solve_trust_region_2d(B, g, Delta):
     """2-D trust-region subproblem (host, 2x2): Newton step if inside, else the boundary minimiser."""
     try:
@@ -296,6 +299,13 @@ class _HostScalars:
         dv.axpby(1.0, gn_h, -r01, s0, s1)
         n1 = dv.norm(s1)
         dv.axpby(-1.0 / n1, s1, 0.0, None, s1)
+        if n1 < _S1_REORTH * abs(r01):
+            # gn_h parallel to g_h (an LSMR run of one iteration under a large damping: the stall of huber and cauchy, DESIGN.md section
+            # 26): s1 is the rounding noise of gn_h - r01 s0 blown up, and not orthogonal to s0 any more -- LAPACK's Householder
+            # vectors, which scipy takes, are.  A second Gram-Schmidt pass on the normalised s1; no other solve comes here
+            r = dv.dot(s0, s1)
+            dv.axpby(1.0, s1, -r, s0, s1)
+            dv.axpby(1.0 / dv.norm(s1), s1, 0.0, None, s1)
         dv.matvec(Jc, Jp, d, s0, Js0)
         dv.matvec(Jc, Jp, d, s1, Js1)
         b00, b01, b11, gs0, gs1 = dv.dots((Js0, Js0), (Js0, Js1), (Js1, Js1), (s0, g_h), (s1, g_h))

@@ -993,7 +993,8 @@ int df3d_ba_lsmr(const df3d_ba_problem* p, const double* Jc, const double* Jp, c
 // operation (same kernels for every vector operation and reduction; the scalar expressions below are written without contraction), so
 // the iterate sequence -- nfev, LSMR counts, every bit of x -- is unchanged (tests/test_gpu_ba.py compares the two back ends).
 namespace {
-enum { TR_GNORM = 0, TR_JG2, TR_GH2, TR_DAMP, TR_CS0, TR_R01, TR_MR01, TR_N1SQ, TR_CS1, TR_B00, TR_B01, TR_B11, TR_GS0, TR_GS1, TR_ONE, TR_SLOTS };
+enum { TR_GNORM = 0, TR_JG2, TR_GH2, TR_DAMP, TR_CS0, TR_R01, TR_MR01, TR_N1SQ, TR_CS1, TR_B00, TR_B01, TR_B11, TR_GS0, TR_GS1, TR_ONE, TR_R2, TR_N2SQ, TR_SLOTS };
+constexpr double S1_REORTH = 0x1p-20;   // |s1| below this fraction of |gn_h|: the second Gram-Schmidt pass (bundle_adjust.py: _S1_REORTH)
 static_assert(TR_OFFSET + TR_SLOTS <= DF3D_BA_SCRATCH_DOUBLES, "scratch");
 
 // out = (*ca) x + (*cb) y (y / cb may be null): axpby_kernel with its coefficients in device memory
@@ -1123,6 +1124,32 @@ int df3d_ba_trf_subspace(const df3d_ba_problem* p, const double* Jc, const doubl
         } else {
             info_from_state(now, info);
         }
+    }
+    // gn_h parallel to g_h -- an LSMR run that one iteration ends, under the large damping of a trust region far smaller than the
+    // gradient step: the stall of huber and cauchy, DESIGN.md section 26 -- leaves gn_h - r01 s0 as rounding noise, and its normalisation
+    // blows the noise's component along s0 up with it: s1 is then not orthogonal to s0 (LAPACK's Householder vectors, which scipy
+    // takes, are, to the last bit, however parallel the columns).  When |s1| has lost S1_REORTH of |gn_h|, a second Gram-Schmidt
+    // pass on the normalised s1 puts that right: the host-scalar back end's statements (bundle_adjust.py: _HostScalars.subspace), kernel
+    // for kernel, with two more read-backs.  No other solve takes this branch, so every other solve keeps its launches and its bits.
+    if (std::sqrt(host[TR_N1SQ]) < S1_REORTH * std::fabs(host[TR_R01])) {
+        double r = 0.0, n2sq = 0.0;
+        const double* a[1] = {s0};
+        const double* b[1] = {s1};
+        const size_t len[1] = {n};
+        if (int rc = enqueue_dots(1, a, b, len, scratch_dev, tr + TR_R2, s)) return rc;
+        if (int rc = read_back(tr + TR_R2, &r, s)) return rc;
+        hipLaunchKernelGGL(axpby_kernel<false>, dim3(gn), dim3(256), 0, s, 1.0, s1, -r, s0, s1, n, nullptr);
+        if (int rc = enqueue_dots(1, b, b, len, scratch_dev, tr + TR_N2SQ, s)) return rc;
+        if (int rc = read_back(tr + TR_N2SQ, &n2sq, s)) return rc;
+        hipLaunchKernelGGL(axpby_kernel<false>, dim3(gn), dim3(256), 0, s, 1.0 / std::sqrt(n2sq), s1, 0.0, nullptr, s1, n, nullptr);
+        if (int rc = launch_matvec(p, Jc, Jp, scale_dev, s1, Js1, s)) return rc;
+        const double* a5[5] = {Js0, Js0, Js1, s0, s1};
+        const double* b5[5] = {Js0, Js1, Js1, g_h, g_h};
+        const size_t len5[5] = {m, m, m, n, n};
+        if (int rc = enqueue_dots(5, a5, b5, len5, scratch_dev, tr + TR_B00, s)) return rc;
+        DF3D_LAUNCH_CHECK();
+        DF3D_HIP(hipMemcpyAsync(host + TR_B00, tr + TR_B00, 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+        DF3D_HIP(hipStreamSynchronize(s));
     }
     out_host[0] = host[TR_GNORM];
     out_host[1] = host[TR_JG2];

@@ -778,6 +778,8 @@ int df3d_ba_update_scale(const double* colsq_dev, double* scale_inv_dev, double*
  *   gn_h (damping read from device memory by the data-local form; the other forms take one more read-back), the orthonormal basis
  *   S = [s0 s1] of span{g_h, gn_h} (LAPACK's QR signs), J_h S and the 2x2 model.  out_host[19]: |g|_inf, |J_h g_h|^2, |g_h|^2, damp, r01,
  *   |s1|^2 (before normalisation), B_S[0][0], B_S[0][1], B_S[1][1], g_S[0], g_S[1], then df3d_ba_lsmr's info[8].
+ *   When gn_h is parallel to g_h to rounding (|s1| < 2^-20 |r01|: an LSMR run that one iteration ends) s1 takes a second Gram-Schmidt
+ *   pass against s0, with two more read-backs; r01 and |s1|^2 are reported as the first pass left them.
  * df3d_ba_trf_trial: step_h = p0 s0 + p1 s1, x_new = x + scale step_h, f_new = residuals(x_new); out_host[6]: |J_h step_h|^2, step_h . g_h,
  *   |step_h|^2, |f_new|^2, |step|^2, |x|^2.
  * df3d_ba_trf_linearize: J (and f when eval_f != 0) at x, g = J^T f, x_scale='jac' bookkeeping (first != 0: the first call); no read-back. */

@@ -143,7 +143,20 @@ def test_the_solve_cases_cover_what_they_are_for():
     cases = {s["case"] for s in brc.SOLVES.values()}
     assert {"three", "mixed"} <= cases and len(brc.SOLVES) >= 3
     assert any(bc.CASES[s["case"]]["nobs"] >= 1024 for s in brc.SOLVES.values())       # two workgroups of the data-local LSMR form
-    assert any(s["fraction"] > 0 for s in brc.SOLVES.values()) and all(s["loss"] == "soft_l1" for s in brc.SOLVES.values())
+    soft = [s for s in brc.SOLVES.values() if s["loss"] == "soft_l1"]
+    assert any(s["fraction"] > 0 for s in soft) and len(soft) >= 4 and {s["case"] for s in soft} >= {"three", "mixed", "eight_1032"}
+    # the other three losses: each solved with, to convergence, with outliers present; the stall -- rejected trials up to xtol -- at least once
+    for loss in ("huber", "cauchy", "arctan"):
+        assert any(s["loss"] == loss and s.get("kind") == "converging" and s["fraction"] > 0 and s["status"] == 2 for s in brc.SOLVES.values()), loss
+    stalls = [s for s in brc.SOLVES.values() if s.get("kind") == "stall"]
+    assert stalls and all(s["status"] == 4 and s["nfev"] - len(s["lsmr_iters"]) - 1 >= 10 for s in stalls)
+    assert all(s["loss"] in brc.ROBUST for s in brc.SOLVES.values())
+    # huber beyond z = 1 (its only branch that differs from the linear loss) is in some solve's start
+    def rows_beyond_one(s):
+        case, (px, _) = bc.make_case(s["case"]), brc.plant(s["case"], s["fraction"], s["shift"], s["seed"])
+        pr = bro.problem(px, case["R_init"], case["tvec_init"], case["intr"])
+        return int((np.abs(pr["evaluate"](pr["x0"], False)[0]) > s["f_scale"]).sum())
+    assert any(s["loss"] == "huber" and s["status"] == 2 and rows_beyond_one(s) > 0 for s in brc.SOLVES.values())
 
 
 # ---- the outcome test's input conditions, on the oracle alone ------------------------------------------------------------------------------------

@@ -132,6 +132,37 @@ def test_linear_is_untouched(native_lib, cuda):
         assert set(ia) == set(ib) and "obs_weight" not in ia
 
 
+def _assert_the_stall(key, form, want, case, px, info, res, cuda):
+    """The stalled solve is there for its run of rejected trials: nfev - len(lsmr_iters) - 1 of them happened, and the weights it
+    returns are those of the point it stalled at, within 64 ulp.
+    The reference for the weights is the oracle's rho' of the device's own unscaled residuals at the device's final x (one more
+    df3d_ba_eval_robust there), as test_robust_eval_and_cost takes it.  The oracle's own final weights cannot serve at that bar, nor can
+    the oracle's residuals at the device's x (both printed beside it): a residual is the difference of two pixel coordinates of some
+    500 px, so two correct evaluations differ by EPS x 500 px, 100 EPS of a 5 px residual, before a weight is formed (measured: 3.3e-14
+    for huber, 2.3e-14 for cauchy); and the device starts from its own triangulation, held to 1e-9 mm of the oracle's
+    (tests/test_gpu_geometry.py), where a start moved by 1e-14 mm moves this solve's final weights by 61 x 64 ulp (measured on the
+    oracle: DESIGN.md section 26, "Sweep")."""
+    from deepfly3d_amd import _native
+    from deepfly3d_amd.bundle_adjust import BAProblemDevice, _Dev
+
+    rejected = info["nfev"] - len(info["lsmr_iters"]) - 1
+    assert rejected == want["nfev"] - len(want["lsmr_iters"]) - 1 >= 10, (key, form, rejected)
+    loss, C = want["loss"], want["f_scale"]
+    prob = BAProblemDevice(px, case["intr"], cuda)
+    f, ft, wd = _nan(prob.m, cuda), _nan(prob.m, cuda), _nan(prob.m, cuda)
+    _Dev(prob).eval_robust(info["x"], _native.BA_LOSSES.index(loss), C, f, f_true=ft, w=wd)
+    want_w = bro.weight(loss, (ft.cpu().numpy() / C) ** 2).reshape(-1, 2).min(axis=1)
+    f_host = bro.problem(px, case["R_init"], case["tvec_init"], case["intr"])["evaluate"](info["x"].cpu().numpy(), False)[0]
+    w = info["weights"].cpu().numpy()
+    e_w = _rel(w, want_w)
+    print("%s form %s: %d rejected trials; weights vs the oracle's rho' of the device's residuals at its x %.2e (bar 64 ulp = %.1e); of the oracle's "
+          "residuals at that x %.2e; vs the oracle's own final weights %.2e"
+          % (key, form, rejected, e_w, ULP, _rel(w, bro.weight(loss, (f_host / C) ** 2).reshape(-1, 2).min(axis=1)), _rel(w, res["obs_weight"])))
+    assert (want_w < 0.5).any() and (want_w > 0.9).any()          # (weights that say something)
+    assert np.array_equal(w, wd.view(-1, 2).min(dim=1).values.cpu().numpy())     # what the solve kept through its rejections: the last linearisation's
+    assert e_w <= ULP, (key, form, e_w)
+
+
 @pytest.mark.parametrize("key", brc.SOLVE_NAMES)
 def test_whole_solve(native_lib, cuda, monkeypatch, key):
     """nfev, status and LSMR counts are the oracle's; R, t and the cost within 100 x the oracle's own spread; the two back ends take the
@@ -161,6 +192,8 @@ def test_whole_solve(native_lib, cuda, monkeypatch, key):
         assert got[0][8] == 0
         assert np.abs(R - Ro).max() <= bar_R and np.abs(t - to).max() <= bar_t and e_c <= bar_c, form
         assert (info["loss"], info["f_scale"]) == (want["loss"], want["f_scale"])
+        if want.get("kind") == "stall":
+            _assert_the_stall(key, form, want, case, px, info, res, cuda)
 
 
 @pytest.mark.parametrize("name", tuple(brc.OUTCOME))
