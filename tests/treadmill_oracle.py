@@ -133,8 +133,9 @@ def normal4(s):
     return A, np.array(s[13:17])
 
 
-def cholesky_solve(A, rhs, floor):
-    """The solution of A p = rhs by Cholesky, row by row as the kernels do; None where a pivot is at or below `floor` or no number."""
+def cholesky_solve(A, rhs, floor, seen=None):
+    """The solution of A p = rhs by Cholesky, row by row as the kernels do; None where a pivot is at or below `floor` or no number.
+    `seen`: a list that takes (pivot, floor) of every pivot decision, up to and with the first refused one."""
     k = len(rhs)
     L = np.zeros((k, k))
     for i in range(k):
@@ -143,6 +144,8 @@ def cholesky_solve(A, rhs, floor):
             for c in range(j):
                 acc = acc - L[i, c] * L[j, c]
             if i == j:
+                if seen is not None:
+                    seen.append((float(acc), float(floor)))
                 if not acc > floor:
                     return None
                 L[i, i] = math.sqrt(acc)
@@ -163,13 +166,13 @@ def cholesky_solve(A, rhs, floor):
     return p
 
 
-def _algebraic(s):
+def _algebraic(s, seen=None):
     """(centre [3], radius) of the 17 sums, or None where the fit is refused."""
     n = s[0]
     if n < 4.0:
         return None
     A, rhs = normal4(s)
-    p = cholesky_solve(A, rhs, PIVOT_MIN * float(np.max(np.diag(A))))
+    p = cholesky_solve(A, rhs, PIVOT_MIN * float(np.max(np.diag(A))), seen)
     if p is None:
         return None
     a = 0.5 * p[:3]
@@ -197,13 +200,42 @@ def normal3(g):
     return np.array([[g[0], g[1], g[2]], [g[1], g[3], g[4]], [g[2], g[4], g[5]]]), np.array(g[6:9])
 
 
-def fit_ball(b, states, radius=None, iterations=ITERATIONS, total=exact_sum):
+def _step(b, states, c, R, total=exact_sum, alter=None, seen=None):
+    """(delta [3] or None, g [10]) of one Gauss-Newton step at the centre c: the step sums, their 3 x 3 Cholesky solve."""
+    g = step_sums(b, states, c, R, total)
+    N, rhs = normal3(g if alter is None else alter(g))
+    delta = cholesky_solve(N, rhs, PIVOT_MIN * float(np.max(np.diag(N))), seen)
+    if delta is None or not np.all(np.isfinite(delta)):
+        return None, g
+    return delta, g
+
+
+def gauss_newton_step(b, states, c, R, total=exact_sum, alter=None, seen=None):
+    """(c_next [3] or None where the step is refused, g [10]: the step sums at c): one step exactly as fit_ball's loop body takes it.
+    `alter`: a function of the ten sums whose result is solved in their place -- the mutants of tests/test_treadmill_cases_host.py,
+    which say what a comparison can and cannot see; `seen`: cholesky_solve's."""
+    delta, g = _step(b, states, np.asarray(c, dtype=np.float64), float(R), total, alter, seen)
+    return (None if delta is None else c + delta), g
+
+
+def start_below(s, R):
+    """m + m (R / |m|) of the 17 sums: the start of a known-radius fit that has no algebraic centre, or None where it has none either."""
+    n = s[0]
+    m = s[1:4] / n if n >= 3.0 else np.full(3, NAN)
+    length = math.sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]) if n >= 3.0 else NAN
+    if not (length > 0.0 and np.isfinite(length)):
+        return None
+    f = R / length
+    return m + m * f
+
+
+def fit_ball(b, states, radius=None, iterations=ITERATIONS, total=exact_sum, alter=None, seen=None):
     """dict(center [3], radius, rms, count, status, sums [17], steps: the lengths of the Gauss-Newton steps, last: the sums of the last
-    step)."""
+    step).  `alter`, `seen`: gauss_newton_step's; `seen` takes the algebraic fit's pivots first."""
     s = ball_sums(b, states, total)
     n = s[0]
     out = dict(center=np.full(3, NAN), radius=NAN, rms=NAN, count=int(n), status=REFUSED, sums=s, steps=[], last=None)
-    fit = _algebraic(s)
+    fit = _algebraic(s, seen)
     status = 0
     if radius is None:
         if fit is None:
@@ -214,17 +246,13 @@ def fit_ball(b, states, radius=None, iterations=ITERATIONS, total=exact_sum):
         if fit is not None:
             c = fit[0]
         else:
-            m = s[1:4] / n if n >= 3.0 else np.full(3, NAN)
-            length = math.sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]) if n >= 3.0 else NAN
-            if not (length > 0.0 and np.isfinite(length)):
+            c = start_below(s, R)
+            if c is None:
                 return out
-            f = R / length
-            c, status = m + m * f, START_BELOW
+            status = START_BELOW
         for _ in range(iterations):
-            g = step_sums(b, states, c, R, total)
-            N, rhs = normal3(g)
-            delta = cholesky_solve(N, rhs, PIVOT_MIN * float(np.max(np.diag(N))))
-            if delta is None or not np.all(np.isfinite(delta)):
+            delta, g = _step(b, states, c, R, total, alter, seen)
+            if delta is None:
                 out["status"] = status | REFUSED
                 return out
             c = c + delta
@@ -281,15 +309,37 @@ def known_radius_bar(b, states, fit):
     # the rate is that near the limit: a first step from far away obeys no rate, and below 1e-9 a step is rounding
     big = [k for k in range(1, len(steps)) if 1e-9 < steps[k - 1] <= 1e-2 * fit["radius"]]
     assert all(steps[k] <= 0.5 * steps[k - 1] for k in big), steps
-    c, R = fit["center"], fit["radius"]
+    c = fit["center"]
+    e = _step_solve_bar(b, states, c, fit["radius"], fit["last"], None)
+    e += U * float(np.linalg.norm(c))
+    return 4.0 * e + 2.0 * steps[-1]
+
+
+def _step_solve_bar(b, states, c, R, g, terms):
+    """_solve_bar on the 3 x 3 system of the step sums g, with the magnitudes sum |u||u|^T, sum |u||r| taken at the centre c and the
+    residual's absolute error sum |u| 8 u rho on the right side (known_radius_bar).  `terms`: the summed terms of an entry, None for
+    the sample count."""
     keep = samples(b, states).reshape(-1)
     d = np.asarray(b, dtype=np.float64).reshape(-1, 3)[keep] - c
     rho = np.sqrt(_dot(d, d))
     u, r = np.abs(d / rho[:, None]), np.abs(rho - R)
-    N, g = normal3(fit["last"])
-    e = _solve_bar(N, u.T @ u, u.T @ r, np.linalg.solve(N, g), len(d), 8.0 * U * float(np.linalg.norm(u.T @ rho)))
-    e += U * float(np.linalg.norm(c))
-    return 4.0 * e + 2.0 * steps[-1]
+    N, rhs = normal3(g)
+    return _solve_bar(N, u.T @ u, u.T @ r, np.linalg.solve(N, rhs), len(d) if terms is None else terms,
+                      8.0 * U * float(np.linalg.norm(u.T @ rho)))
+
+
+def step_bar(b, states, c, R):
+    """The bar on |device's c_next - gauss_newton_step's c_next| where both step from the same centre c.  Derived, not measured: the
+    device's delta solves the system of its own sums, n samples an entry in the kernel's order: within _solve_bar(terms = n) of the
+    exact step (the residual's 8 u rho on the right side, as in known_radius_bar); the oracle's sums are exact (math.fsum), so its
+    delta carries the roundings of the terms and of the solve alone: _solve_bar(terms = 0); and c + delta rounds once in each of
+    the two, by at most u |c_next| per vector: 2 u (|c| + |delta|).  No contraction enters: one step, not a sequence."""
+    c = np.asarray(c, dtype=np.float64)
+    g = step_sums(b, states, c, R)
+    N, rhs = normal3(g)
+    delta = np.linalg.solve(N, rhs)
+    e = _step_solve_bar(b, states, c, R, g, None) + _step_solve_bar(b, states, c, R, g, 0)
+    return e + 2.0 * U * (float(np.linalg.norm(c)) + float(np.linalg.norm(delta)))
 
 
 def rms_bar(b, states, fit, center_bar, radius_bar):
@@ -355,6 +405,18 @@ def solve3(M, rhs, floor):
     ok &= np.all(np.isfinite(w), axis=-1)
     w[~ok] = np.nan
     return w, ok
+
+
+def solve3_pivots(M):
+    """[T, 3]: the three pivots solve3 compares with its floor, in its order (NaN after a pivot that is not positive)."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        xx, xy, xz, yy, yz, zz = M[:, 0, 0], M[:, 0, 1], M[:, 0, 2], M[:, 1, 1], M[:, 1, 2], M[:, 2, 2]
+        l00 = np.sqrt(xx)
+        l10, l20 = xy / l00, xz / l00
+        d1 = yy - l10 * l10
+        l21 = (yz - l20 * l10) / np.sqrt(d1)
+        d2 = zz - l20 * l20 - l21 * l21
+    return np.stack([xx, d1, d2], axis=-1)
 
 
 def fictive_of(omega, c, R):
