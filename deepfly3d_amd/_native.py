@@ -68,6 +68,8 @@ PROTOTYPES = {
     "df3d_read_files": (c_int, [POINTER(c_char_p), c_int, c_void_p, c_size_t, c_void_p, c_void_p, POINTER(c_size_t), c_int]),
     "df3d_jpeg_work_bytes": (c_size_t, [c_int, c_int, c_int, c_size_t]),
     "df3d_jpeg_decode_luma": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_uint, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "df3d_jpeg_encode_work_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "df3d_jpeg_encode_rgb": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "df3d_heatmap_argmax": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "df3d_heatmap_argmax_checked": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_heatmap_argmax_subpixel": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -37,6 +37,9 @@ def parse_cli_args(argv=None):
     p.add_argument("--smooth-2d", dest="smooth_2d", action="store_true",
                    help="With --video-2d: draw the temporally smoothed 2-D detections (a 20-frame Gaussian where the detections are "
                         "quiet, the detection itself where they move) instead of the raw ones; results on disk are unchanged")
+    p.add_argument("--video-quality", dest="video_quality", type=int, default=90, metavar="Q",
+                   help="JPEG quality of the video frames, 1 .. 100 (default 90).  Has effect on the Motion-JPEG path only: the .avi written "
+                        "when ffmpeg is not on PATH, whose frames are encoded on the GPU")
     p.add_argument("--skip-pose-estimation", help="Skip 2D and 3D pose estimation", dest="skip_estimation", action="store_true")
     p.add_argument("--batch-size", help="Batch size for inference", type=int, default=8)
     p.add_argument("--pin-memory-disabled", help="Disable pinned host staging buffers", action="store_true")
@@ -332,7 +335,9 @@ def parse_cli_args(argv=None):
         p.error("--correct-only-flagged restricts --auto-correct: it needs --auto-correct")
     if args.smooth_2d and not args.video_2d:
         p.error("--smooth-2d changes what --video-2d draws: it needs --video-2d")
-    inp = Path(args.input_folder).expanduser().resolve()
+    if not 1 <= args.video_quality <= 100:
+        p.error(f"--video-quality is a JPEG quality, 1 .. 100: got {args.video_quality}")
+    inp =Path(args.input_folder).expanduser().resolve()
     args.output_folder = str(inp.with_name(inp.stem + "_df3d")) if args.output_folder is None else str(Path(args.output_folder).expanduser().resolve())
     args.input_folder = str(inp)
     return args
@@ -438,13 +443,15 @@ def run(args):
 
         fps = args.output_fps if args.output_fps is not None else core.fps
 
+        quality = getattr(args, "video_quality", 90)
+
         def videos(beat):
             if args.video_2d:
-                video.make_pose2d_video(core, fps=fps, progress=beat, smooth=getattr(args, "smooth_2d", False))
+                video.make_pose2d_video(core, fps=fps, progress=beat, smooth=getattr(args, "smooth_2d", False), quality=quality)
             if args.video_3d:
-                video.make_pose3d_video(core, fps=fps, progress=beat)
+                video.make_pose3d_video(core, fps=fps, progress=beat, quality=quality)
             if video_heatmap:
-                video.make_heatmap_video(core, fps=fps, progress=beat)
+                video.make_heatmap_video(core, fps=fps, progress=beat, quality=quality)
 
         dd.primary_section(videos, "video")
     if args.delete_images:

@@ -5,6 +5,9 @@ Replaces the libjpeg decode inside df2d's DataLoader workers (call site referenc
 result is the JPEG's luma plane with libjpeg's default "islow" IDCT, bit-identical to Pillow / libjpeg-turbo for
 grayscale and chroma-neutral files (the rig's monochrome cameras) and to libjpeg's own grayscale output
 (`Image.draft("L", ...)`) for coloured ones.
+
+The second half of the file is the encoder: RGB frames on the device -> baseline JPEG files, byte-equal to
+Pillow's (csrc/jpeg_encode.hip, C ABI `df3d_jpeg_encode_rgb`); the Motion-JPEG videos are written with it.
 """
 import numpy as np
 import torch
@@ -307,3 +310,163 @@ class JpegFolderReader:
                     if slot["buf"] is not None:
                         _pool_put(slot["buf"])
                     slot["buf"] = None
+
+
+# ---- the encoder ------------------------------------------------------------------------------------------------
+# libjpeg's baseline encoder on the device (csrc/jpeg_encode.hip, C ABI `df3d_jpeg_encode_rgb`): 4:2:0, the Annex K tables, no restart
+# markers.  The device writes the entropy-coded scan; the header and EOI are put around it here.  Byte-equal to Pillow's
+# `save(format="JPEG", quality=q)`.
+ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36,
+          29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+_BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68,
+              109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_BASE_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+# the Annex K Huffman tables as DHT segment bodies: class/id, 16 counts, the symbols
+_DHT = (
+    bytes([0x00, 0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]) + bytes(range(12)),
+    bytes([0x10, 0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D]) + bytes.fromhex(
+        "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a434445464748494a"
+        "535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7"
+        "c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa"),
+    bytes([0x01, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0]) + bytes(range(12)),
+    bytes([0x11, 0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77]) + bytes.fromhex(
+        "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a434445464748"
+        "494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4"
+        "c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"),
+)
+assert all(len(t) == 17 + sum(t[1:17]) for t in _DHT)
+
+
+def _quality(quality):
+    q = int(quality)
+    if q != quality or not 1 <= q <= 100:
+        raise ValueError(f"quality must be an integer 1 .. 100, got {quality!r}")
+    return q
+
+
+def quality_tables(quality):
+    """libjpeg's quantisation tables for `quality` (1 .. 100): (luma, chroma), each [64] uint8 in natural order."""
+    q = _quality(quality)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(np.clip((np.asarray(base, dtype=np.int64) * scale + 50) // 100, 1, 255).astype(np.uint8) for base in (_BASE_LUMA, _BASE_CHROMA))
+
+
+def _segment(marker, body):
+    return bytes([0xFF, marker]) + (len(body) + 2).to_bytes(2, "big") + body
+
+
+def jfif_header(width, height, quality):
+    """Everything in front of the scan, in the order libjpeg (Pillow) writes it: SOI, APP0 (JFIF 1.1), two DQT, SOF0 (4:2:0), four DHT, SOS."""
+    if not (1 <= int(width) <= 65535 and 1 <= int(height) <= 65535):
+        raise ValueError(f"width and height must be 1 .. 65535, got {width} x {height}")
+    luma, chroma = quality_tables(quality)
+    zz = list(ZIGZAG)
+    out = b"\xff\xd8" + _segment(0xE0, b"JFIF\0" + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
+    out += _segment(0xDB, b"\0" + luma[zz].tobytes()) + _segment(0xDB, b"\1" + chroma[zz].tobytes())
+    out += _segment(0xC0, bytes([8]) + int(height).to_bytes(2, "big") + int(width).to_bytes(2, "big") + bytes([3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for table in _DHT:
+        out += _segment(0xC4, table)
+    return out + _segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 0x3F, 0]))
+
+
+def blocks_per_frame(width, height):
+    """8 x 8 blocks in a frame's scan, the dummy ones that fill the last MCUs included."""
+    return 6 * ((width + 15) // 16) * ((height + 15) // 16)
+
+
+def encode_scans(frames, tables, out, sizes, status, work, coef=None, bits=None):
+    """One `df3d_jpeg_encode_rgb` call on the current stream: frames [n, H, W, 3] uint8 cuda, contiguous -> out [n, capacity] uint8 (the scans),
+    sizes [n] int64, status [n] int32; `coef` [n, blocks, 64] int16 and `bits` [n, blocks] int32 take the stages when given."""
+    lib = _native.load()
+    n, h, w, _ = frames.shape
+    luma, chroma = (np.ascontiguousarray(t, dtype=np.uint8) for t in tables)
+    with torch.cuda.device(frames.device):
+        _native.check(
+            lib.df3d_jpeg_encode_rgb(frames.data_ptr(), n, h, w, luma.ctypes.data, chroma.ctypes.data, out.data_ptr(), out.shape[1], sizes.data_ptr(),
+                                     status.data_ptr(), work.data_ptr(), work.numel(), coef.data_ptr() if coef is not None else None,
+                                     bits.data_ptr() if bits is not None else None, torch.cuda.current_stream(frames.device).cuda_stream),
+            "df3d_jpeg_encode_rgb",
+        )
+
+
+class JpegFrameEncoder:
+    """Encodes batches of up to `batch` RGB frames of one size on the device and returns their JPEG files.  The work area, the output slots
+    and a pinned host buffer persist across calls.  Per batch: one launch sequence, then the sizes and the first `fetch` bytes of every slot
+    cross to the host behind one synchronisation (`fetch` is 1.25 x the largest scan seen so far; a batch that outgrows it costs one more copy).
+    The slots' capacity starts as a guess: a frame that does not fit is encoded again with the size the device reported, never truncated."""
+
+    def __init__(self, width, height, batch=16, quality=90, device=None, capacity=None):
+        _native.require_gpu()
+        self.lib = _native.load()
+        self.dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        if self.dev.type == "cuda" and self.dev.index is None:   # "cuda": the current device, by its index (tensors carry one)
+            self.dev = torch.device("cuda", torch.cuda.current_device())
+        self.w, self.h, self.batch, self.quality = int(width), int(height), int(batch), _quality(quality)
+        if self.batch < 1:
+            raise ValueError("batch must be at least 1")
+        self.tables = quality_tables(self.quality)
+        self.header = jfif_header(self.w, self.h, self.quality)
+        need = self.lib.df3d_jpeg_encode_work_bytes(self.batch, self.w, self.h)
+        if need == 0:
+            raise ValueError(f"a {self.w} x {self.h} frame is outside what the encoder takes: {self.lib.df3d_last_error().decode() or 'size'}")
+        self.work = torch.empty((need,), dtype=torch.uint8, device=self.dev)
+        self.meta = torch.zeros((2 * self.batch,), dtype=torch.int64, device=self.dev)   # sizes, then the statuses (int32) in the second half
+        self.meta_host = torch.zeros((2 * self.batch,), dtype=torch.int64).pin_memory()
+        self.retries = 0
+        self.largest = 0     # the largest scan seen so far
+        self._room(capacity if capacity is not None else self.w * self.h // 4 + 4096)
+
+    def _room(self, capacity):
+        self.capacity = (int(capacity) + 255) // 256 * 256
+        self.out = torch.empty((self.batch, self.capacity), dtype=torch.uint8, device=self.dev)
+        self.host = torch.empty((self.batch * self.capacity,), dtype=torch.uint8).pin_memory()
+
+    @property
+    def fetch(self):
+        """Bytes of every slot that cross to the host with the sizes: the whole slot until a scan has been seen, then 1.25 x the largest."""
+        if not self.largest:
+            return self.capacity
+        return min(self.capacity, max(4096, (self.largest + self.largest // 4 + 255) // 256 * 256))
+
+    def encode(self, frames):
+        """frames [n, H, W, 3] uint8 on the encoder's device, n <= batch -> [bytes, ...]: n whole JPEG files."""
+        if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4):
+            raise ValueError("frames must be a [n, H, W, 3] uint8 CUDA tensor")
+        if frames.device != self.dev or tuple(frames.shape[1:]) != (self.h, self.w, 3) or frames.shape[0] > self.batch:
+            raise ValueError(f"frames must be [<= {self.batch}, {self.h}, {self.w}, 3] on {self.dev}, got {list(frames.shape)} on {frames.device}")
+        n = frames.shape[0]
+        if n == 0:
+            return []
+        frames = frames.contiguous()
+        sizes, status = self.meta[:self.batch], self.meta[self.batch:].view(torch.int32)[:self.batch]
+        while True:
+            encode_scans(frames, self.tables, self.out, sizes, status, self.work)
+            self.meta_host.copy_(self.meta, non_blocking=True)
+            fetched = self.fetch
+            rows = self.host[:n * fetched].view(n, fetched)
+            rows.copy_(self.out[:n, :fetched], non_blocking=True)
+            torch.cuda.current_stream(self.dev).synchronize()
+            size = self.meta_host[:n].numpy()
+            biggest = int(size.max())
+            if biggest <= self.capacity:
+                break
+            self.retries += 1
+            self._room(biggest + biggest // 8)     # the reported size, and some room for the frames that follow
+        if biggest > fetched:                      # the guess of how much to fetch was too small for this batch
+            rows = self.host[:n * biggest].view(n, biggest)
+            rows.copy_(self.out[:n, :biggest])
+        self.largest = max(self.largest, biggest)
+        view = rows.numpy()
+        return [self.header + view[i, :int(size[i])].tobytes() + b"\xff\xd9" for i in range(n)]
+
+
+def encode_rgb(frames, quality=90):
+    """[n, H, W, 3] or [H, W, 3] uint8 cuda -> [bytes, ...]: the frames' baseline JPEG files (4:2:0), byte-equal to Pillow's at that quality."""
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() in (3, 4) and frames.shape[-1] == 3):
+        raise ValueError("frames must be a [n, H, W, 3] or [H, W, 3] uint8 CUDA tensor")
+    if frames.dim() == 3:
+        frames = frames[None]
+    n, h, w, _ = frames.shape
+    if n == 0:
+        return []
+    return JpegFrameEncoder(w, h, batch=n, quality=quality, device=frames.device).encode(frames)

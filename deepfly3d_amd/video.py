@@ -7,8 +7,9 @@ encodes them.  Here a frame is drawn by ONE kernel launch on the GPU (csrc/rende
 frames to the encoder:
 
     ffmpeg on PATH   -> raw RGB frames piped into `ffmpeg ... -c:v mpeg4`, the reference's file name  video_pose2d_<folder>.mp4
-    no ffmpeg        -> Motion-JPEG in an AVI container written here (Pillow encodes the frames): same stem, .avi -- this image has
-                        neither cv2 nor ffmpeg, and an MP4 muxer is outside the hot path
+    no ffmpeg        -> Motion-JPEG in an AVI container written here: same stem, .avi -- this image has neither cv2 nor ffmpeg, and an
+                        MP4 muxer is outside the hot path.  The frames are encoded on the device, 16 at a time (csrc/jpeg_encode.hip,
+                        DESIGN.md section 27): only the JPEG bytes cross to the host, and they are the bytes Pillow would have written
 
 Same layout, same file naming, same frame rate rule (--output-fps, else the camera videos' rate, else 30) as the reference; the
 drawing rule (joint discs over bone segments over the grey image; orthographic 3-D panels) is this build's own and is pinned by
@@ -179,10 +180,12 @@ class FfmpegWriter:
 
 
 class MjpegAviWriter:
-    """Motion-JPEG in a RIFF/AVI container: what can be written with this image's tools (Pillow) when ffmpeg is absent."""
+    """Motion-JPEG in a RIFF/AVI container: what can be written without ffmpeg.  `write_jpeg` takes a finished JPEG file (the video
+    functions encode their frames on the device, jpeg.JpegFrameEncoder); `write` takes an RGB array and has Pillow encode it.  The two give
+    the same file.  `device_encode=False` asks the video functions for the Pillow route."""
 
-    def __init__(self, path, width, height, fps, quality=90):
-        self.path, self.w, self.h, self.fps, self.q = path, width, height, float(fps), quality
+    def __init__(self, path, width, height, fps, quality=90, device_encode=True):
+        self.path, self.w, self.h, self.fps, self.q, self.device_encode = path, width, height, float(fps), quality, bool(device_encode)
         self.f = open(path, "wb")
         self.index = []
         self.limit = (1 << 32) - (1 << 24)   # a plain RIFF/AVI carries 32-bit sizes and idx1 offsets: stop 16 MiB short of 4 GiB
@@ -197,7 +200,10 @@ class MjpegAviWriter:
 
         buf = io.BytesIO()
         Image.fromarray(frame).save(buf, format="JPEG", quality=self.q)
-        data = buf.getvalue()
+        self.write_jpeg(buf.getvalue())
+
+    def write_jpeg(self, data):
+        """One frame, already encoded: a baseline JPEG file of the writer's size."""
         pad = len(data) & 1
         if self.f.tell() + 8 + len(data) + pad + 16 * (len(self.index) + 1) + 8 > self.limit:
             raise RuntimeError(f"{self.path}: the Motion-JPEG fallback writes a plain RIFF/AVI, which ends at 4 GiB ({len(self.index)} frames written so far); "
@@ -230,14 +236,52 @@ class MjpegAviWriter:
         self.f.close()
 
 
-def open_writer(stem, width, height, fps):
-    """The encoder for `<stem>.mp4` (ffmpeg) or, without ffmpeg, `<stem>.avi` (Motion-JPEG).  Returns (writer, path)."""
+def open_writer(stem, width, height, fps, quality=90, device_encode=True):
+    """The encoder for `<stem>.mp4` (ffmpeg) or, without ffmpeg, `<stem>.avi` (Motion-JPEG at JPEG quality `quality`, its frames encoded
+    on the device unless `device_encode=False`).  Returns (writer, path)."""
     if shutil.which("ffmpeg"):
         path = stem + ".mp4"
         return FfmpegWriter(path, width, height, fps), path
     path = stem + ".avi"
     logger.warning(f"ffmpeg is not on PATH: writing Motion-JPEG to {path} instead of the reference's .mp4")
-    return MjpegAviWriter(path, width, height, fps), path
+    return MjpegAviWriter(path, width, height, fps, quality=quality, device_encode=device_encode), path
+
+
+ENCODE_BATCH = 16   # device frames per JPEG-encoder call
+
+
+def _write_frames(writer, frames, width, height, device, progress=None):
+    """Every (img_id, [height, width, 3] uint8 cuda) of `frames` into `writer`.  The Motion-JPEG writer gets JPEG files encoded on the device,
+    ENCODE_BATCH frames per call; any other writer (and `device_encode=False`) gets the RGB frames through one pinned host buffer."""
+    if isinstance(writer, MjpegAviWriter) and writer.device_encode:
+        from . import jpeg
+
+        dev = torch.device(device)
+        encoder = jpeg.JpegFrameEncoder(width, height, batch=ENCODE_BATCH, quality=writer.q, device=dev)
+        stage = torch.empty((ENCODE_BATCH, height, width, 3), dtype=torch.uint8, device=dev)
+        held = 0
+
+        def flush():
+            for data in encoder.encode(stage[:held]):
+                writer.write_jpeg(data)
+                if progress is not None:
+                    progress()
+
+        for _, frame in frames:
+            stage[held].copy_(frame)    # (the renderers reuse their output buffers)
+            held += 1
+            if held == ENCODE_BATCH:
+                flush()
+                held = 0
+        if held:
+            flush()
+        return
+    host = torch.empty((height, width, 3), dtype=torch.uint8).pin_memory()
+    for _, frame in frames:
+        host.copy_(frame)
+        writer.write(host.numpy())
+        if progress is not None:
+            progress()
 
 
 def read_mjpeg_avi(path):
@@ -290,29 +334,26 @@ def _video_stem(core, kind):
     return os.path.join(core.output_folder, f"video_{kind}_" + core.input_folder.replace("/", "_"))
 
 
-def make_pose2d_video(core, fps=None, progress=None, smooth=False):
+def make_pose2d_video(core, fps=None, progress=None, smooth=False, quality=90, device_encode=True):
     """video_pose2d_<folder>: per image the 2 x 3 camera grid with the 2-D pose drawn on it (reference video.py:21-49).  Returns the path.
-    `smooth=True` draws the temporally smoothed detections; the default draws the detections themselves."""
+    `smooth=True` draws the temporally smoothed detections; the default draws the detections themselves.
+    `quality` (1 .. 100) and `device_encode` act on the Motion-JPEG path only (open_writer)."""
     fps = fps or DEFAULT_FPS
     W, H = core.image_shape
     renderer = FrameRenderer(H, W, config["num_joints"], core.device)
-    writer, path = open_writer(_video_stem(core, "pose2d"), 3 * W, 2 * H, fps)
-    host = torch.empty((2 * H, 3 * W, 3), dtype=torch.uint8).pin_memory()
+    writer, path = open_writer(_video_stem(core, "pose2d"), 3 * W, 2 * H, fps, quality=quality, device_encode=device_encode)
     try:
-        for _, frame in _grid_frames(core, renderer, smooth=smooth):
-            host.copy_(frame)
-            writer.write(host.numpy())
-            if progress is not None:
-                progress()   # (multi-rank: rank 0's heartbeat to the waiting peers, distributed.primary_section)
+        # (progress: multi-rank, rank 0's heartbeat to the waiting peers, distributed.primary_section)
+        _write_frames(writer, _grid_frames(core, renderer, smooth=smooth), 3 * W, 2 * H, renderer.dev, progress)
     finally:
         writer.close()
     logger.info(f"Video created at {path}\n")
     return path
 
 
-def make_pose3d_video(core, fps=None, progress=None):
+def make_pose3d_video(core, fps=None, progress=None, quality=90, device_encode=True):
     """video_pose3d_<folder>: two rows of the six camera images with their 2-D pose (200 x 100 each) over a row of three 3-D views of
-    the pose `Core.get_points3d` returns (reference video.py:52-82).  Returns the path."""
+    the pose `Core.get_points3d` returns (reference video.py:52-82).  Returns the path.  `quality`, `device_encode`: as in make_pose2d_video."""
     fps = fps or DEFAULT_FPS
     W, H = core.image_shape
     renderer = FrameRenderer(H, W, config["num_joints"], core.device)
@@ -320,16 +361,16 @@ def make_pose3d_video(core, fps=None, progress=None):
     sh, sw = SMALL_2D
     fw, fh = 3 * sw, 2 * sh + PANEL_SIZE
     frame = torch.empty((fh, fw, 3), dtype=torch.uint8, device=renderer.dev)
-    writer, path = open_writer(_video_stem(core, "pose3d"), fw, fh, fps)
-    host = torch.empty((fh, fw, 3), dtype=torch.uint8).pin_memory()
-    try:
+    writer, path = open_writer(_video_stem(core, "pose3d"), fw, fh, fps, quality=quality, device_encode=device_encode)
+
+    def frames():
         for i, grid in _grid_frames(core, renderer):
             renderer.resize(grid, frame[: 2 * sh])
             renderer.panels3d(pose[i].contiguous(), out=frame[2 * sh:])
-            host.copy_(frame)
-            writer.write(host.numpy())
-            if progress is not None:
-                progress()   # (multi-rank: rank 0's heartbeat to the waiting peers, distributed.primary_section)
+            yield i, frame
+
+    try:
+        _write_frames(writer, frames(), fw, fh, renderer.dev, progress)
     finally:
         writer.close()
     logger.info(f"Video created at {path}\n")
@@ -362,23 +403,18 @@ def _heatmap_frames(core, renderer, batch=16, joints=()):
             yield i, renderer.heatmap_grid(luma[k], hm[k], core.camera_ordering, joints)
 
 
-def make_heatmap_video(core, fps=None, progress=None, joints=()):
+def make_heatmap_video(core, fps=None, progress=None, joints=(), quality=90, device_encode=True):
     """video_heatmap_<folder>: per image the 2 x 3 camera grid of the pose-2d video with the network's heat-maps drawn on the images
     instead of the pose.  Needs the images and the weights only, not a pose.  `joints` restricts the drawing to
-    those ids of the 38-joint layout.  Returns the path."""
+    those ids of the 38-joint layout.  Returns the path.  `quality`, `device_encode`: as in make_pose2d_video."""
     if not core.has_heatmap:
         raise FileNotFoundError(f"the heat-map video is computed from the images, and {core.input_folder} holds none (deleted with --delete-images?)")
     fps = fps or DEFAULT_FPS
     W, H = core.image_shape
     renderer = FrameRenderer(H, W, config["num_joints"], core.device)
-    writer, path = open_writer(_video_stem(core, "heatmap"), 3 * W, 2 * H, fps)
-    host = torch.empty((2 * H, 3 * W, 3), dtype=torch.uint8).pin_memory()
+    writer, path = open_writer(_video_stem(core, "heatmap"), 3 * W, 2 * H, fps, quality=quality, device_encode=device_encode)
     try:
-        for _, frame in _heatmap_frames(core, renderer, joints=joints):
-            host.copy_(frame)
-            writer.write(host.numpy())
-            if progress is not None:
-                progress()   # (multi-rank: rank 0's heartbeat to the waiting peers, distributed.primary_section)
+        _write_frames(writer, _heatmap_frames(core, renderer, joints=joints), 3 * W, 2 * H, renderer.dev, progress)
     finally:
         writer.close()
     logger.info(f"Video created at {path}\n")

@@ -106,6 +106,30 @@ int df3d_read_files(const char* const* paths, int n, unsigned char* dst, size_t 
                     size_t* total_bytes, int threads);
 
 /* ------------------------------------------------------------------------------------------------
+ * a1' JPEG encoder: n RGB frames -> the entropy-coded scans of their baseline JPEG files, on
+ *     the device; libjpeg's arithmetic (integer colour conversion, 4:2:0 with the h2v2 downsampler, the "islow"
+ *     forward DCT, the Annex K Huffman tables, no restart markers), byte-equal to libjpeg's scan.  The header
+ *     (SOI .. SOS) and EOI are the host's (deepfly3d_amd/jpeg.py: jfif_header).
+ * rgb_dev     [n, h, w, 3] uint8, packed; w and h 1 .. 65535.  Rows are read as dwords where 3 w is a multiple of 4
+ *             and rgb_dev is 4-byte aligned, as bytes otherwise
+ * qtab_luma, qtab_chroma   [64] host, natural order, every entry 1 .. 255
+ * out_dev     [n, out_capacity_per_frame] uint8: frame i's scan starts at i * out_capacity_per_frame
+ * sizes_dev   [n] int64: frame i's true scan size, also where it exceeds the capacity
+ * status_dev  [n] int32: 0 ok, 1 the scan did not fit (nothing is written past the frame's slot; encode again with
+ *             sizes_dev[i] bytes of room)
+ * work_dev    >= df3d_jpeg_encode_work_bytes(n, w, h) bytes, 256-byte aligned (0 is returned for arguments the
+ *             encoder refuses)
+ * coef_out_dev  optional [n, blocks, 64] int16, 4-byte aligned (may be NULL): the quantised coefficients in zigzag
+ *             order, blocks in scan order (per MCU: Y00 Y01 Y10 Y11 Cb Cr; blocks = 6 ceil(w/16) ceil(h/16)), dummy
+ *             blocks filled by libjpeg's rule
+ * bits_out_dev  optional [n, blocks] int32 (may be NULL): entropy-coded bits per block
+ * ---------------------------------------------------------------------------------------------- */
+size_t df3d_jpeg_encode_work_bytes(int n, int w, int h);
+int df3d_jpeg_encode_rgb(const unsigned char* rgb_dev, int n, int h, int w, const unsigned char* qtab_luma, const unsigned char* qtab_chroma,
+                         unsigned char* out_dev, size_t out_capacity_per_frame, long long* sizes_dev, int* status_dev, void* work_dev, size_t work_bytes,
+                         short* coef_out_dev, int* bits_out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a3  heat-map -> point + confidence.   Replaces df2d's heatmap2points / confidence extraction behind
  *     inference_folder(..., return_confidence=True)          (reference df3d/core.py:177-185,
  *     semantics reference README.md:404: arg-max over (h, w), confidence = the max value).
