@@ -155,6 +155,12 @@ PROTOTYPES = {
     "df3d_triangulate_heatmaps": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_double), POINTER(ctypes.c_ubyte), POINTER(c_int),
                                           c_int, c_void_p, c_double, c_int, c_double, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "df3d_sync_work_bytes": (c_longlong, [c_int, c_longlong, c_int]),
+    "df3d_sync_pair_costs": (c_int, [POINTER(c_double), POINTER(c_int), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_void_p,
+                                     c_void_p, c_void_p]),
+    "df3d_sync_paths": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_int, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_longlong, c_void_p]),
+    "df3d_sync_apply": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "df3d_ba_eval": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_colsq": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "df3d_ba_matvec": (c_int, [POINTER(BAProblem), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -42,6 +42,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # heatmap3d.hip: the projection, the Catmull-Rom weights, the taps' sums and the score of the heat-map triangulation are
 # the operations of tests/heatmap3d_oracle.py one by one: the arg-max of a level is compared exactly wherever the oracle's two best scores
 # lie further apart than the logarithm's rounding
+# sync.hip: the Sampson distance of the camera-lag model is the float64 operations of tests/sync_oracle.py one by
+# one, rounded once to int64; everything after that is integer arithmetic, compared exactly
 # preprocess.hip and hourglass.hip, the two users of csrc/preprocess_math.h: the front-end's per-pixel arithmetic carries
 # `#pragma clang fp contract(off)` so that (v / 255 - mean) / std and the bilinear taps round like the numpy statement, and an explicit
 # -ffp-contract=fast DISREGARDS that pragma (the compiler fused v * (1 / 255) - mean and the taps).  fast-honor-pragmas, hipcc's own
@@ -51,6 +53,7 @@ FILE_FLAGS = {"pose3d.hip": ["-ffp-contract=off"], "ba_lsmr.hip": ["-ffp-contrac
               "subpixel.hip": ["-ffp-contract=off"], "behaviour_segment.hip": ["-ffp-contract=off"], "gait.hip": ["-ffp-contract=off"],
               "pose_repair.hip": ["-ffp-contract=off"], "treadmill.hip": ["-ffp-contract=off"], "track.hip": ["-ffp-contract=off"],
               "consensus.hip": ["-ffp-contract=off"], "trajectory.hip": ["-ffp-contract=off"], "heatmap3d.hip": ["-ffp-contract=off"],
+              "sync.hip": ["-ffp-contract=off"],
               "preprocess.hip": ["-ffp-contract=fast-honor-pragmas"], "hourglass.hip": ["-ffp-contract=fast-honor-pragmas"]}
 
 

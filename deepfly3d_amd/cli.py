@@ -233,7 +233,48 @@ def parse_cli_args(argv=None):
     p.add_argument("--heatmap-floor", dest="heatmap_floor", type=float, default=None, metavar="E",
                    help="With --heatmap-triangulation: the heat-map value at and below which a cell says nothing, between 0 and 1 "
                         "(default 1e-3, a guess)")
+    p.add_argument("--check-sync", dest="check_sync", action="store_true",
+                   help="Check that frame t of every camera shows the same instant: for every pair of cameras that see a common joint, the "
+                        "detections of one camera are compared with the other's up to --sync-max-lag frames earlier and later, by their "
+                        "distance to the pair's epipolar lines, per window of --sync-window frames; a camera that dropped a frame shows "
+                        "up as a lag from that window on.  Needs only the detections and the calibration.  Appends, after every other "
+                        "key, sync_lag [7, nW] (camera c shows instant t in its frame t + lag), sync_status [7] (0 the camera shares no "
+                        "joint with another, 1 in step, 2 lagging somewhere), sync_pairs, sync_pair_lag, sync_pair_margin, "
+                        "sync_pair_inconsistency, sync_pair_cost, sync_pair_count and sync_params to the result, and logs one line per "
+                        "lagging camera.  Lags are relative within a group of cameras that share joints: a lag between the left and the "
+                        "right cameras cannot be seen.  The defaults are guesses that nobody has measured on a recording.  Works with "
+                        "--skip-pose-estimation on an earlier result")
+    p.add_argument("--sync-cameras", dest="sync_cameras", action="store_true",
+                   help="--check-sync, and undo the lags before triangulating: camera c's detection of instant t is taken from its frame "
+                        "t + lag (unseen where that frame does not exist); points2d and every later stage of the save hold the shifted "
+                        "detections, and the originals are kept as points2d_unsynced.  Not with --auto-correct, --track-2d, "
+                        "--heatmap-triangulation or --video-heatmap, which read heat-maps by frame index")
+    p.add_argument("--sync-max-lag", dest="sync_max_lag", type=int, default=None, metavar="N",
+                   help="With --check-sync or --sync-cameras: the largest lag searched, in frames, 0 to 64 (default 8)")
+    p.add_argument("--sync-window", dest="sync_window", type=int, default=None, metavar="W",
+                   help="With --check-sync or --sync-cameras: the frames of a window, >= 1 (default 256): a lag is constant inside one")
+    p.add_argument("--sync-tau", dest="sync_tau", type=float, default=None, metavar="PX",
+                   help="With --check-sync or --sync-cameras: the epipolar distance, in pixels, at which a sample's cost is truncated "
+                        "(default 20, a guess)")
+    p.add_argument("--sync-switch", dest="sync_switch", type=float, default=None, metavar="K",
+                   help="With --check-sync or --sync-cameras: the cost, in px^2 per frame of lag, of changing the lag between neighbouring "
+                        "windows (default 64, a guess): a window without motion then keeps its neighbours' lag")
     args = p.parse_args(argv)
+    for name in ("max_lag", "window", "tau", "switch"):
+        if getattr(args, "sync_" + name) is not None and not (args.check_sync or args.sync_cameras):
+            p.error(f"--sync-{name.replace('_', '-')} sets a parameter of --check-sync and --sync-cameras: it needs one of them")
+    if args.check_sync or args.sync_cameras:
+        from . import sync
+
+        try:
+            sync.sync_params(args.sync_max_lag, args.sync_window, args.sync_tau, args.sync_switch)
+        except ValueError as e:
+            p.error(f"--sync-max-lag, --sync-window, --sync-tau and --sync-switch: {e}")
+    if args.sync_cameras:
+        for flag in ("auto_correct", "track_2d", "heatmap_triangulation", "video_heatmap"):
+            if getattr(args, flag, False):
+                p.error(f"--sync-cameras shifts the detections' frames, and --{flag.replace('_', '-')} reads the heat-maps by frame index: "
+                        "they cannot be combined")
     for name in ("half", "levels", "floor"):
         if getattr(args, "heatmap_" + name) is not None and not args.heatmap_triangulation:
             p.error(f"--heatmap-{name} sets a parameter of --heatmap-triangulation: it needs --heatmap-triangulation")
@@ -395,6 +436,11 @@ def run(args):
         flagged.append("heatmap_triangulation")
         extras.update(heatmap_triangulation=True, heatmap_half=getattr(args, "heatmap_half", None), heatmap_levels=getattr(args, "heatmap_levels", None),
                       heatmap_floor=getattr(args, "heatmap_floor", None))
+    if getattr(args, "check_sync", False) or getattr(args, "sync_cameras", False):   # after the heat-map keys
+        flagged.append("sync_cameras" if getattr(args, "sync_cameras", False) else "check_sync")
+        extras.update(check_sync=True, sync_cameras=getattr(args, "sync_cameras", False), sync_max_lag=getattr(args, "sync_max_lag", None),
+                      sync_window=getattr(args, "sync_window", None), sync_tau=getattr(args, "sync_tau", None),
+                      sync_switch=getattr(args, "sync_switch", None))
     if args.skip_estimation and not args.video_2d and not args.video_3d and not video_heatmap and not flagged:
         logger.info("Nothing to do. Check your command-line arguments.")
         return 0

@@ -120,6 +120,25 @@ HEATMAP3D_LEVELS = 4
 HEATMAP3D_LEVELS_RANGE = (1, 6)
 HEATMAP3D_FLOOR = 1e-3
 
+# ---- per-camera frame lags from epipolar consistency: for every pair of cameras that share a joint, camera a's
+# frame t is paired with camera b's frame t + d for every lag |d| <= SYNC_MAX_LAG; the squared Sampson distance of every such sample
+# against the pair's fundamental matrix, truncated at SYNC_TAU^2 (pixels; the consensus stage's guess), is summed per window of
+# SYNC_WINDOW frames, and the lag of a pair is the path through the windows that minimises those sums plus SYNC_SWITCH (px^2) per frame
+# of lag changed between neighbouring windows.  A pair exists when both cameras detect some joint in at least SYNC_MIN_COUNT frames,
+# and a window's margin is reported only where the chosen lag has that many samples.  SYNC_SWITCH and SYNC_MIN_COUNT were chosen on the
+# planted recordings of tests/sync_cases.py (section 28 holds the margins); all five are guesses: nobody has measured them on a
+# recording.
+SYNC_MAX_LAG = 8
+SYNC_MAX_LAG_RANGE = (0, 64)
+SYNC_WINDOW = 256
+SYNC_TAU = 20.0
+SYNC_TAU_MAX = 4096.0
+SYNC_SWITCH = 64.0
+SYNC_SWITCH_MAX = float(1 << 24)
+SYNC_MIN_COUNT = 16
+SYNC_COST_SCALE = 1024   # an integer cost is the squared Sampson distance in units of 2^-10 px^2 (csrc/sync.hip: COST_SCALE)
+SYNC_MAX_FRAMES = 1 << 20
+
 
 # ---- leg joint angles.  Leg L = 3 side + l (l = 0, 1, 2: front, mid, hind) owns the five joints
 # 19 side + 5 l + k; its eight angles come in this order: thorax-coxa yaw, pitch and roll, coxa-trochanter pitch and roll,

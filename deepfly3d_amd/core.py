@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _native, logger, ops
+from . import sync as sync_mod
 from . import bundle_adjust as _ba
 from . import config as config_mod
 from .camera_network import CameraNetwork
@@ -444,6 +445,52 @@ class Core:
         if joint_id is not None:
             return [int(c) for c in np.nonzero(rejected[:, int(joint_id)])[0]]
         return {int(j): [int(c) for c in np.nonzero(rejected[:, j])[0]] for j in np.nonzero(rejected.any(axis=0))[0]}
+
+    # -- camera frame lags: a rank-0 method on the detections save() triangulates ------------------------------------
+    _SYNC_KEYS = ("sync_lag", "sync_status", "sync_pairs", "sync_pair_lag", "sync_pair_margin", "sync_pair_inconsistency", "sync_pair_cost",
+                  "sync_pair_count", "sync_params")
+
+    def _sync_on(self, what, params):
+        """The sync.SyncResult on the device of the camera network's detections, with the refusals of _robust_on.  `params`:
+        sync.sync_params' values."""
+        from . import distributed as dd
+
+        if dd.current()[0] != 0:
+            raise RuntimeError(f"{what} is a rank-0 method: the camera network lives on rank 0")
+        if self.camNet is None or not self.camNet.has_calibration():
+            raise RuntimeError(f"{what} needs calibrated cameras: run calibrate_calc() first")
+        _native.require_gpu()
+        dev = torch.device(self.device if self.device is not None else f"cuda:{torch.cuda.current_device()}")
+        P = np.stack([c.P for c in self.camNet.cam_list])
+        px = torch.from_numpy(np.ascontiguousarray(self.camNet.points2d, dtype=np.float64)).to(dev)
+        return sync_mod.camera_sync(P, px, *params)
+
+    def camera_sync(self, **params):
+        """The frame lag of every camera from the epipolar consistency of the camera network's detections -- the ones save()
+        triangulates -- and the calibration (sync.camera_sync), a sync.SyncResult of numpy arrays: lag [7, nW]
+        int32 (camera c shows instant t in its frame t + lag[c, t // window]), status [7] int8 (0 unobservable, 1 in step throughout, 2
+        lagging somewhere), pairs, pair_lag, pair_margin, pair_inconsistency, pair_cost, pair_count, path_cost, F, points2d_px
+        [7, T, 38, 2] (the detections with the lags undone, pixels) and params.  `params`: max_lag, window, tau, switch, min_count
+        (sync.sync_params; the defaults are guesses nobody has measured on a recording).  Lags are relative within a group of cameras that
+        share joints: one between the left and the right cameras cannot be seen.  A rank-0 method with the refusals of the
+        reprojection-error queries."""
+        r = self._sync_on("camera_sync", sync_mod.sync_params(**params))   # refused before any work
+        return dataclasses.replace(r, **{f.name: getattr(r, f.name).cpu().numpy() for f in dataclasses.fields(r)
+                                         if isinstance(getattr(r, f.name), torch.Tensor)})
+
+    def _sync_keys(self, r):
+        """The result keys of a SyncResult, in their order, and one log line per lagging camera."""
+        host = lambda t: t.cpu().numpy()   # noqa: E731
+        cost, count = host(r.pair_cost), host(r.pair_count)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean = cost.astype(np.float64) / count.astype(np.float64) / float(config_mod.SYNC_COST_SCALE)
+        window = r.params[1]
+        for c in np.nonzero(r.status == 2)[0]:
+            for w in range(r.lag.shape[1]):
+                if r.lag[c, w] != (r.lag[c, w - 1] if w else 0):
+                    logger.warning(f"camera {c} lags by {int(r.lag[c, w]):+d} frames from frame {w * window} on")
+        return dict(zip(self._SYNC_KEYS, (r.lag, r.status, r.pairs, host(r.pair_lag), host(r.pair_margin), r.pair_inconsistency, mean, count,
+                                          np.array(r.params, dtype=np.float64))))
 
     # -- trajectory triangulation (DESIGN.md section 24): a rank-0 method on the detections save() triangulates ------------------------------
     def _trajectory_on(self, what, params, X=None, robust=None):
@@ -961,6 +1008,7 @@ class Core:
     def save(self, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False, behaviour_perplexity=None,
              behaviour_segments=False, behaviour_sigma=None, behaviour_grid=None, gait=False, gait_on=None, gait_off=None, repair_pose=False,
              repair_window=None, repair_threshold=None, repair_floor=None, repair_max_gap=None, treadmill=False, ball_radius=None,
+             check_sync=False, sync_cameras=False, sync_max_lag=None, sync_window=None, sync_tau=None, sync_switch=None, sync_min_count=None,
              heatmap_triangulation=False, heatmap_half=None, heatmap_levels=None, heatmap_floor=None,
              trajectory_triangulation=False, trajectory_lambda=None, trajectory_huber=None, trajectory_max_gap=None,
              robust_triangulation=False, robust_tau=None, robust_min_views=None):
@@ -1020,13 +1068,25 @@ class Core:
         points3d_wo_procrustes, "heatmap3d_status" [T, 38] int8, "heatmap3d_score" [T, 38], "heatmap3d_views" [T, 38] int32,
         "heatmap3d_shift" [T, 38], "heatmap3d_counts" [38, 4] and "heatmap3d_params" (half, levels, floor, grid).  The stages run in the
         order robust, trajectory, heat-map, repair: the search starts from the latest pose of the save, and every other opt-in key
-        of the same save is computed from the heat-map pose (repaired afterwards with repair_pose), which is computed once."""
+        of the same save is computed from the heat-map pose (repaired afterwards with repair_pose), which is computed once.
+        `check_sync=True` appends, after every other key (after the heat-map keys), the frame lags of the cameras (Core.camera_sync()
+        with `sync_max_lag`, `sync_window`, `sync_tau`, `sync_switch` and `sync_min_count`; the defaults are guesses nobody has measured
+        on a recording): "sync_lag" [7, nW] int32 (camera c shows instant t in its frame t + lag[c, t // window]), "sync_status" [7] int8
+        (0 unobservable, 1 in step throughout, 2 lagging somewhere), "sync_pairs" [npair, 2], "sync_pair_lag" [npair, nW],
+        "sync_pair_margin" [npair, nW] (px^2), "sync_pair_inconsistency" [npair, nW], "sync_pair_cost" [npair, nW, 2 max_lag + 1]
+        (float64 px^2: the mean cost of a sample, NaN without one), "sync_pair_count" and "sync_params" (max_lag, window, tau, switch,
+        min_count), and logs one line per lagging camera.  `sync_cameras=True` (it implies check_sync) also undoes the lags before the
+        triangulation: "points2d", the triangulation and every later stage of this save hold the shifted detections (zeros where a
+        camera has no such frame), and the originals follow the sync keys as "points2d_unsynced".  The object's own detections stay as
+        they were.  Not after auto_correct() or track_detections() and not with heatmap_triangulation: those read heat-maps by frame
+        index."""
         from . import distributed as dd
         from . import heatmap3d
 
         # a collective: every rank takes part.  After auto_correct() the peers hold only their raw (uncorrected) shards, so rank 0
         # triangulates every frame itself -- every rank knows that it ran (the flag is set on all of them) and takes this branch
-        pts3d_sharded = self._triangulate_sharded() if dd.current()[1] > 1 and not getattr(self, "_corrected", False) else None
+        # (with sync_cameras too: the detections it triangulates are the shifted ones, which only rank 0 computes)
+        pts3d_sharded = self._triangulate_sharded() if dd.current()[1] > 1 and not getattr(self, "_corrected", False) and not sync_cameras else None
         error = None
         if behaviour_segments and not behaviour_map:
             raise ValueError("behaviour_segments segments the map behaviour_map computes: it needs behaviour_map=True")
@@ -1057,6 +1117,14 @@ class Core:
         if not heatmap_triangulation and any(v is not None for v in (heatmap_half, heatmap_levels, heatmap_floor)):
             raise ValueError("heatmap_half, heatmap_levels and heatmap_floor belong to heatmap_triangulation: they need heatmap_triangulation=True")
         heatmap = heatmap3d.heatmap3d_params(heatmap_half, heatmap_levels, heatmap_floor) if heatmap_triangulation else None   # refused before any work
+        if not (check_sync or sync_cameras) and any(v is not None for v in (sync_max_lag, sync_window, sync_tau, sync_switch, sync_min_count)):
+            raise ValueError("sync_max_lag, sync_window, sync_tau, sync_switch and sync_min_count belong to check_sync and sync_cameras: "
+                             "they need one of them")
+        if sync_cameras and (heatmap_triangulation or getattr(self, "_corrected", False)):
+            raise ValueError("sync_cameras shifts the detections' frames: it cannot follow auto_correct() or track_detections() or be combined "
+                             "with heatmap_triangulation, which read heat-maps by frame index")
+        sync = ((sync_mod.sync_params(sync_max_lag, sync_window, sync_tau, sync_switch, sync_min_count), bool(sync_cameras))
+                if check_sync or sync_cameras else None)   # refused before any work
         segments = (behaviour_sigma, behaviour_grid) if behaviour_segments else None
         if segments is not None:   # refused before any work
             if behaviour_grid is not None:
@@ -1066,17 +1134,44 @@ class Core:
         if self.is_primary:
             try:
                 self._write_result(pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity, segments, gait,
-                                   repair, treadmill, robust, trajectory, heatmap)
+                                   repair, treadmill, robust, trajectory, heatmap, sync)
             except Exception as e:  # noqa: BLE001  (ENOSPC, a failing Procrustes, ...: re-raised by agree, on every rank)
                 error = e
         dd.agree(error, "save")   # rank 0 failing here must not leave its peers in the NEXT step's collectives alone
 
     def _write_result(self, pts3d_sharded=None, joint_angles=False, rigid_legs=False, angle_spectrogram=False, behaviour_map=False,
                       behaviour_perplexity=None, segments=None, gait=None, repair=None, treadmill=None, robust=None, trajectory=None,
-                      heatmap=None):
+                      heatmap=None, sync=None):
         if behaviour_map and getattr(self, "num_images", None) is not None:   # too short for the perplexity: refused before any work
             ops.behaviour_map_points(self.num_images, behaviour_perplexity)
-        result = {"points2d": np.copy(self.points2d)}
+        if sync is None:
+            return self._write_result_of(np.copy(self.points2d), {}, pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map,
+                                         behaviour_perplexity, segments, gait, repair, treadmill, robust, trajectory, heatmap)
+        r = self._sync_on("sync_cameras" if sync[1] else "check_sync", sync[0])
+        sync_keys = self._sync_keys(r)
+        if not sync[1]:
+            return self._write_result_of(np.copy(self.points2d), sync_keys, pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram,
+                                         behaviour_map, behaviour_perplexity, segments, gait, repair, treadmill, robust, trajectory, heatmap)
+        # the same gather on the normalised detections (exact: no arithmetic) is the result's "points2d"; the camera network holds the
+        # shifted pixels while this save runs, so that every stage reads them, and gets its own back whatever happens
+        shifted = sync_mod.apply_sync(torch.from_numpy(np.ascontiguousarray(self.points2d, dtype=np.float64)).to(r.points2d_px.device), r.lag,
+                                 r.params[1]).cpu().numpy()
+        sync_keys["points2d_unsynced"] = np.copy(self.points2d)
+        own = np.copy(self.camNet.points2d)
+        np.copyto(self.camNet.points2d, r.points2d_px.cpu().numpy())
+        r = None
+        try:
+            return self._write_result_of(shifted, sync_keys, None, joint_angles, rigid_legs, angle_spectrogram, behaviour_map,
+                                         behaviour_perplexity, segments, gait, repair, treadmill, robust, trajectory, heatmap)
+        finally:
+            np.copyto(self.camNet.points2d, own)
+            self.camNet.triangulate()   # as every other save leaves it: the triangulation of the object's own detections
+
+    def _write_result_of(self, points2d, sync_keys, pts3d_sharded, joint_angles, rigid_legs, angle_spectrogram, behaviour_map, behaviour_perplexity,
+                         segments, gait, repair, treadmill, robust, trajectory, heatmap):
+        """_write_result on `points2d` (normalised, the result's key; the camera network holds the same in pixels); `sync_keys` follow
+        every other key."""
+        result = {"points2d": points2d}
         if self.camNet is not None and self.camNet.has_calibration():
             if pts3d_sharded is not None:
                 self.camNet.points3d = pts3d_sharded
@@ -1104,6 +1199,7 @@ class Core:
                                                repair, treadmill, robust, trajectory, heatmap))
         if getattr(self, "_ba_robust", None) is not None:   # only after a robust calibration: else the schema is what it was
             result.update(self._ba_robust)
+        result.update(sync_keys)
         with open(self.save_path, "wb") as f:
             pickle.dump(result, f)
         print(f"Saved results at: {self.save_path}")

@@ -698,6 +698,36 @@ int df3d_triangulate_heatmaps(const float* hm_dev, int n, int V, int C, int H, i
                               int* views_dev, double* shift_dev, int* choice_dev, long long* counts_dev, signed char* path_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a23 per-camera frame lags from epipolar consistency (the model is this project's own specification, stated in
+ *     numpy / int64 by tests/sync_oracle.py).  pts_px_dev [ncam, T, J, 2] (row_px, col_px); pairs_host [npair, 2] HOST int32, cameras
+ *     a < b; F_host [npair, 9] HOST float64, row-major, x_b^T F x_a = 0 with x = (col_px, row_px, 1).  Lag d in [-D, D] pairs camera
+ *     a's frame t with camera b's frame t + d for every joint; the sample is valid when neither detection has a zero coordinate and
+ *     0 <= t + d < T.  l = F x_a, m = F^T x_b, s = x_b . l, e = s s / (l0 l0 + l1 l1 + m0 m0 + m1 m1), every sum left to right and every
+ *     product rounded on its own; a sample whose denominator is 0 is skipped; its cost is q = floor(min(e, tau tau) 2^10 + 0.5) as
+ *     int64 (a NaN costs tau tau).  The window of a sample is t / W, nW = ceil(T / W).
+ * df3d_sync_pair_costs: cost_dev, count_dev [npair, nW, 2 D + 1] int64: the sum of q and the number of valid samples; index d + D.
+ * df3d_sync_paths: per pair the lags d_0 .. d_{nW - 1} that minimise sum cost[w, d_w] + switch_q sum |d_w - d_{w - 1}|, an exact
+ *     Viterbi on int64; ties, for a predecessor and for the last state, go to the smaller (|d|, d).  lag_dev [npair, nW] int32;
+ *     path_cost_dev [npair] int64 (the minimum); margin_dev [npair, nW] float64, px^2: the smallest cost / count / 2^10 over the lags
+ *     d != d_w with a sample, minus that of d_w (+inf where no other lag has one); NaN where the count at d_w is 0 or below
+ *     min_count.  work_dev: df3d_sync_work_bytes(npair, nW, D) bytes (a byte per window and state; 0 for arguments out of range).
+ * df3d_sync_apply: out_dev [ncam, T, J, 2]: camera c's frame t + lag_cam[c, t / W], zeros where that frame does not exist.
+ *     lag_cam_dev [ncam, nW] int32 on the device.
+ * 1 <= ncam <= 8, 1 <= J <= 64, 0 <= T <= 1048576, 0 <= npair <= 28, 0 <= D <= 64, W >= 1, 0 <= tau <= 4096, 0 <= switch_q <= 2^34,
+ *     min_count >= 0: within them no sum leaves int64.  T = 0 and npair = 0 launch nothing and return DF3D_OK.  DF3D_EINVAL before the
+ *     device is touched, with a message, for a value outside those ranges, a pair that is not 0 <= a < b < ncam, a workspace below
+ *     the query, a null, misaligned (8 bytes for float64 / int64, 4 for int32) or overlapping buffer.  No atomics: two calls on the
+ *     same input give the same bits.  Asynchronous on `stream`; the host arrays are copied before the call returns.
+ * ---------------------------------------------------------------------------------------------- */
+long long df3d_sync_work_bytes(int npair, long long nW, int D);
+int df3d_sync_pair_costs(const double* F_host, const int* pairs_host, int npair, const double* pts_px_dev, int ncam, int T, int J, int D,
+                         int W, double tau, long long* cost_dev, long long* count_dev, void* stream);
+int df3d_sync_paths(const long long* cost_dev, const long long* count_dev, int npair, long long nW, int D, long long switch_q,
+                    long long min_count, int* lag_dev, long long* path_cost_dev, double* margin_dev, void* work_dev, long long work_bytes,
+                    void* stream);
+int df3d_sync_apply(const double* pts_px_dev, const int* lag_cam_dev, int ncam, int T, int J, int W, double* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a7  bundle adjustment building blocks.   Replaces the arithmetic under pyba
  *     CameraNetwork.bundle_adjust(update_intrinsic=False, update_distort=False)
  *     (call site reference df3d/core.py:249).  Unknowns x = [ncam x (rvec, tvec)] ++ [npts x XYZ];
