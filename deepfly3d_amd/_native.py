@@ -234,6 +234,7 @@ PROTOTYPES = {
     "df3d_render_heatmap": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(ctypes.c_ubyte),
                                     POINTER(ctypes.c_ubyte), c_double, c_void_p, c_void_p]),
     "df3d_hg_step_desc": (c_int, [c_void_p, c_int, c_char_p, c_int, POINTER(c_int)]),
+    "df3d_hg_step_pooled": (c_int, [c_void_p, c_int]),
     "df3d_hg_forward_upto": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 

@@ -83,10 +83,13 @@ __device__ __forceinline__ void bt_t1_issue(const unsigned char* tin, const void
 // lane-derived register those kernels keep: hoisted out of the tile loop they are ~70 registers and ~50 spill lanes alive across phase 2 (the
 // empty asms hide their loop invariance).  An instruction between fp32 MFMAs or a live VGPR more is measurable in those kernels, which is why
 // they do not share the form above.
-template <int HW, int HALO, int ROWB, int NH>
+// K0, K1: the call requests the wave's pieces wave + 4 k of k = K0 .. K1 - 1 only (all of them by default).  A tile's halo in several calls is
+// how the fp32 Winograd tails meter it out between the MFMAs of a K loop, instead of one burst that fills the CU's memory queue.
+template <int HW, int HALO, int ROWB, int NH, int K0 = 0, int K1 = (HALO / 4 + 3) / 4>
 __device__ __forceinline__ void bt_t1_issue_persistent(const void* t1in, const void* zeros, int view, int tx0, int ty0, int H, int W, unsigned t1_addr,
                                                        int wave, unsigned uoff) {
     static_assert(NH == 1 || NH == 2, "one 64-channel half, or both");
+    static_assert(0 <= K0 && K0 < K1 && K1 <= (HALO / 4 + 3) / 4, "a range of the wave's pieces");
     int lane_ = (int)(uoff >> 4);
     asm volatile("" : "+v"(lane_));
     int wave_ = wave;
@@ -97,10 +100,10 @@ __device__ __forceinline__ void bt_t1_issue_persistent(const void* t1in, const v
     // the lane's halo pixel (hy, hx): divided by HW once, for the wave's first piece; from piece to piece it advances by 16 halo pixels, which
     // wraps at most once (HW >= 16).  Both halves of a piece share address and bounds test: the second is 256 bytes on (inside the image)
     static_assert(HW >= 16, "one wrap per step of 16 halo pixels");
-    const int hp0 = 4 * wave_ + q;
+    const int hp0 = 4 * (wave_ + 4 * K0) + q;
     int hy = hp0 / HW, hx = hp0 - hy * HW;
 #pragma unroll
-    for (int k = 0; k < (HALO / 4 + 3) / 4; ++k) {
+    for (int k = K0; k < K1; ++k) {
         const int pc = wave_ + 4 * k;
         if (pc < HALO / 4) {
             const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;

@@ -68,6 +68,8 @@ constexpr int WN_B3_OFF = WN_T1_OFF + WN_T1_BYTES;
 constexpr int WN_RING2_OFF = WN_B3_OFF + 1024 + 512;   // b3 [256] | b2 [128] | W3 ring slots 4 .. 7
 constexpr int WN_LDS_BYTES = WN_RING2_OFF + BR_RING_BYTES;
 static_assert(WN_LDS_BYTES <= 160 * 1024, "one workgroup per CU");
+constexpr int WN_HALO_K = (BT_HALO / 4 + 3) / 4;            // a wave's halo pieces per 64-channel half (12; the last is wave 0's alone)
+static_assert(WN_HALO_K % 4 == 0, "phase 3 requests the halo in four equal parts");
 static_assert(WN_PASSES % WN_UBUF == 0 && WN_UBUF >= 2, "a chunk's passes use the same buffers in every chunk");
 static_assert(WN_V_BYTES <= BR_RING_BYTES / 2, "V buffers 0, 1 in the W3 ring's slots 0 .. 3, buffer 2 in slots 4 .. 7");
 static_assert(WN_T2_BYTES <= WN_T1_BYTES, "t2 lives in the t1 region");
@@ -208,8 +210,9 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
     // lane index is recomputed from it where it is needed -- kept alive, `lane` itself sat in scratch and every reload was a vmcnt(0)
     unsigned uoff = (unsigned)(lane * 16);
     asm volatile("" : "+v"(uoff));
-    auto t1_issue = [&](int tx0, int ty0, int view) {
-        bt_t1_issue_persistent<BT_HW, BT_HALO, 512, 2>(p.t1in, p.zeros, view, tx0, ty0, p.H, p.W, t1_addr, wave, uoff);
+    // (k0, k1: the wave's pieces wave + 4 k of k0 <= k < k1 -- phase 3 requests the next tile's halo a few pieces at a time)
+    auto t1_issue = [&](auto k0_tag, auto k1_tag, int tx0, int ty0, int view) {
+        bt_t1_issue_persistent<BT_HW, BT_HALO, 512, 2, decltype(k0_tag)::value, decltype(k1_tag)::value>(p.t1in, p.zeros, view, tx0, ty0, p.H, p.W, t1_addr, wave, uoff);
     };
 
 
@@ -344,7 +347,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
     int vb = blockIdx.x;
     int tx0, ty0, view;
     tile_of(vb, tx0, ty0, view);
-    t1_issue(tx0, ty0, view);
+    t1_issue(std::integral_constant<int, 0>{}, std::integral_constant<int, WN_HALO_K>{}, tx0, ty0, view);
     b3_lds[tid] = L2 ? p.b3[tid] + p.bd[tid] : p.b3[tid];   // (L2: b3 + bd as ONE float add, as the direct kernels)
     if (tid < 128) b2_lds[tid] = p.b2[tid];
     bool first = true;
@@ -546,29 +549,51 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
         }
 
         br_barrier();   // every wave holds its t2 in registers: the t1 region may take the next tile's halo
-        if (has_next && !(WN_ABL & 32)) t1_issue(ntx0, nty0, nview);
-        // ---- residual values (and the ADD2 addends) of the whole tile, requested here -- behind the ring's first half (no ring wait has to let them pass), 16 000 MFMA cycles
-        //      in front of their first use (one wave per SIMD: nobody hides a load issued in an epilogue; the 512-register file has room) ----
+        const bool halo_next = has_next && !(WN_ABL & 32);
+        // ---- What phase 3 reads from memory -- the next tile's t1 halo (92 KB per workgroup), the residual values (and the ADD2 addends / UP values)
+        //      of each output half (64 + 16 KB) -- is requested A FEW OPERATIONS AT A TIME between the MFMAs of the K loops (`feed`, below), each
+        //      6 000 MFMA cycles or more in front of its first use.  Requested in one burst here (round 8) the 43 operations of a wave took 6 400
+        //      cycles to ISSUE: 256 workgroups in step ask for 40 MB within a microsecond, a CU holds some 70 KB of loads in flight, and a
+        //      vector-memory instruction that finds the queue full stalls its wave, which has nothing else to run (profiles/r09_tail_queue.txt:
+        //      the stamps show the time in the issue, not in any wait).  L2 keeps the halo burst: its x operands are plain loads, and no register
+        //      is free across its phase 3 for a second set of halo lane values ----
+        if constexpr (L2) {
+            if (halo_next) t1_issue(std::integral_constant<int, 0>{}, std::integral_constant<int, WN_HALO_K>{}, ntx0, nty0, nview);
+        }
         f32x4 xres[1][16];   // !L2: the CURRENT output half's residual values, [register r <-> pixel (r & 3) + 8 (r >> 2) + 4 half]: channels 128 nh + 4 l31 .. + 3
                              // L2: [0][2 k8 + jj] = the skip convolution's A operand, x[this lane's pixel][16 k8 + 8 jj + 4 half ..]
         f32x4 exv[4];        // ADD2: the addends / UP: the half-resolution values of the current half's four pixel quads
         static_assert(!(UP && ADD2), "one extra operand");
-        // (inline assembly: scalar base + lane offset, issued HERE -- half 0 now, 16 000 MFMA cycles in front of its epilogue; half 1 behind the
-        // first epilogue, into the same registers)
-        auto res_issue = [&](int nh) {
+        // (inline assembly: scalar base + lane offset, issued where it stands; a quarter g of output half nh: registers 4 g .. 4 g + 3 = pixels
+        // 8 g .. 8 g + 3 (+ 4 half) = row g >> 1, columns 8 (g & 1) .., and the extra operand of pixel quad g.  Half 1 goes into the registers
+        // of half 0, which epilogue a has read by then)
+        auto res_issue = [&](int nh, int g) {
+            if (WN_ABL & 64) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {   // registers 4 g .. 4 g + 3: pixels 8 g .. 8 g + 3 (+ 4 half) = row g >> 1, columns 8 (g & 1) ..
-                if (WN_ABL & 64) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) xres[0][4 * g + j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                } else {
-                    wn_uload4(*reinterpret_cast<f32x4(*)[4]>(&xres[0][4 * g]), xtile + ((size_t)(g >> 1) * p.W + 8 * (g & 1)) * (CIN * 4) + nh * 512, lane_full);
-                }
+                for (int j = 0; j < 4; ++j) xres[0][4 * g + j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            } else {
+                wn_uload4(*reinterpret_cast<f32x4(*)[4]>(&xres[0][4 * g]), xtile + ((size_t)(g >> 1) * p.W + 8 * (g & 1)) * (CIN * 4) + nh * 512, lane_full);
             }
-            if constexpr (ADD2 || UP) {
-#pragma unroll
-                for (int key = 0; key < 4; ++key)
-                    wn_xload1(exv[key], reinterpret_cast<const unsigned char*>(ADD2 ? p.add2 : p.in2) + htile + ((key & 1) + 4 * (key >> 1)) * (CO * 4) + nh * 512, lane_half);
+            if constexpr (ADD2 || UP)
+                wn_xload1(exv[g], reinterpret_cast<const unsigned char*>(ADD2 ? p.add2 : p.in2) + htile + ((g & 1) + 4 * (g >> 1)) * (CO * 4) + nh * 512, lane_half);
+        };
+        // W3 stage k8 (2 048 MFMA cycles) of output half nh is about to start.  First half: stages 0 .. 3 take a quarter of the next tile's halo
+        // each (3 x 2 LDS-DMA pieces), stages 2 .. 5 a quarter of the half's residual values each -- the halo FIRST, while few of the 64 + 16
+        // residual registers are taken: its lane values need a dozen registers, and with every residual register already a load's destination the
+        // UP and ADD2 kernels spilled.  The last residual quarter is 6 000 MFMA cycles ahead of its use.  Second half: stages 0 .. 3 take the
+        // residual quarters.  A wave's queue therefore holds, in issue order: halo (22, wave 0: 24; none behind the workgroup's last tile),
+        // from its third part on interleaved with residual half 0 (16 or 20) | ring set 1 (16) | the stores of epilogue a | residual half 1 |
+        // the stores of epilogue b -- the counted waits below follow from that
+        auto feed = [&](int nh, int k8) {
+            if constexpr (!L2) {
+                if (nh == 0 && k8 < 4 && halo_next) {
+                    if (k8 == 0) t1_issue(std::integral_constant<int, 0>{}, std::integral_constant<int, WN_HALO_K / 4>{}, ntx0, nty0, nview);
+                    if (k8 == 1) t1_issue(std::integral_constant<int, WN_HALO_K / 4>{}, std::integral_constant<int, WN_HALO_K / 2>{}, ntx0, nty0, nview);
+                    if (k8 == 2) t1_issue(std::integral_constant<int, WN_HALO_K / 2>{}, std::integral_constant<int, 3 * WN_HALO_K / 4>{}, ntx0, nty0, nview);
+                    if (k8 == 3) t1_issue(std::integral_constant<int, 3 * WN_HALO_K / 4>{}, std::integral_constant<int, WN_HALO_K>{}, ntx0, nty0, nview);
+                }
+                const int g = nh == 0 ? k8 - 2 : k8;
+                if (g >= 0 && g < 4) res_issue(nh, g);
             }
         };
         auto res_wait = [&](auto n_tag) {   // the counted wait that makes them valid, naming the registers (the epilogue's reads depend on it)
@@ -581,8 +606,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 xres[0][r] = *reinterpret_cast<const f32x4*>(xtile + (8 * r) * 4 + (unsigned)((((l31_3 >> 4) * p.W + (l31_3 & 15)) * CIN + 4 * half3) * 4));
-        } else {
-            res_issue(0);
         }
         BR_STAMP(4);
         // ---- phase 3: out = W3 relu(t2) + b3 + x  (bottleneck_ring_f32_kernel's exact-fp32 form: rows = the wave's pixels, columns = channels);
@@ -591,11 +614,19 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
         for (int nh = 0; nh < 2; ++nh) {
             f32x16 o[4];
             if (nh == 1) {
-                // the second half's stages were requested behind the first half's K loop(s); younger than them are only the first half's epilogue's
-                // operations -- at least its 16 output stores -- which need not have drained (operations retire in issue order)
-                // (!L2: and the second half's residual loads: 16 + 4 with an extra operand)
-                br_wait_vm(L2 ? 16 : (ADD2 || UP) ? 36 : 32);
+                // the second half's stages were requested behind the first half's K loop(s); younger than them are exactly the first half's
+                // epilogue's operations, which need not have drained (operations retire in issue order, and vmcnt counts stores): its 16 output
+                // stores and 4 more per pooled output the block writes (pool, pool_in) -- the second half's residual loads come behind this wait.
+                // The pooled outputs are the launch's (wave-uniform): one of three immediates; counted without them (round 8) the wait sat out the
+                // round trip of the epilogue's first 4 or 8 stores.  Older than ring set 1, hence complete behind this wait and published by the
+                // barrier: the next tile's halo
+                constexpr int young = 16;
+                const int pooled = (p.pool ? 1 : 0) + (!UP && !L2 && p.pool_in ? 1 : 0);
+                if (pooled == 0) br_wait_vm(young);
+                else if (pooled == 1) br_wait_vm(young + 4);
+                else br_wait_vm(young + 8);
                 br_barrier();
+                BR_STAMP(10);   // (the wait for ring set 1 on its own: stamp 7 is then the K loop alone)
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -610,6 +641,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
 #pragma unroll
                 for (int k8 = 0; k8 < 8; ++k8) {
                     const int tile = k8 >> 1, q2 = k8 & 1;
+                    if constexpr (!SKIP) feed(nh, k8);
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
@@ -643,10 +675,12 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
             BR_STAMP(5 + 2 * nh);
             if constexpr (!L2) {
                 if (!(WN_ABL & 64)) {
-                    if (nh == 0) res_wait(std::integral_constant<int, 16>{});   // younger: the sixteen stage pieces just requested
+                    // younger than residual half 0: the sixteen stage pieces just requested (the halo is older); than half 1: nothing
+                    if (nh == 0) res_wait(std::integral_constant<int, 16>{});
                     else res_wait(std::integral_constant<int, 0>{});
                 }
             }
+            if (nh == 0) BR_STAMP(9);   // (the wait for residual half 0 on its own: stamp 6 is then the epilogue alone)
             // epilogue: D[row = pixel (r&3) + 8(r>>2) + 4 half of the wave][col = channel nh*128 + 4 l31 + i]: register r of the four tiles = four
             // consecutive channels of one pixel
             // -- walked by 2x2 pixel quads (registers r0, r0 + 1, r0 + 8, r0 + 9: horizontal neighbour r ^ 1, vertical r ^ 8; one half-resolution pixel),
@@ -683,9 +717,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck_wino_f32_kernel(BtRingArgs 
                 if (p.pool) *reinterpret_cast<f32x4*>(reinterpret_cast<unsigned char*>(p.pool) + htile + hoff + lane_half) = max4(ov);
             }
             BR_STAMP(6 + 2 * nh);
-            if constexpr (!L2) {
-                if (nh == 0) res_issue(1);
-            }
         }
         if (!has_next) break;
         vb = vbn;

@@ -244,6 +244,13 @@ int df3d_hg_step_desc(const df3d_hg* h, int step, char* name_buf, int buflen, in
     return DF3D_OK;
 }
 
+int df3d_hg_step_pooled(const df3d_hg* h, int step) {
+    DF3D_CHECK_ARG(h, "null argument");
+    DF3D_CHECK_ARG(step >= 0 && step < (int)h->steps.size(), "step out of range");
+    const Step& st = h->steps[step];
+    return (st.pool_out >= 0 ? 1 : 0) | (st.pool_in >= 0 ? 2 : 0);
+}
+
 int df3d_hg_forward_upto(df3d_hg* h, const float* images_dev, int n, int upto, float* out_dev, void* workspace_dev,
                          size_t workspace_bytes, void* stream) {
     if (int rc = check_forward_args(h, images_dev, n, workspace_dev, workspace_bytes)) return rc;

@@ -983,6 +983,9 @@ int df3d_hg_num_steps(const df3d_hg* h);
 /* model-M1 bytes of plan step `step` over n views (the steps' values sum to df3d_hg_work()'s bytes) */
 double df3d_hg_step_m1_bytes(const df3d_hg* h, int step, int n);
 int df3d_hg_step_desc(const df3d_hg* h, int step, char* name_buf, int buflen, int* n_h_w_c /*[3]: h, w, c*/);
+/* the 2x2 max-pooled tensors plan step `step` writes beside its output: bit 0 the pooled output, bit 1 the pooled input (< 0: an error).
+ * A step whose output IS the pooled tensor (layer1 when nothing else reads its full-resolution output) writes nothing beside it: 0 */
+int df3d_hg_step_pooled(const df3d_hg* h, int step);
 int df3d_hg_forward_upto(df3d_hg* h, const float* images_dev, int n, int upto, float* out_dev, void* workspace_dev,
                          size_t workspace_bytes, void* stream);
 

@@ -15,7 +15,8 @@ img = torch.rand((views, 256, 512, 3), device=dev)
 steps = eng.steps()
 names = [n for n, _ in steps]
 buf = (ctypes.c_ulonglong * 12)()
-labels = ["prologue / tile entry", "first transform", "phase 2 (16 chunks)", "output transform + residual requests", "t2 crossing", "phase3a K", "epilogue a", "phase3b K", "epilogue b"]
+labels = ["prologue / tile entry", "first transform", "phase 2 (16 chunks)", "output transform + residual requests", "t2 crossing", "phase3a K", "epilogue a", "phase3b K", "epilogue b",
+          "wait: residual half 0 (res_wait)", "wait: ring set 1 + barrier", "-"]
 eng.forward(img); torch.cuda.synchronize()
 lib.df3d_dbg_ring_cycles.argtypes = [ctypes.c_void_p]
 
